@@ -24,7 +24,10 @@ profile, every counter-derived field is null and the note says why.
     hbm_achieved_gbs [GB/s] = fabric_bytes_per_ray x rays per launch / avg kernel duration  (peak 8000); hbm_frac = / 8000
     valu_issue_utilisation  = fraction of the SIMDs' cycles in which a VALU instruction issues (from the profile run)
 
-Prints one JSON line on rank 0.  --profile-run skips the CPU baseline and the side workloads (for use under rocprofv3).
+A plain run sets up, warms up, times --steps steps, writes the outputs of the last timed step if --dump-outputs DIR is given
+and prints one JSON line on rank 0.  Everything else it can measure or check (the FIXED64 bitwise proof, the energy window,
+the CPU baseline, the other workloads, the record interface, the effective-area RMS) runs only with --full; --profile-run
+then skips the CPU baseline and the side workloads (for use under rocprofv3), --no-proof the bitwise proof.
 """
 from __future__ import annotations
 
@@ -82,13 +85,22 @@ def parse():
     ap.add_argument("--headroom", type=int, default=0,
                     help="fixed64: bits of headroom (0 = the library's default, 27: one accumulator then lasts ~1e12 BabyIAXO rays; "
                          "31 carries 2.6e12, profiles/r04_v48_fixed64_long_run.txt)")
-    ap.add_argument("--profile-run", action="store_true", help="no CPU baseline / side workloads (run under rocprofv3)")
+    ap.add_argument("--full", action="store_true",
+                    help="behind the timed region also run the FIXED64 bitwise proof and (one GPU) the energy window, the CPU baseline "
+                         "and, for the headline workload, the other workloads, the record interface and the effective-area RMS; "
+                         "a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path hands its caller as float64 .npy files in DIR: image.npy "
+                         "(256 x 256) and summary.npy (the accumulator's scalars in _lib.ACC order); for the scan workloads one "
+                         "file per per-point array of split_mass_scan / split_angular_scan (<KEY>.npy) and shared.npy")
+    ap.add_argument("--profile-run", action="store_true", help="with --full: no CPU baseline / side workloads (run under rocprofv3)")
     ap.add_argument("--no-proof", action="store_true",
-                    help="skip the FIXED64 bitwise proof behind the timed region (counter profiles: its 2e8-ray launches of the same "
-                         "kernel would be averaged into the profiled ones, tools/pmc_summary.py)")
+                    help="with --full: skip the FIXED64 bitwise proof behind the timed region (counter profiles: its 2e8-ray launches "
+                         "of the same kernel would be averaged into the profiled ones, tools/pmc_summary.py)")
     ap.add_argument("--emit-bitwise-constants", metavar="PATH", default=None,
-                    help="one GPU: write the FIXED64 reference image's SHA-256, integer flux and the hash of the input tables to PATH "
-                         "(the committed copy is tests/golden/bench_bitwise_fixed64.json; a --gpus N run holds its reduced image to it)")
+                    help="one GPU: run the bitwise proof and write the FIXED64 reference image's SHA-256, integer flux and the hash "
+                         "of the input tables to PATH (the committed copy is tests/golden/bench_bitwise_fixed64.json; a --gpus N "
+                         "--full run holds its reduced image to it)")
     ap.add_argument("--preflight", action="store_true",
                     help="first contact with a multi-GPU node: only bring the process group up (RCCL), reduce one 512 KB buffer "
                          "once and print {world_size, backend, reduce_ms}; no tables, no rays")
@@ -510,7 +522,8 @@ def main():
     # the result, not only the rate: a fixed id range traced by all ranks in FIXED64 against rank 0 alone (every rank takes part)
     D.heartbeat("bitwise proof")
     proof = None
-    if scan_masses is None and scan_angles is None and full.fluxRadiusCDF is not None and not args.no_proof:
+    if ((args.full or args.emit_bitwise_constants) and not args.no_proof and scan_masses is None and scan_angles is None
+            and full.fluxRadiusCDF is not None):
         proof = bitwise_proof(rt, full, flags, rank, world, dev, seed, D, restore=(args.accumulation, args.headroom))
     proof_failed = False
 
@@ -554,6 +567,8 @@ def main():
                           "ray_mass_evaluations_per_s": total_rays * SCAN_MASSES / elapsed_s,
                           "relative_flux": [round(float(x), 6) for x in per_mass["SUM_WEIGHTS"] / per_mass["SUM_WEIGHTS"].max()],
                           "relative_error_at_resonance": float(np.sqrt(per_mass["SUM_WEIGHTS_SQ"][k0]) / per_mass["SUM_WEIGHTS"][k0])}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, host, scan_masses, scan_angles)
         value = total_rays / elapsed_s
         avg_kernel_s = kernel_ms / 1e3 / max(1, n_launch)
         out = {
@@ -597,7 +612,7 @@ def main():
             out["mass_scan"] = scan_block
         if ascan_block is not None:
             out["angular_scan"] = ascan_block
-        if world == 1 and not args.profile_run:
+        if world == 1 and args.full and not args.profile_run:
             en = energy_block(step, stream, float(rays_rank))
             out["roofline"].update({"socket_power_w": en["socket_power_w"], "sclk_mhz": en["sclk_mhz"], "nj_per_ray": en["nj_per_ray"]})
             if en["sclk_mhz"] and out["roofline"]["achieved"] is not None:
@@ -631,6 +646,27 @@ def main():
         # not a measurement of this path: non-zero exit (the self-launcher hands rank 0's code on)
         sys.stderr.write("bench.py: bitwise proof FAILED: %s\n" % json.dumps(proof))
         raise SystemExit(5)
+
+
+def dump_outputs(directory: str, host, scan_masses, scan_angles):
+    """--dump-outputs: the finalized accumulator as the timed path leaves it after its last step (every timed step adds into it),
+    split as the library's Python API hands it to a caller, one float64 .npy file per array.  The seed and the ray ids are
+    fixed, so two builds run with the same arguments can be compared file for file."""
+    import numpy as np
+    import solaraxionraytracing_amd as sa
+    from solaraxionraytracing_amd import _lib as L
+    n_img = 256 * 256
+    if scan_masses is not None or scan_angles is not None:
+        per_point, shared = (sa.split_mass_scan(host, SCAN_MASSES) if scan_masses is not None
+                             else sa.split_angular_scan(host, SCAN_ANGLES))
+        arrays = dict(per_point)
+        arrays["shared"] = np.array(list(shared.values()))
+    else:
+        arrays = {"image": host[:n_img].reshape(256, 256),
+                  "summary": host[n_img:n_img + len(L.ACC)]}     # the keys of _lib.ACC are the slots 0 .. len(ACC) - 1
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def energy_block(step, stream, rays_per_step: float, seconds: float = 5.0):

@@ -2,6 +2,7 @@
 HDF5 reflectivity schema, solar-model CSV)."""
 import os
 import subprocess
+import tempfile
 
 import numpy as np
 import pytest
@@ -120,11 +121,13 @@ def test_reference_defaults_build_the_babyiaxo_setup_and_trace_on_the_cpu(tmp_pa
 
 
 def _h5_available():
-    try:
-        tables.write_reflectivity_h5("/tmp/_sart_probe.h5", tables.analytic_reflectivity_grid(1, 4, 4))
-        return True
-    except L.SartError:
-        return False
+    # a private directory: a probe file another user left at a fixed path would read as "no libhdf5"
+    with tempfile.TemporaryDirectory() as d:
+        try:
+            tables.write_reflectivity_h5(os.path.join(d, "probe.h5"), tables.analytic_reflectivity_grid(1, 4, 4))
+            return True
+        except L.SartError:
+            return False
 
 
 def test_config_toml_drives_init_full_setup(tmp_path):

@@ -390,7 +390,7 @@ def test_bench_two_rank_rehearsal(scaling):
     env = dict(os.environ, SART_BENCH_BACKEND="gloo", SART_BENCH_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29547" if scaling == "weak" else "29549", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--rays-per-step", "2e7", "--profile-run", "--scaling", scaling]
+           "--warmup", "1", "--rays-per-step", "2e7", "--full", "--profile-run", "--scaling", scaling]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
