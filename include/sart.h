@@ -592,6 +592,34 @@ int sart_trace_angular_scan(sart_context* ctx, const sart_trace_params_t* params
 int sart_finalize_angular_scan_device(sart_context* ctx, const sart_trace_params_t* params, int32_t n_angles,
                                       const void* scan_fixed_device, double* out_f64_device);
 
+/*
+ * The fused angular scan with a complete result set per angle.  performAngularScan (:2778-2815) runs calculateFluxFractions at
+ * every angle, and without --noPlots each angle writes its own focal-plane image (plotHeatmap :857-921, suffix "_angle_{a:.2f}")
+ * with its containment radii (:2459-2527): the telescope's off-axis point-spread function.  These entry points are
+ * sart_trace_angular_scan_device plus, per angle k, the accumulator a sart_trace_histogram_device launch fills:
+ *   scan_acc_device   the scan rows of sart_trace_angular_scan_device (same layout, same values: bit for bit in FIXED64)
+ *   blocks_device     n_angles consecutive blocks of sart_accumulator_len(nx, ny) slots, or sart_accumulator_len_spectra(nx, ny,
+ *                     n_radial_bins, n_energies) with params->spectra - image, SART_ACC_* scalars, spectra: the layout above.
+ * Block k holds what sart_trace_histogram_device would after sart_set_telescope_angles(ctx, NaN, turned_y_deg[k]) on the same params
+ * and ray ids: bit for bit in SART_ACCUM_FIXED64 (raw int64 slots, both limbs of every two-limb sum, every counter; an angle that
+ * leaves the telescope unrotated - turned x and y both 0 - agrees to ~1e-13, as in the scan), up to the summation order in
+ * SART_ACCUM_F64.  params->accumulate as in the scan (0: rows and blocks are zeroed first).  FIXED64: the quanta are the scan's and
+ * are frozen for the context like a histogram launch's (an accumulate == 1 call whose frozen quanta differ: SART_ERR_INVALID_ARGUMENT);
+ * a raw block is finalized or rolled over one block at a time by sart_finalize_accumulator_device /
+ * sart_rollover_accumulator_device with the same params, whose checks (resolution, conservation) then hold per angle; ranks reduce
+ * rows and blocks as int64 sums.  Angles, groups of up to 32 per launch, stage A0 and the common random numbers as in the scan.
+ * SART_ERR_INVALID_ARGUMENT, with the context unchanged: image_nx or image_ny 0 (the flux-only scan is sart_trace_angular_scan),
+ * an angle non-finite or outside (-90, 90), n_angles < 1, a NULL pointer, an invalid image or spectra specification.
+ * Cost: the scan's trace plus, per passed (ray, angle), one global pixel atomic (no LDS image tile: 32 of them do not fit beside the
+ * rings) and three LDS atomics (position sums, folded per workgroup); params->spectra adds five global atomics.
+ * Asynchronous on the context's stream.
+ */
+int sart_trace_angular_scan_images_device(sart_context* ctx, const sart_trace_params_t* params, const double* turned_y_deg,
+                                          int32_t n_angles, double* scan_acc_device, double* blocks_device);
+/* Blocking form with HOST outputs of sart_angular_scan_len(n_angles) and n_angles block lengths doubles (finalized in FIXED64 mode). */
+int sart_trace_angular_scan_images(sart_context* ctx, const sart_trace_params_t* params, const double* turned_y_deg,
+                                   int32_t n_angles, double* scan_out_host, double* blocks_out_host);
+
 /* ---- multi-GPU ---------------------------------------------------------- */
 /*
  * Sum the fused accumulators of n contexts (one per GPU of this process) into the one of contexts[root]:

@@ -150,6 +150,12 @@ proc sart_trace_angular_scan*(ctx: ptr SartContext, p: ptr SartTraceParams, turn
                               scanOutHost: ptr cdouble): cint {.importc, header: sartH.}
 proc sart_finalize_angular_scan_device*(ctx: ptr SartContext, p: ptr SartTraceParams, nAngles: int32, scanFixedDevice: pointer,
                                         outF64Device: ptr cdouble): cint {.importc, header: sartH.}
+## the same with a complete accumulator per angle (image, scalars, spectra: what performAngularScan's per-angle
+## calculateFluxFractions plots): the scan rows plus nAngles consecutive blocks of sart_accumulator_len[_spectra] slots
+proc sart_trace_angular_scan_images_device*(ctx: ptr SartContext, p: ptr SartTraceParams, turnedYDeg: ptr cdouble, nAngles: int32,
+                                            scanAccDevice: ptr cdouble, blocksDevice: ptr cdouble): cint {.importc, header: sartH.}
+proc sart_trace_angular_scan_images*(ctx: ptr SartContext, p: ptr SartTraceParams, turnedYDeg: ptr cdouble, nAngles: int32,
+                                     scanOutHost: ptr cdouble, blocksOutHost: ptr cdouble): cint {.importc, header: sartH.}
 proc sart_reduce_across_devices*(contexts: ptr ptr SartContext, accumulatorsDevice: ptr ptr cdouble, n: int32, nDoubles: csize_t,
                                  root: int32): cint {.importc, header: sartH.}
 proc sart_enable_kernel_timing*(ctx: ptr SartContext, enable: cint): cint {.importc, header: sartH.}

@@ -2,6 +2,7 @@
 
     python -m solaraxionraytracing_amd [--ignoreDetWindow] [--ignoreGasAbs] [--ignoreConvProb] [--ignoreReflection]
         [--xrayTest] [--detectorInstall] [--magnet] [--angularScanMin A --angularScanMax B --numAngularScanPoints N]
+        [--fusedAngularScan] [--angularImages]
         [--noPlots] [--config FILE | --configPath DIR]  [--rays N] [--seed S] [--outpath DIR]
         [--massScanMin M0 --massScanMax M1 --numMassScanPoints K]     (not in the reference: see below)
 
@@ -21,7 +22,8 @@ import sys
 import numpy as np
 
 from . import _lib, config as cfgmod
-from .raytracer import RayTracer, containment_radii, initFullSetup, performAngularScan, performAxionMassScan, write_image_csv
+from .raytracer import (RayTracer, angle_image_names, containment_radii, initFullSetup, performAngularScan, performAxionMassScan,
+                        write_image_csv)
 
 WINDOW_YEAR = {_lib.DK_INGRID2017: "2017", _lib.DK_INGRID2018: "2018", _lib.DK_INGRIDIAXO: "IAXO"}   # WindowYearKind, :1468-1484
 
@@ -38,6 +40,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--fusedAngularScan", action="store_true",
                     help="extension: the angular scan through the fused kernel (sart_trace_angular_scan: every ray sampled once and "
                          "turned through every angle, the same rays for all angles) instead of a re-trace on fresh rays per angle")
+    ap.add_argument("--angularImages", action="store_true",
+                    help="extension: the angular scan also writes every angle's focal-plane image, axion_image_{year}_angle_{a:.2f}.csv "
+                         "(the reference's per-angle calculateFluxFractions without --noPlots), and prints its counters and means; "
+                         "angles that share a name at two decimals get the fewest decimals that tell them apart (equal angles: "
+                         "their index behind the name)")
     ap.add_argument("--massScanMin", type=float, default=0.0, help="eV (extension: fused axion-mass scan)")
     ap.add_argument("--massScanMax", type=float, default=0.0, help="eV")
     ap.add_argument("--numMassScanPoints", type=int, default=32)
@@ -57,6 +64,20 @@ def setup_from_args(args):
     if path:
         return cfgmod.init_full_setup_from_config(path, flags), flags
     return initFullSetup(flags=flags), flags
+
+
+def write_result(path, img, s, spec, chip_max):
+    """The numbers of generateResultPlots (:2252-2257, :2276-2278, :2459-2527) and the heat map's CSV (:885-921)."""
+    print("Passed axions", int(s["N_PASSED"]))
+    print("Passed axions until the Window", int(s["N_PASSED_TILL_WINDOW"]))
+    print("Number of X-rays hitting nickel:", int(s["N_HIT_NICKEL"]))
+    if s["N_PASSED"] > 0:   # means of the passed rays' detector coordinates (:2276-2278)
+        print("mean x %.6f mean y %.6f mean r %.6f" % tuple(s[k] / s["N_PASSED"] for k in ("SUM_X", "SUM_Y", "SUM_R")))
+    r1, r2, r1w, r2w = containment_radii(spec)
+    print("rSigma1 %.4f rSigma2 %.4f rSigma1W %.4f rSigma2W %.4f" % (r1, r2, r1w, r2w))
+    flux = write_image_csv(path, img, chip_max, r1w, r2w)
+    print("The total flux", flux)
+    print("wrote", path)
 
 
 def main(argv=None) -> int:
@@ -82,23 +103,19 @@ def main(argv=None) -> int:
         elif args.angularScanMin == args.angularScanMax:
             # calculateFluxFractions + the numbers of generateResultPlots (:2252-2257, :2459-2527, :885-921)
             img, s, spec = rt.trace_spectra(n, seed=args.seed, flags=flags)
-            print("Passed axions", int(s["N_PASSED"]))
-            print("Passed axions until the Window", int(s["N_PASSED_TILL_WINDOW"]))
-            print("Number of X-rays hitting nickel:", int(s["N_HIT_NICKEL"]))
-            if s["N_PASSED"] > 0:   # means of the passed rays' detector coordinates (:2276-2278)
-                print("mean x %.6f mean y %.6f mean r %.6f" % tuple(s[k] / s["N_PASSED"] for k in ("SUM_X", "SUM_Y", "SUM_R")))
-            r1, r2, r1w, r2w = containment_radii(spec)
-            print("rSigma1 %.4f rSigma2 %.4f rSigma1W %.4f rSigma2W %.4f" % (r1, r2, r1w, r2w))
             year = WINDOW_YEAR.get(full.setup.detector_kind, "IAXO")
-            out = os.path.join(args.outpath, "axion_image_%s.csv" % year)
-            flux = write_image_csv(out, img, full.setup.chip_x_max, r1w, r2w)
-            print("The total flux", flux)
-            print("wrote", out)
+            write_result(os.path.join(args.outpath, "axion_image_%s.csv" % year), img, s, spec, full.setup.chip_x_max)
         else:
             res = performAngularScan(rt, args.angularScanMin, args.angularScanMax, args.numAngularScanPoints, n, seed=args.seed, flags=flags,
-                                     fused=args.fusedAngularScan, errors=args.fusedAngularScan)
+                                     fused=args.fusedAngularScan, errors=args.fusedAngularScan, images=args.angularImages)
             angles, fluxes, rel = res[:3]
             errs = res[3] if args.fusedAngularScan else [float("nan")] * len(angles)
+            if args.angularImages:   # performAngularScan :2787: calculateFluxFractions(suffix = "_angle_{angle:.2f}") per angle
+                imgs, summ, spec = res[-1]
+                year = WINDOW_YEAR.get(full.setup.detector_kind, "IAXO")
+                for a, name, img, s, sp in zip(angles, angle_image_names(year, angles), imgs, summ, spec):
+                    print("angle %r deg:" % float(a))
+                    write_result(os.path.join(args.outpath, name), img, s, sp, full.setup.chip_x_max)
             out = os.path.join(args.outpath, "angular_scan_telescope_y.csv")   # the reference only saves the PDF of this curve
             with open(out, "w") as f:
                 f.write("Angles [deg],Flux fraction,relative flux,flux error\n")

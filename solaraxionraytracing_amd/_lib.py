@@ -218,6 +218,8 @@ SART_SYMBOLS = {
     "sart_trace_angular_scan_device": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, C.c_void_p]),
     "sart_trace_angular_scan": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, _dp]),
     "sart_finalize_angular_scan_device": (C.c_int, [C.c_void_p, _P(TraceParams), _i, C.c_void_p, C.c_void_p]),
+    "sart_trace_angular_scan_images_device": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, C.c_void_p, C.c_void_p]),
+    "sart_trace_angular_scan_images": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, _dp, _dp]),
     "sart_reduce_across_devices": (C.c_int, [_P(C.c_void_p), _P(C.c_void_p), _i, C.c_size_t, _i]),
     "sart_enable_kernel_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "sart_get_kernel_timing": (C.c_int, [C.c_void_p, _dp, _P(C.c_int64)]),

@@ -40,6 +40,9 @@ void launch_finalize_scan(const void* in, double* out, int n_masses, const doubl
 void launch_trace_angular_scan(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, const AScanArgs& AN, double* rows,
                                double* shared_row, int n_blocks, hipStream_t stream, bool fast, bool fixed);
 int angular_scan_blocks_per_cu(bool fast);
+void launch_ascan_images(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, const AScanArgs& AN, double* img_partials,
+                         double* rows, double* shared_row, int n_blocks, hipStream_t stream, bool fast, bool fixed);
+int ascan_images_blocks_per_cu(bool fast);
 int histogram_block_of(int variant);
 void launch_trace_records(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, sart_axion_t* out, int n_blocks,
                           hipStream_t stream, const double* uniforms_dev);
@@ -255,6 +258,9 @@ struct sart_context {
   // fused mass scan: per-workgroup per-mass partial sums, scratch accumulators of the blocking call
   DevBuf<double> d_scan_partials, d_scan, d_scan_fin;
   DevBuf<double> d_ascan_partials;   // fused angular scan: per-workgroup per-angle partial sums
+  DevBuf<double> d_aimg_partials;    // ... with images: per-angle per-workgroup scalars
+  DevBuf<double> d_aimg;             // ... scratch blocks of the blocking form
+  int blocks_per_cu_aimg[2] = {0, 0};
 
   // timing
   bool timing = false;
@@ -2151,6 +2157,133 @@ int sart_trace_angular_scan(sart_context* c, const sart_trace_params_t* p, const
     src = c->d_scan_fin.p;
   }
   SART_HIP(hipMemcpyAsync(out_host, src, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  SART_HIP(hipStreamSynchronize(c->stream));
+  return status_take(c);
+}
+
+// ---- fused angular scan with per-angle images (include/sart.h) --------------------------------------------------------------------
+namespace {
+
+// Everything that can make an image-scan call invalid, checked before the call changes anything (scratch, quanta, accumulators).
+int aimg_check(sart_context* c, const sart_trace_params_t* p, const double* turned_y_deg, int32_t n_angles, const void* scan, const void* blocks) {
+  if (int rc = ascan_check(c, p, n_angles)) return rc;
+  if (!turned_y_deg || !scan || !blocks) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (p->image_nx < 1 || p->image_ny < 1)
+    return fail(SART_ERR_INVALID_ARGUMENT, "the image scan needs image_nx, image_ny >= 1 (the flux-only scan is sart_trace_angular_scan)");
+  for (int32_t k = 0; k < n_angles; ++k)
+    if (!std::isfinite(turned_y_deg[k]) || !(std::fabs(turned_y_deg[k]) < 90.0))
+      return fail(SART_ERR_INVALID_ARGUMENT, "telescope angles must be finite and inside (-90, 90) degrees");
+  if (p->spectra && (p->n_radial_bins < 1 || !c->have_solar)) return fail(SART_ERR_INVALID_ARGUMENT, "invalid spectra specification");
+  if (acc_len_of(c, p) > 0xFFFFFFFFull) return fail(SART_ERR_INVALID_ARGUMENT, "accumulator block too large for the image scan");
+  return 0;
+}
+
+}  // namespace
+
+int sart_trace_angular_scan_images_device(sart_context* c, const sart_trace_params_t* p, const double* turned_y_deg, int32_t n_angles,
+                                          double* scan_dev, double* blocks_dev) {
+  if (int rc = aimg_check(c, p, turned_y_deg, n_angles, scan_dev, blocks_dev)) return rc;
+  SART_HIP(hipSetDevice(c->device));
+  if (int rc = refresh_derived(c)) return rc;
+  if (int rc = sync_blob(c)) return rc;
+  TraceArgs a;
+  if (int rc = make_args(c, p, a)) return rc;
+  const size_t block_len = acc_len_of(c, p);
+  a.fx_scale_w = a.fx_scale_w2 = 0.0;
+  const bool fixed = c->accum_mode == SART_ACCUM_FIXED64;
+  if (fixed) {
+    // One quantum for the scan rows and the blocks: the scan's (a function of setup, tables, flags and headroom), frozen like a
+    // histogram launch's so that sart_finalize_accumulator_device / sart_rollover_accumulator_device read the blocks with it.
+    const double b = weight_bound_of(c, p->flags, c->params.gas_dm2_abs);
+    QuantaExp qe;
+    if (int rc = quanta_exp_of(c, b, qe)) return rc;
+    if (p->accumulate && c->quanta_frozen && (c->weight_exp != qe.w || c->weight_sq_exp != qe.w2))
+      return fail(SART_ERR_INVALID_ARGUMENT, "FIXED64: the quanta frozen for the accumulator are not the scan's (setup, flags or mass "
+                                             "changed since its accumulate == 0 launch)");
+    if (int rc = freeze_quanta(c, b, true)) return rc;
+    a.fx_scale_w = std::ldexp(1.0, -qe.w);
+    a.fx_scale_w2 = std::ldexp(1.0, -qe.w2);
+  }
+  if (!p->accumulate) {
+    SART_HIP(hipMemsetAsync(scan_dev, 0, sart_angular_scan_len(n_angles) * sizeof(double), c->stream));
+    SART_HIP(hipMemsetAsync(blocks_dev, 0, static_cast<size_t>(n_angles) * block_len * sizeof(double), c->stream));
+  }
+  if (p->n_rays == 0) return 0;
+  const DevParams& P = c->params;
+  const bool fast = !P.test_active && !(P.telescope_kind == SART_TK_XMM && P.inner_blocks < 0) && !c->knobs.force_generic && !P.stage_gas;
+  HotA hot = c->hot;   // stage A0 zones per launch group, as in sart_trace_angular_scan_device
+  hot.rotated = 1;
+  int& bpc = c->blocks_per_cu_aimg[fast ? 1 : 0];
+  if (bpc == 0) {
+    bpc = std::max(1, ascan_images_blocks_per_cu(fast));
+    if (c->knobs.hist_blocks_per_cu > 0) bpc = c->knobs.hist_blocks_per_cu;
+  }
+  const int32_t n_groups = (n_angles + kAScanMaxAngles - 1) / kAScanMaxAngles;
+  a.replica_mask = 0u;
+  a.replica_stride = static_cast<uint32_t>(block_len);
+  a.partials = nullptr;
+  for (uint64_t done = 0; done < p->n_rays;) {   // pieces of at most 2^31 rays (32-bit ray indices inside a launch)
+    const uint64_t n = std::min<uint64_t>(p->n_rays - done, 1ull << 31);
+    a.n_rays = n;
+    a.ray_id_offset = p->ray_id_offset + done;
+    const int n_blocks = grid_for(n, c->n_cu, bpc, 1024);
+    const size_t rows_need = std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4);
+    if (c->d_ascan_partials.n < static_cast<size_t>(n_blocks) * kAScanMaxAngles * kAScanPartialSlots ||
+        c->d_aimg_partials.n < static_cast<size_t>(n_blocks) * kAScanMaxAngles * SART_ACC_COUNT) {
+      SART_HIP(hipStreamSynchronize(c->stream));
+      if (int rc = c->d_ascan_partials.reserve(rows_need * kAScanMaxAngles * kAScanPartialSlots)) return rc;
+      if (int rc = c->d_aimg_partials.reserve(rows_need * kAScanMaxAngles * SART_ACC_COUNT)) return rc;
+    }
+    for (int32_t g = 0, k0 = 0; g < n_groups; ++g) {   // balanced groups, as in the flux-only scan
+      AScanArgs an;
+      std::memset(&an, 0, sizeof an);
+      an.n_angles = n_angles / n_groups + (g < n_angles % n_groups ? 1 : 0);
+      an.partials = c->d_ascan_partials.p;
+      double tilt_max = 0.0;
+      for (int k = 0; k < an.n_angles; ++k) {
+        an.a[k] = ascan_angle_of(c, turned_y_deg[k0 + k]);
+        const double t = tilt_bound_of(c->setup, turned_y_deg[k0 + k]);
+        tilt_max = (t < 0.0 || tilt_max < 0.0) ? -1.0 : std::max(tilt_max, t);
+      }
+      if (!c->knobs.no_early_reject) build_zones(c->setup, P, c->n_radii, hot, tilt_max);
+      double* const rows = scan_dev + static_cast<size_t>(k0) * SART_ASCAN_ROW;
+      double* const shared = (k0 == 0) ? scan_dev + static_cast<size_t>(n_angles) * SART_ASCAN_ROW : nullptr;
+      a.replicas = blocks_dev + static_cast<size_t>(k0) * block_len;   // the group's first block; angle k of the group: + k block_len
+      {
+        TimedLaunch tl(c);
+        launch_ascan_images(hot, c->hotb, c->d_blob.p, a, an, c->d_aimg_partials.p, rows, shared, n_blocks, c->stream, fast, fixed);
+      }
+      SART_HIP(hipGetLastError());
+      k0 += an.n_angles;
+    }
+    done += n;
+  }
+  return 0;
+}
+
+int sart_trace_angular_scan_images(sart_context* c, const sart_trace_params_t* p, const double* turned_y_deg, int32_t n_angles,
+                                   double* scan_out_host, double* blocks_out_host) {
+  if (int rc = aimg_check(c, p, turned_y_deg, n_angles, scan_out_host, blocks_out_host)) return rc;
+  SART_HIP(hipSetDevice(c->device));
+  const size_t len = sart_angular_scan_len(n_angles), block_len = acc_len_of(c, p);
+  if (int rc = c->d_scan.resize(len)) return rc;
+  if (int rc = c->d_aimg.reserve(static_cast<size_t>(n_angles) * block_len)) return rc;
+  sart_trace_params_t q = *p;
+  q.accumulate = 0;   // the blocking form has no accumulator the caller could add into
+  if (int rc = sart_trace_angular_scan_images_device(c, &q, turned_y_deg, n_angles, c->d_scan.p, c->d_aimg.p)) return rc;
+  const double* src = c->d_scan.p;
+  if (c->accum_mode == SART_ACCUM_FIXED64) {   // rows and blocks hold integers: finalize (each block in place, with its own checks)
+    if (int rc = c->d_scan_fin.resize(len)) return rc;
+    if (int rc = sart_finalize_angular_scan_device(c, p, n_angles, c->d_scan.p, c->d_scan_fin.p)) return rc;
+    src = c->d_scan_fin.p;
+    for (int32_t k = 0; k < n_angles; ++k) {
+      double* const blk = c->d_aimg.p + static_cast<size_t>(k) * block_len;
+      if (int rc = sart_finalize_accumulator_device(c, p, blk, blk)) return rc;
+    }
+  }
+  SART_HIP(hipMemcpyAsync(scan_out_host, src, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  SART_HIP(hipMemcpyAsync(blocks_out_host, c->d_aimg.p, static_cast<size_t>(n_angles) * block_len * sizeof(double), hipMemcpyDeviceToHost,
+                          c->stream));
   SART_HIP(hipStreamSynchronize(c->stream));
   return status_take(c);
 }

@@ -438,6 +438,39 @@ class RayTracer:
         _lib.check(self.lib.sart_finalize_angular_scan_device(self.handle, C.byref(params), int(n_angles), C.c_void_p(raw_ptr),
                                                               C.c_void_p(out_ptr if out_ptr is not None else raw_ptr)))
 
+    def trace_angular_scan_images(self, turned_y_deg, n_rays: int, seed: int = 299792458, ray_id_offset: int = 0,
+                                  flags: int | None = None, image_n: int = 256, spectra: bool = False, n_radial_bins: int = 10_000,
+                                  radial_max: float = 10.0):
+        """The fused angular scan with a complete accumulator per angle (sart_trace_angular_scan_images): per angle what
+        trace_histogram / trace_spectra return after set_telescope_angles(turned_y_deg=a) on the same rays.  Returns (images
+        [K, ny, nx], list of K summary dicts keyed like SART_ACC_*, list of K split_spectra dicts or None, the scan rows as
+        trace_angular_scan returns them)."""
+        angles = np.ascontiguousarray(turned_y_deg, dtype=np.float64)
+        p = self.angular_scan_images_params(n_rays, seed, ray_id_offset, flags, image_n, spectra, n_radial_bins, radial_max)
+        n_e1 = self.full.energies.size + 1
+        blen = image_n * image_n + _lib.SART_ACC_COUNT + (2 * n_radial_bins + 3 * n_e1 if spectra else 0)
+        rows = np.empty(angular_scan_len(angles.size))
+        blocks = np.empty((angles.size, blen))
+        _lib.check(self.lib.sart_trace_angular_scan_images(self.handle, C.byref(p), _lib.as_dp(angles), angles.size, _lib.as_dp(rows),
+                                                           _lib.as_dp(blocks)))
+        return split_image_blocks(blocks, image_n, n_radial_bins if spectra else 0, n_e1, radial_max) + (split_angular_scan(rows, angles.size),)
+
+    def angular_scan_images_params(self, n_rays: int, seed: int = 299792458, ray_id_offset: int = 0, flags: int | None = None,
+                                   image_n: int = 256, spectra: bool = False, n_radial_bins: int = 10_000, radial_max: float = 10.0,
+                                   accumulate: bool = False) -> TraceParams:
+        """The TraceParams of trace_angular_scan_images (for the _device form)."""
+        p = self.trace_params(n_rays, seed, ray_id_offset, flags, image_n, accumulate)
+        if spectra:
+            p.spectra, p.n_radial_bins, p.radial_max = 1, n_radial_bins, radial_max
+        return p
+
+    def trace_angular_scan_images_device(self, params: TraceParams, turned_y_deg, scan_acc_ptr: int, blocks_ptr: int):
+        """Asynchronous form: adds into a device scan accumulator of angular_scan_len(K) slots and K device accumulator blocks
+        (raw int64 in fixed64 mode; finalize block by block with finalize_accumulator_device)."""
+        angles = np.ascontiguousarray(turned_y_deg, dtype=np.float64)
+        _lib.check(self.lib.sart_trace_angular_scan_images_device(self.handle, C.byref(params), _lib.as_dp(angles), angles.size,
+                                                                  C.c_void_p(scan_acc_ptr), C.c_void_p(blocks_ptr)))
+
     def trace_flux(self, n_rays: int, seed: int = 299792458, ray_id_offset: int = 0, flags: int | None = None):
         """Flux-only launch (image_nx = image_ny = 0, include/sart.h): the summary of trace_histogram without an image."""
         p = self.trace_params(n_rays, seed, ray_id_offset, flags, 0, False)
@@ -523,6 +556,31 @@ def split_angular_scan(acc: np.ndarray, n_angles: int):
     return per_angle, shared
 
 
+def split_image_blocks(blocks: np.ndarray, image_n: int, n_radial_bins: int, n_e1: int, radial_max: float = 10.0):
+    """(images [K, ny, nx], K summary dicts, K split_spectra dicts or None) from K finalized accumulator blocks of
+    image_n x image_n pixels (n_radial_bins = 0: without spectra)."""
+    blocks = np.asarray(blocks, dtype=np.float64)
+    n_img = image_n * image_n
+    images = blocks[:, :n_img].reshape(-1, image_n, image_n).copy()
+    summaries = [{k: float(b[n_img + i]) for k, i in _lib.ACC.items()} for b in blocks]
+    spectra = [split_spectra(b[n_img + _lib.SART_ACC_COUNT:], n_radial_bins, n_e1, radial_max) for b in blocks] if n_radial_bins else None
+    return images, summaries, spectra
+
+
+def angle_image_names(year: str, angles) -> list:
+    """File names of the per-angle images of an angular scan: `axion_image_{year}_angle_{a:.2f}.csv` as plotHeatmap's suffix
+    (raytracer.nim:2787) writes them.  Where two angles give the same name at two decimals, every name takes the fewest decimals
+    (up to 17) that make them distinct; angles that are equal to the last bit keep that name with `_{k}` (their index) behind it."""
+    angles = [float(a) for a in angles]
+    values = set(angles)
+    d = next((d for d in range(2, 18) if len({"%.*f" % (d, a) for a in values}) == len(values)), 17)
+    tags = ["%.*f" % (d, a) for a in angles]
+    counts = {}
+    for t in tags:
+        counts[t] = counts.get(t, 0) + 1
+    return ["axion_image_%s_angle_%s%s.csv" % (year, t, "_%d" % k if counts[t] > 1 else "") for k, t in enumerate(tags)]
+
+
 def calculateFluxFractions(tracer: RayTracer, n_rays: int = 1_000_000, seed: int = 299792458,
                            ray_id_offset: int = 0):
     """calculateFluxFractions (raytracer.nim:2755-2776) in histogram form: NumberOfPointsSun rays ->
@@ -570,16 +628,21 @@ def performAxionMassScanHostLoop(tracer: RayTracer, masses_ev, n_rays_per_mass: 
 
 def performAngularScan(tracer: RayTracer, angularScanMin: float, angularScanMax: float, numAngularScanPoints: int = 50,
                        n_rays_per_angle: int = 1_000_000, seed: int = 299792458, flags: int | None = None,
-                       angles=None, ray_id_offset: int = 0, fused: bool = False, errors: bool = False):
+                       angles=None, ray_id_offset: int = 0, fused: bool = False, errors: bool = False, images: bool = False):
     """performAngularScan (raytracer.nim:2778-2802) through the C++ host driver: returns (angles, fluxes,
     relative fluxes).  ``angles`` overrides the linspace (used when angle bins are sharded over GPUs).
     ``fused = False``: the reference's shape - a host loop, angle i on its own block of fresh ray ids (flux-only launches).
     ``fused = True``: the fused scan kernel - every ray of [ray_id_offset, ray_id_offset + n_rays_per_angle) is sampled once
     and turned through every angle (common random numbers); with ``errors`` also sqrt(sum of squared weights) and the
-    passed-ray counts."""
+    passed-ray counts.
+    ``images``: every angle's full result set as well (the per-angle calculateFluxFractions of :2787), appended to the tuple as
+    (images [K, 256, 256], K summary dicts, K spectra dicts) - fused: sart_trace_angular_scan_images; host loop: one trace_spectra
+    launch per angle on the ids the flux-only host loop uses (the fluxes then come from those launches)."""
     host = _lib.load_host()
     angles = np.linspace(angularScanMin, angularScanMax, numAngularScanPoints) if angles is None else \
         np.ascontiguousarray(angles, dtype=np.float64)
+    if images:
+        return _angular_scan_images(tracer, angles, n_rays_per_angle, seed, flags, ray_id_offset, fused, errors)
     fluxes = np.empty_like(angles)
     rel = np.empty_like(angles)
     fl = tracer.full.flags if flags is None else flags
@@ -591,3 +654,29 @@ def performAngularScan(tracer: RayTracer, angularScanMin: float, angularScanMax:
     _lib.check(host.sart_host_perform_angular_scan(tracer.handle, _lib.as_dp(angles), angles.size, n_rays_per_angle,
                                                    seed, ray_id_offset, fl, _lib.as_dp(fluxes), _lib.as_dp(rel)), host=True)
     return angles, fluxes, rel
+
+
+def _angular_scan_images(tracer: RayTracer, angles: np.ndarray, n_rays: int, seed: int, flags, ray_id_offset: int, fused: bool,
+                         errors: bool):
+    if fused:
+        imgs, summ, spec, (rows, _) = tracer.trace_angular_scan_images(angles, n_rays, seed, ray_id_offset, flags, spectra=True)
+        fluxes = rows["SUM_WEIGHTS"]
+        extra = (np.sqrt(rows["SUM_WEIGHTS_SQ"]), rows["N_PASSED"]) if errors else ()
+    else:
+        cur = _lib.Setup()
+        _lib.check(tracer.lib.sart_get_setup(tracer.handle, C.byref(cur)))
+        ty0 = cur.telescope_turned_y_deg   # put back on every way out, as the host driver does
+        imgs, summ, spec = [], [], []
+        try:
+            for i, a in enumerate(angles):   # raytracer.nim:2791-2800, the ray ids of sart_host_perform_angular_scan
+                tracer.set_telescope_angles(turned_y_deg=float(a))
+                img, s, sp = tracer.trace_spectra(n_rays, seed, ray_id_offset + i * n_rays, flags)
+                imgs.append(img)
+                summ.append(s)
+                spec.append(sp)
+        finally:
+            tracer.set_telescope_angles(turned_y_deg=ty0)
+        imgs = np.stack(imgs) if imgs else np.empty((0, 256, 256))
+        fluxes = np.array([s["SUM_WEIGHTS"] for s in summ])
+        extra = (np.full(angles.size, np.nan), np.array([s["N_PASSED"] for s in summ])) if errors else ()
+    return (angles, fluxes, fluxes / fluxes.max()) + extra + ((imgs, summ, spec),)

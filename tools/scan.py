@@ -19,6 +19,7 @@
 
 Examples
   python tools/scan.py angular --angularScanMin 0 --angularScanMax 0.3 --numAngularScanPoints 16 --rays 1e7
+  python tools/scan.py angular --fused --images --gpus 4 --accumulation fixed64 --rays 1e8    (+ one image CSV per angle)
   python tools/scan.py mass --gpus 8 --points 32 --rays 3e8          (starts its own 8 ranks; RCCL)
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/scan.py mass --points 32 --rays 3e8
 """
@@ -53,6 +54,10 @@ def main():
                     help="angular: the parallel X-ray test source in front of the bore (raytracer.nim:1765-1806) instead of the sun - "
                          "the cleaner effective-area probe (SURVEY 8(d) config 4)")
     ap.add_argument("--fused", action="store_true", help="angular: the fused scan kernel (same rays for every angle) instead of a re-trace per angle")
+    ap.add_argument("--images", action="store_true",
+                    help="angular --fused (--shard rays): also every angle's 256 x 256 image with its spectra (sart_trace_angular_scan_images), "
+                         "reduced over the ranks like the scan rows (int64 with fixed64) and written beside --out as "
+                         "axion_image_IAXO_angle_{a:.2f}.csv")
     ap.add_argument("--host-loop", action="store_true",
                     help="mass: one re-trace per mass point (what the fused scan replaces; independent ray blocks per point)")
     ap.add_argument("--emission", default=None, choices=["agss09-device", "agss09", "primakoff", "legacy", "flat"],
@@ -83,6 +88,8 @@ def main():
         local_rank = int(os.environ["SART_BENCH_DEVICE"])
     if args.shard is None:
         args.shard = "rays" if (args.mode == "angular" and args.fused) else "bins"
+    if args.images and not (args.mode == "angular" and args.fused and args.shard == "rays"):
+        raise SystemExit("--images goes with angular --fused (--shard rays)")
     D.heartbeat("tables")
     n_rays = int(args.rays)
     emission = args.emission or ("agss09-device" if args.mode == "mass" else "primakoff")
@@ -112,16 +119,40 @@ def main():
             rt.set_stream(stream.cuda_stream)
             rt.set_accumulation_mode(args.accumulation)
             p = rt.trace_params(hi - lo, ray_id_offset=lo, flags=flags, accumulate=True)
-            rt.trace_angular_scan_device(p, xs, acc.data_ptr())
+            if args.images:   # + one accumulator block (image, scalars, spectra) per angle, reduced like the scan rows
+                p = rt.angular_scan_images_params(hi - lo, ray_id_offset=lo, flags=flags, spectra=True, accumulate=True)
+                blen = 256 * 256 + L.SART_ACC_COUNT + 2 * p.n_radial_bins + 3 * (full.energies.size + 1)
+                blocks = torch.zeros(len(xs) * blen, dtype=torch.float64, device=acc.device)
+                rt.trace_angular_scan_images_device(p, xs, acc.data_ptr(), blocks.data_ptr())
+            else:
+                rt.trace_angular_scan_device(p, xs, acc.data_ptr())
             red = acc if use_cuda else acc.cpu()
             D.reduce_accumulator(red, dst=0, fixed64=fixed64)
+            if args.images:
+                red_b = blocks if use_cuda else blocks.cpu()
+                D.reduce_accumulator(red_b, dst=0, fixed64=fixed64)   # int64 sums of the raw blocks in fixed64
             if fixed64:
                 if not use_cuda:
                     acc.copy_(red)
                 rt.finalize_angular_scan_device(p, len(xs), acc.data_ptr())
+                if args.images:
+                    if not use_cuda:
+                        blocks.copy_(red_b)
+                    for k in range(len(xs)):   # block by block (sart_finalize_accumulator_device)
+                        rt.finalize_accumulator_device(p, blocks.data_ptr() + 8 * k * blen)
+                    red_b = blocks
                 rt.synchronize()
                 red = acc
             red = red.cpu()
+            if args.images and rank == 0:
+                from solaraxionraytracing_amd.raytracer import angle_image_names, containment_radii, split_image_blocks, write_image_csv
+                imgs, summ, spec = split_image_blocks(red_b.cpu().numpy().reshape(len(xs), blen), 256, p.n_radial_bins,
+                                                         full.energies.size + 1, p.radial_max)
+                out_dir = os.path.dirname(args.out) or "."
+                for name, img, sp in zip(angle_image_names("IAXO", xs), imgs, spec):
+                    r1w, r2w = containment_radii(sp)[2:]
+                    write_image_csv(os.path.join(out_dir, name), img, full.setup.chip_x_max, r1w, r2w)
+                print("wrote %d angle images to %s" % (len(xs), out_dir))
         per_angle, shared = sa.split_angular_scan(red.numpy(), len(xs))
         curve = per_angle["SUM_WEIGHTS"]
         errs = np.sqrt(per_angle["SUM_WEIGHTS_SQ"])
