@@ -620,6 +620,56 @@ int sart_trace_angular_scan_images_device(sart_context* ctx, const sart_trace_pa
 int sart_trace_angular_scan_images(sart_context* ctx, const sart_trace_params_t* params, const double* turned_y_deg,
                                    int32_t n_angles, double* scan_out_host, double* blocks_out_host);
 
+/* ---- fused energy scan (effective-area curve of the X-ray test source) ------ */
+/*
+ * With the X-ray test source (sart_setup_t::test_active) the energy is a constant of the setup (energyAx =
+ * testSource.energy, raytracer.nim:1771), and nothing geometric depends on it: it enters a ray through its weight factors
+ * alone - the reflectivities (computeReflectivity :2126), the magnet transmission with conversion and absorption in gas
+ * (computeMagnetTransmission :1582-1625), the window / strongback transmission (:2170, :2179) and the gas absorption in the
+ * detector (:2190).  These entry points trace every ray ONCE and form its weight for n_energies energies: the effective area
+ * (or the whole detection efficiency) as a function of X-ray energy in one call instead of a trace, and a rebuild of the
+ * energy tables, per energy.  The same ray ids for every energy (common random numbers).
+ * Per energy k the row and the shared counters equal what a sart_trace_histogram_device launch gives on the same params and
+ * ray ids after sart_set_setup with test_energy = energies_kev[k] and everything else unchanged: bit for bit in
+ * SART_ACCUM_FIXED64 (both limbs of both sums, every counter), up to the summation order in SART_ACCUM_F64.  N_PASSED and
+ * N_PASSED_TILL_WINDOW depend on the energy (they count rays whose weight is not zero, :2135, :2220) and are per energy;
+ * N_HIT_NICKEL is decided by the first mirror's reflection angle alone (:2040-2057) and is shared.
+ *
+ * Scan accumulator: (n_energies + 1) rows of SART_ESCAN_ROW 8-byte slots (f64, or int64 when raw SART_ACCUM_FIXED64):
+ *   row k < n_energies   SART_ESCAN_SUM_WEIGHTS, _SUM_WEIGHTS_SQ, _N_PASSED, _N_PASSED_TILL_WINDOW of energies_kev[k]
+ *                        (raw FIXED64: + the high limbs SART_ESCAN_SUM_WEIGHTS_HI / _SQ_HI, value = (hi 2^40 + lo) quantum)
+ *   row n_energies       energy-independent counters SART_ESCAN_N_* below
+ * Only params->n_rays, seed, ray_id_offset, flags and accumulate are read (no image is accumulated); accumulate == 0 zeroes
+ * the rows first.  The context's setup is not modified (sart_get_setup returns the same bytes before and after).
+ * SART_ERR_INVALID_ARGUMENT, with the context unchanged: the setup's test source is not active (the solar source samples
+ * radius and energy jointly, :425-471: its energy response is the energy spectrum of sart_trace_histogram_spectra),
+ * n_energies < 1, an energy not finite or <= 0, a NULL pointer.
+ * Energies go in balanced groups of up to 32 per kernel launch (99 = 25 + 25 + 25 + 24: the per-energy sums of a workgroup
+ * live in LDS), and every group traces the rays again.  The per-energy tables (the EnergyDev row and the reflectivity rows of
+ * every coating, hoisted exactly as the single launch hoists its test-source row) are built by the host per call and kept for
+ * the next call with the same energies; the context's own tables are not touched.
+ * FIXED64: the quanta of energy k come from the weight bound of that energy's rows (the bound the single launch derives from
+ * its test-source row) - a function of (setup, tables, flags, headroom, energies_kev[k]) alone: ranks compute the same ones, a
+ * reduce is an int64 sum of the raw scan accumulators, sart_finalize_energy_scan_device (same energies) converts to doubles
+ * with the mass scan's resolution and overflow checks per row.
+ */
+enum { SART_ESCAN_SUM_WEIGHTS = 0, SART_ESCAN_SUM_WEIGHTS_SQ = 1, SART_ESCAN_N_PASSED = 2, SART_ESCAN_N_PASSED_TILL_WINDOW = 3,
+       SART_ESCAN_SUM_WEIGHTS_HI = 4, SART_ESCAN_SUM_WEIGHTS_SQ_HI = 5, SART_ESCAN_ROW = 8 };
+enum { SART_ESCAN_N_RAYS = 0, SART_ESCAN_N_REACHED_TELESCOPE = 1, SART_ESCAN_N_SHELL_SELECTED = 2, SART_ESCAN_N_HIT_NICKEL = 3 };
+/* 8-byte slots of an energy-scan accumulator: (n_energies + 1) SART_ESCAN_ROW.  (Exported by the library rather than a static
+ * inline helper like sart_mass_scan_len, so that every binding - ctypes, Nim - can call it by name.) */
+size_t sart_energy_scan_len(int32_t n_energies);
+/* scan_acc_device: DEVICE memory of sart_energy_scan_len(n_energies) 8-byte slots; asynchronous on the context's stream. */
+int sart_trace_energy_scan_device(sart_context* ctx, const sart_trace_params_t* params, const double* energies_kev,
+                                  int32_t n_energies, double* scan_acc_device);
+/* Blocking form with a HOST output of sart_energy_scan_len(n_energies) doubles (finalized in FIXED64 mode). */
+int sart_trace_energy_scan(sart_context* ctx, const sart_trace_params_t* params, const double* energies_kev,
+                           int32_t n_energies, double* scan_out_host);
+/* Raw FIXED64 scan accumulator -> doubles (device pointers; in place allowed); asynchronous.  Resolution / overflow
+ * problems surface as SART_ERR_ACCUMULATOR from the next sart_synchronize. */
+int sart_finalize_energy_scan_device(sart_context* ctx, const sart_trace_params_t* params, const double* energies_kev,
+                                     int32_t n_energies, const void* scan_fixed_device, double* out_f64_device);
+
 /* ---- multi-GPU ---------------------------------------------------------- */
 /*
  * Sum the fused accumulators of n contexts (one per GPU of this process) into the one of contexts[root]:

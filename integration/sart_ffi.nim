@@ -18,6 +18,7 @@ const
   SartAccCount = 24     # SART_ACC_COUNT (ABI version 2)
   SartScanRow = 8       # SART_SCAN_ROW: 8-byte slots per row of a mass-scan accumulator
   SartAScanRow = 8      # SART_ASCAN_ROW: the same for the fused angular scan (ABI version 3)
+  SartEScanRow = 8      # SART_ESCAN_ROW: the same for the fused energy scan
   SartErrAccumulator* = -7   # SART_ERR_ACCUMULATOR: a raw FIXED64 accumulator wrapped / does not resolve the weights
 
 type
@@ -156,6 +157,16 @@ proc sart_trace_angular_scan_images_device*(ctx: ptr SartContext, p: ptr SartTra
                                             scanAccDevice: ptr cdouble, blocksDevice: ptr cdouble): cint {.importc, header: sartH.}
 proc sart_trace_angular_scan_images*(ctx: ptr SartContext, p: ptr SartTraceParams, turnedYDeg: ptr cdouble, nAngles: int32,
                                      scanOutHost: ptr cdouble, blocksOutHost: ptr cdouble): cint {.importc, header: sartH.}
+## fused energy scan (X-ray test source): every ray traced once, weighed at nEnergies energies [keV]; (nEnergies + 1) rows of
+## SartEScanRow slots (per energy: sum w, sum w^2, N_PASSED, N_PASSED_TILL_WINDOW; last row: N_RAYS, N_REACHED_TELESCOPE,
+## N_SHELL_SELECTED, N_HIT_NICKEL)
+proc sart_energy_scan_len*(nEnergies: int32): csize_t {.importc, header: sartH.}
+proc sart_trace_energy_scan_device*(ctx: ptr SartContext, p: ptr SartTraceParams, energiesKev: ptr cdouble, nEnergies: int32,
+                                    scanAccDevice: ptr cdouble): cint {.importc, header: sartH.}
+proc sart_trace_energy_scan*(ctx: ptr SartContext, p: ptr SartTraceParams, energiesKev: ptr cdouble, nEnergies: int32,
+                             scanOutHost: ptr cdouble): cint {.importc, header: sartH.}
+proc sart_finalize_energy_scan_device*(ctx: ptr SartContext, p: ptr SartTraceParams, energiesKev: ptr cdouble, nEnergies: int32,
+                                       scanFixedDevice: pointer, outF64Device: ptr cdouble): cint {.importc, header: sartH.}
 proc sart_reduce_across_devices*(contexts: ptr ptr SartContext, accumulatorsDevice: ptr ptr cdouble, n: int32, nDoubles: csize_t,
                                  root: int32): cint {.importc, header: sartH.}
 proc sart_enable_kernel_timing*(ctx: ptr SartContext, enable: cint): cint {.importc, header: sartH.}

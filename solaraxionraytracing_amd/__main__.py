@@ -5,6 +5,7 @@
         [--fusedAngularScan] [--angularImages]
         [--noPlots] [--config FILE | --configPath DIR]  [--rays N] [--seed S] [--outpath DIR]
         [--massScanMin M0 --massScanMax M1 --numMassScanPoints K]     (not in the reference: see below)
+        [--energyScanMin E0 --energyScanMax E1 --numEnergyScanPoints K]  (not in the reference: see below)
 
 Same switches, same two modes (full run = calculateFluxFractions, :2755-2776; angular scan, :2778-2815).  What differs:
 `--rays` replaces the compile-time constant NumberOfPointsSun (:251, default 1e6), plots are never made (the numbers
@@ -12,7 +13,11 @@ behind them are written as CSV), and without a config file the setup is that of 
 (BabyIAXO / InGridIAXO / vacuum / XMM, config_default.toml:19-22) with the synthetic input tables of tables.py.
 A third mode the reference does not have (it has one constant mAxion, :255): --massScanMin / --massScanMax / --numMassScanPoints
 run the fused axion-mass scan (every ray traced once, weighed for every mass; `stageSetup = "gas"` in the config, else the flux does
-not depend on the mass) and write `axion_mass_scan.csv`."""
+not depend on the mass) and write `axion_mass_scan.csv`.
+A fourth: --energyScanMin / --energyScanMax / --numEnergyScanPoints (keV) run the fused energy scan of the X-ray test source
+(`--xrayTest` or the config's [TestXraySource]; every ray traced once, weighed at every energy) and write `energy_scan.csv`: the
+detection efficiency per energy and, for a parallel beam, the effective area (the quantity of the reference's
+llnl_xray_telescope_cast_effective_area_parallel_light_DTU_thesis.csv).  It cannot be combined with the other scans."""
 from __future__ import annotations
 
 import argparse
@@ -23,7 +28,7 @@ import numpy as np
 
 from . import _lib, config as cfgmod
 from .raytracer import (RayTracer, angle_image_names, containment_radii, initFullSetup, performAngularScan, performAxionMassScan,
-                        write_image_csv)
+                        performEnergyScan, write_image_csv)
 
 WINDOW_YEAR = {_lib.DK_INGRID2017: "2017", _lib.DK_INGRID2018: "2018", _lib.DK_INGRIDIAXO: "IAXO"}   # WindowYearKind, :1468-1484
 
@@ -48,6 +53,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--massScanMin", type=float, default=0.0, help="eV (extension: fused axion-mass scan)")
     ap.add_argument("--massScanMax", type=float, default=0.0, help="eV")
     ap.add_argument("--numMassScanPoints", type=int, default=32)
+    ap.add_argument("--energyScanMin", type=float, default=0.0, help="keV (extension: fused energy scan of the X-ray test source)")
+    ap.add_argument("--energyScanMax", type=float, default=0.0, help="keV")
+    ap.add_argument("--numEnergyScanPoints", type=int, default=32)
     ap.add_argument("--config", default="", help="path of a config.toml")
     ap.add_argument("--configPath", default="", help="directory that holds config.toml")
     ap.add_argument("--rays", type=float, default=1e6, help="NumberOfPointsSun (raytracer.nim:251)")
@@ -55,6 +63,21 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--outpath", default="out")
     ap.add_argument("--device", type=int, default=0)
     return ap
+
+
+def energy_scan_requested(args) -> bool:
+    return args.energyScanMin != 0.0 or args.energyScanMax != 0.0
+
+
+def check_scan_args(ap: argparse.ArgumentParser, args) -> None:
+    """The energy scan is a mode of its own: exits 2 (argparse's usage error) when it is combined with another scan or asks for
+    no valid energies."""
+    if not energy_scan_requested(args):
+        return
+    if args.massScanMax > args.massScanMin or args.angularScanMin != args.angularScanMax:
+        ap.error("--energyScanMin / --energyScanMax cannot be combined with a mass scan or an angular scan")
+    if not (0.0 < args.energyScanMin < args.energyScanMax) or args.numEnergyScanPoints < 1:
+        ap.error("the energy scan needs 0 < --energyScanMin < --energyScanMax (keV) and --numEnergyScanPoints >= 1")
 
 
 def setup_from_args(args):
@@ -81,8 +104,12 @@ def write_result(path, img, s, spec, chip_max):
 
 
 def main(argv=None) -> int:
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    check_scan_args(ap, args)
     full, flags = setup_from_args(args)
+    if energy_scan_requested(args) and not full.setup.test_active:
+        ap.error("the energy scan needs the X-ray test source: --xrayTest, or [TestXraySource] active in the config")
     n = int(args.rays)
     os.makedirs(args.outpath, exist_ok=True)
     print("Flags:", [name for name, bit in (("cfIgnoreDetWindow", _lib.CF_IGNORE_DET_WINDOW), ("cfIgnoreGasAbs", _lib.CF_IGNORE_GAS_ABS),
@@ -90,7 +117,20 @@ def main(argv=None) -> int:
                                             ("cfXrayTest", _lib.CF_XRAY_TEST), ("cfReadMagnetConfig", _lib.CF_READ_MAGNET_CONFIG),
                                             ("cfReadDetInstallConfig", _lib.CF_READ_DET_INSTALL_CONFIG)) if flags & bit])
     with RayTracer(full, device=args.device) as rt:
-        if args.massScanMax > args.massScanMin:
+        if energy_scan_requested(args):
+            energies = np.linspace(args.energyScanMin, args.energyScanMax, args.numEnergyScanPoints)
+            res = performEnergyScan(rt, energies, n, seed=args.seed, flags=flags)
+            n_rays = res["shared"]["N_RAYS"]
+            area = res["effective_area_cm2"] if res["effective_area_cm2"] is not None else np.full(energies.size, np.nan)
+            out = os.path.join(args.outpath, "energy_scan.csv")
+            with open(out, "w") as f:
+                f.write("Energy [keV],efficiency,efficiency error,passed X-rays,effective area [cm^2]\n")
+                for e, eff, sg, k, a in zip(energies, res["efficiency"], res["sigma"], res["n_passed"], area):
+                    f.write("%r,%r,%r,%d,%r\n" % (float(e), float(eff), float(sg / n_rays), int(k), float(a)))
+            print("energy scan: %d energies on %d rays, maximum efficiency %.6g at %.6g keV"
+                  % (energies.size, n, float(np.max(res["efficiency"])), float(energies[int(np.argmax(res["efficiency"]))])))
+            print("wrote", out)
+        elif args.massScanMax > args.massScanMin:
             masses = np.linspace(args.massScanMin, args.massScanMax, args.numMassScanPoints)
             fluxes, errs, n_pass = performAxionMassScan(rt, masses, n, seed=args.seed, flags=flags, errors=True)
             out = os.path.join(args.outpath, "axion_mass_scan.csv")

@@ -48,7 +48,27 @@ ASCAN = dict(SUM_WEIGHTS=0, SUM_WEIGHTS_SQ=1, N_PASSED=2, N_SHELL_SELECTED=3, N_
 ASCAN_HI = dict(SUM_WEIGHTS=4, SUM_WEIGHTS_SQ=5)
 ASCAN_SHARED = dict(N_RAYS=0, N_REACHED_TELESCOPE=1)
 ASCAN_MAX_ANGLES = 32   # csrc/sart_device.h: kAScanMaxAngles (angles per kernel launch)
+# fused energy scan (include/sart.h: SART_ESCAN_*): (n_energies + 1) rows of ESCAN_ROW slots; the last row holds the counters of ESCAN_SHARED
+ESCAN_ROW = 8
+ESCAN = dict(SUM_WEIGHTS=0, SUM_WEIGHTS_SQ=1, N_PASSED=2, N_PASSED_TILL_WINDOW=3)
+ESCAN_HI = dict(SUM_WEIGHTS=4, SUM_WEIGHTS_SQ=5)
+ESCAN_SHARED = dict(N_RAYS=0, N_REACHED_TELESCOPE=1, N_SHELL_SELECTED=2, N_HIT_NICKEL=3)
+ESCAN_MAX_ENERGIES = 32   # csrc/sart_device.h: kEScanMaxEnergies (energies per kernel launch)
 FIXED_LIMB_BITS = 40
+
+
+def energy_scan_len(n_energies: int) -> int:
+    """sart_energy_scan_len: 8-byte slots of an energy-scan accumulator."""
+    return (int(n_energies) + 1) * ESCAN_ROW
+
+
+def split_energy_scan(acc, n_energies: int):
+    """(per-energy dict of arrays, shared-counter dict) from a finalized energy-scan accumulator."""
+    import numpy as np
+    rows = np.asarray(acc, dtype=np.float64).reshape(int(n_energies) + 1, ESCAN_ROW)
+    per_energy = {k: rows[:n_energies, i].copy() for k, i in ESCAN.items()}
+    shared = {k: float(rows[n_energies, i]) for k, i in ESCAN_SHARED.items()}
+    return per_energy, shared
 
 ACC = dict(SUM_WEIGHTS=0, N_PASSED=1, N_PASSED_TILL_WINDOW=2, N_HIT_NICKEL=3, SUM_X=4, SUM_Y=5, SUM_R=6,
            SUM_WEIGHTS_SQ=7, N_RAYS=8, N_REACHED_TELESCOPE=9, N_SHELL_SELECTED=10, N_OUTSIDE_IMAGE=11)
@@ -220,6 +240,10 @@ SART_SYMBOLS = {
     "sart_finalize_angular_scan_device": (C.c_int, [C.c_void_p, _P(TraceParams), _i, C.c_void_p, C.c_void_p]),
     "sart_trace_angular_scan_images_device": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, C.c_void_p, C.c_void_p]),
     "sart_trace_angular_scan_images": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, _dp, _dp]),
+    "sart_energy_scan_len": (C.c_size_t, [_i]),
+    "sart_trace_energy_scan_device": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, C.c_void_p]),
+    "sart_trace_energy_scan": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, _dp]),
+    "sart_finalize_energy_scan_device": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, C.c_void_p, C.c_void_p]),
     "sart_reduce_across_devices": (C.c_int, [_P(C.c_void_p), _P(C.c_void_p), _i, C.c_size_t, _i]),
     "sart_enable_kernel_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "sart_get_kernel_timing": (C.c_int, [C.c_void_p, _dp, _P(C.c_int64)]),

@@ -43,6 +43,9 @@ int angular_scan_blocks_per_cu(bool fast);
 void launch_ascan_images(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, const AScanArgs& AN, double* img_partials,
                          double* rows, double* shared_row, int n_blocks, hipStream_t stream, bool fast, bool fixed);
 int ascan_images_blocks_per_cu(bool fast);
+int energy_scan_blocks_per_cu(bool rotated);
+void launch_trace_energy_scan(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, const EScanArgs& EN, double* rows,
+                              double* shared_row, int n_blocks, hipStream_t stream, bool rotated, bool fixed);
 int histogram_block_of(int variant);
 void launch_trace_records(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, sart_axion_t* out, int n_blocks,
                           hipStream_t stream, const double* uniforms_dev);
@@ -261,6 +264,17 @@ struct sart_context {
   DevBuf<double> d_aimg_partials;    // ... with images: per-angle per-workgroup scalars
   DevBuf<double> d_aimg;             // ... scratch blocks of the blocking form
   int blocks_per_cu_aimg[2] = {0, 0};
+  // fused energy scan: the per-energy tables of the last call's energies (energy_row_of / refl_rows_of, built beside the context's
+  // own tables, which they do not touch), reused while the energies and the context's tables stay the same
+  uint64_t tables_gen = 0;           // bumped whenever refresh_derived rebuilds the context's tables
+  uint64_t escan_gen = ~0ull;        // tables_gen the cached rows were built from
+  std::vector<double> escan_energies;
+  std::vector<EnergyDev> escan_rows;
+  std::vector<double> escan_max;     // [k][4]: |t_window|, |t_strongback|, |a_gas|, max |reflectivity| of energy k (the weight bound)
+  std::vector<double> escan_refl;    // [n_coatings][n][n_angles]
+  bool escan_uploaded = false;
+  DevBuf<double> d_escan_refl, d_escan_partials, d_escan, d_escan_fin;
+  int blocks_per_cu_escan[2] = {0, 0};
 
   // timing
   bool timing = false;
@@ -456,29 +470,34 @@ int hoist_setup(sart_context* c) {
 }
 
 // ---- per-energy-index tables -------------------------------------------------------------------
-int hoist_energy_tables(sart_context* c) {
+// The E-only factors of a ray's weight at energy E (keV): row i < n_energies of the table (E = max(0.03, energies[i])), row
+// n_energies (the X-ray test source's energy, :1771) and the rows of the fused energy scan all come from here.
+EnergyDev energy_row_of(const sart_context* c, double E) {
   const sart_setup_t& s = c->setup;
-  const int nE = c->n_energies;
-  std::vector<EnergyDev> tab(static_cast<size_t>(nE) + 1);
   const double pGas = s.magnet_pGasRoom / s.room_temp * s.magnet_tGas;
   auto density = [](double p, double temp) {  // axionMassforMagnet.nim:4-15
     const double pressure = p * 1e2;
     double r = pressure * 4.002602 / (8.314 * temp * 1000.0);
     return r / 1000.0;
   };
-  for (int i = 0; i <= nE; ++i) {
-    const double E = (i < nE) ? std::max(0.03, c->energies[i]) : s.test_energy;  // :470-471 / :1771
-    EnergyDev& e = tab[i];
-    e.energy = E;
-    e.t_window = linear1d(c->win_x, c->win_y, E);
-    e.t_strongback = linear1d(c->sb_x, c->sb_y, E);
-    e.a_gas = linear1d(c->gas_x, c->gas_y, E);
-    const double massAtt = std::exp(-1.5832 + 5.9195 * std::exp(-0.353808 * E) + 4.03598 * std::exp(-0.970557 * E));  // :70-73
-    e.gamma = 1.97e-7 * 100.0 * density(pGas, s.magnet_tGas) * massAtt;  // :84
-    e.inv_two_e_ev = 1.0 / (2 * (E * 1000.0));                             // :68 (the kernel multiplies)
-    e.mu_pipe = massAtt * density(pGas, s.room_temp) * 100;                // :109-113
-    e.mu_magnet = massAtt * density(pGas, s.magnet_tGas) * 100;
-  }
+  EnergyDev e;
+  e.energy = E;
+  e.t_window = linear1d(c->win_x, c->win_y, E);
+  e.t_strongback = linear1d(c->sb_x, c->sb_y, E);
+  e.a_gas = linear1d(c->gas_x, c->gas_y, E);
+  const double massAtt = std::exp(-1.5832 + 5.9195 * std::exp(-0.353808 * E) + 4.03598 * std::exp(-0.970557 * E));  // :70-73
+  e.gamma = 1.97e-7 * 100.0 * density(pGas, s.magnet_tGas) * massAtt;  // :84
+  e.inv_two_e_ev = 1.0 / (2 * (E * 1000.0));                             // :68 (the kernel multiplies)
+  e.mu_pipe = massAtt * density(pGas, s.room_temp) * 100;                // :109-113
+  e.mu_magnet = massAtt * density(pGas, s.magnet_tGas) * 100;
+  return e;
+}
+
+int hoist_energy_tables(sart_context* c) {
+  const sart_setup_t& s = c->setup;
+  const int nE = c->n_energies;
+  std::vector<EnergyDev> tab(static_cast<size_t>(nE) + 1);
+  for (int i = 0; i <= nE; ++i) tab[i] = energy_row_of(c, (i < nE) ? std::max(0.03, c->energies[i]) : s.test_energy);  // :470-471 / :1771
   // bounds for the FIXED64 weight quantum: the solar source draws indices < nE ([0..3]: maxima over those rows), the X-ray test
   // source uses row nE alone ([4..7]: its values - at BabyIAXO's 0.021 keV they are orders of magnitude below the maxima)
   c->etab_max.assign(8, 0.0);
@@ -495,45 +514,48 @@ int hoist_energy_tables(sart_context* c) {
   return c->d_etab.upload(tab.data(), tab.size());
 }
 
-// Reflectivity re-tabulated per energy index: for each coating and each energy index the bilinear
-// interpolation (numericalnim eval_bilinear; call sites :1567-1568, :1577-1578) is carried out along
-// the energy axis, leaving g[i] with  R(alpha, E_idx) = g[i] + xUnit (g[i+1] - g[i]).
+// Reflectivity re-tabulated at energy E: the bilinear interpolation (numericalnim eval_bilinear; call sites :1567-1568,
+// :1577-1578) carried out along the energy axis for every coating, leaving g[i] with  R(alpha, E) = g[i] + xUnit (g[i+1] - g[i]).
+// Coating cc's n_angles values go to out + cc * coating_stride.  Returns max |g| over them (the weight bound's reflectivity).
+double refl_rows_of(const sart_context* c, double E, double* out, size_t coating_stride) {
+  const int nA = c->refl_na, nEr = c->refl_ne, nC = c->refl_nc;
+  const double dy = (c->refl_emax - c->refl_emin) / static_cast<double>(nEr - 1);
+  long j = static_cast<long>(std::floor((E - c->refl_emin) / dy));
+  j = std::min<long>(j, nEr - 2);
+  if (j < 0) j = 0;  // below the grid the reference would index out of bounds; hold the first cell
+  const double yCorner = c->refl_emin + static_cast<double>(j) * dy;
+  const double yUnit = (E - yCorner) / dy;
+  double m = 0.0;
+  for (int cc = 0; cc < nC; ++cc) {
+    const double* z = c->refl_data.data() + static_cast<size_t>(cc) * nA * nEr;
+    double* g = out + static_cast<size_t>(cc) * coating_stride;
+    for (int i = 0; i < nA; ++i) {
+      const double f0 = z[static_cast<size_t>(i) * nEr + j], f1 = z[static_cast<size_t>(i) * nEr + j + 1];
+      g[i] = f0 + (f1 - f0) * yUnit;
+      m = std::max(m, std::fabs(g[i]));
+    }
+  }
+  return m;
+}
+
+// Reflectivity re-tabulated per energy index (refl_rows_of for every row of the energy table).
 int hoist_reflectivity(sart_context* c) {
-  const int nE = c->n_energies, nA = c->refl_na, nEr = c->refl_ne, nC = c->refl_nc;
+  const int nE = c->n_energies, nA = c->refl_na, nC = c->refl_nc;
   // the kernel addresses the re-tabulated grid with 32-bit byte offsets built from 24-bit multiplicands
   if (nA >= (1 << 24) || static_cast<size_t>(nC) * (nE + 1) * nA >= (size_t(1) << 29))
     return fail(SART_ERR_UNSUPPORTED, "reflectivity grid too large: n_coatings * (n_energies + 1) * n_angles must stay below 2^29");
   std::vector<double> out(static_cast<size_t>(nC) * (nE + 1) * nA);
-  const double dy = (c->refl_emax - c->refl_emin) / static_cast<double>(nEr - 1);
+  // |R| <= max |g| for every angle inside the grid (the kernel clamps the cell; outside it extrapolates from the edge cell);
+  // [3]: the rows of the solar energies, [7]: the rows of the test source's energy (index nE of every coating)
+  double m = 0.0, mt = 0.0;
   for (int e = 0; e <= nE; ++e) {
     const double E = (e < nE) ? std::max(0.03, c->energies[e]) : c->setup.test_energy;
-    long j = static_cast<long>(std::floor((E - c->refl_emin) / dy));
-    j = std::min<long>(j, nEr - 2);
-    if (j < 0) j = 0;  // below the grid the reference would index out of bounds; hold the first cell
-    const double yCorner = c->refl_emin + static_cast<double>(j) * dy;
-    const double yUnit = (E - yCorner) / dy;
-    for (int cc = 0; cc < nC; ++cc) {
-      const double* z = c->refl_data.data() + static_cast<size_t>(cc) * nA * nEr;
-      double* g = out.data() + (static_cast<size_t>(cc) * (nE + 1) + e) * nA;
-      for (int i = 0; i < nA; ++i) {
-        const double f0 = z[static_cast<size_t>(i) * nEr + j], f1 = z[static_cast<size_t>(i) * nEr + j + 1];
-        g[i] = f0 + (f1 - f0) * yUnit;
-      }
-    }
+    const double r = refl_rows_of(c, E, out.data() + static_cast<size_t>(e) * nA, static_cast<size_t>(nE + 1) * nA);
+    double& dst = (e < nE) ? m : mt;
+    dst = std::max(dst, r);
   }
-  {
-    // |R| <= max |g| for every angle inside the grid (the kernel clamps the cell; outside it extrapolates from the edge cell);
-    // [3]: the rows of the solar energies, [7]: the rows of the test source's energy (index nE of every coating)
-    double m = 0.0, mt = 0.0;
-    for (int cc = 0; cc < nC; ++cc)
-      for (int e = 0; e <= nE; ++e) {
-        const double* g = out.data() + (static_cast<size_t>(cc) * (nE + 1) + e) * nA;
-        double& dst = (e < nE) ? m : mt;
-        for (int i = 0; i < nA; ++i) dst = std::max(dst, std::fabs(g[i]));
-      }
-    c->etab_max[3] = m;
-    c->etab_max[7] = mt;
-  }
+  c->etab_max[3] = m;
+  c->etab_max[7] = mt;
   return c->d_refl.upload(out.data(), out.size());
 }
 
@@ -553,6 +575,7 @@ int refresh_derived(sart_context* c) {
   if (int rc = hoist_energy_tables(c)) return rc;
   if (int rc = hoist_reflectivity(c)) return rc;
   c->derived_dirty = false;
+  ++c->tables_gen;
   c->blob_dirty = true;
   c->spot_may_have_moved = true;
   return 0;
@@ -805,33 +828,44 @@ DevTables tables_of(sart_context* c) {
 // maximised over the energies a ray can have (the table rows of the solar source, or the test source's one row).  Off resonance
 // P falls like 4 / (q L)^2: a bound that ignored the mass (L^2 alone) would leave the weights of a far-off-resonance scan point
 // 1e-6 .. 1e-7 of it, at or below what the integer quanta resolve.
-double gas_prob_bound(const sart_context* c, double dm2_abs) {
+// (rows: the energy-table rows a ray can have - those of the solar source, or the test source's one row)
+double gas_prob_bound_rows(const sart_context* c, double dm2_abs, const EnergyDev* rows, size_t n) {
   const DevParams& P = c->params;
   const double l_nat = P.length_b * P.gas_inv_hbarc_m;
-  const size_t nE = static_cast<size_t>(c->n_energies);
-  const size_t lo = P.test_active ? nE : 0, hi = P.test_active ? nE + 1 : nE;
   double best = 0.0;
-  for (size_t i = lo; i < hi && i < c->etab_host.size(); ++i) {
-    const EnergyDev& e = c->etab_host[i];
+  for (size_t i = 0; i < n; ++i) {
+    const EnergyDev& e = rows[i];
     const double q = dm2_abs * e.inv_two_e_ev;
     best = std::max(best, std::min(l_nat * l_nat, 4.0 / (q * q + 0.25 * e.gamma * e.gamma)));
   }
   return P.gas_term1 * best;
 }
-
-double weight_bound_of(const sart_context* c, uint32_t flags, double dm2_abs) {
+double gas_prob_bound(const sart_context* c, double dm2_abs) {
   const DevParams& P = c->params;
-  const double* m = c->etab_max.data() + (P.test_active ? 4 : 0);   // the test source has ONE energy: its row, not the maxima
+  const size_t nE = static_cast<size_t>(c->n_energies);
+  const size_t lo = P.test_active ? nE : 0, hi = std::min(P.test_active ? nE + 1 : nE, c->etab_host.size());
+  return gas_prob_bound_rows(c, dm2_abs, c->etab_host.data() + lo, hi > lo ? hi - lo : 0);
+}
+
+// m[0..3]: max |t_window|, |t_strongback|, |a_gas|, |reflectivity| over the rows a ray can have; prob_bound: gas stage only.
+double weight_bound_with(const sart_context* c, uint32_t flags, const double* m, double prob_bound) {
+  const DevParams& P = c->params;
   double b = 1.0;
   if (!(flags & SART_CF_IGNORE_REFLECTION)) b *= m[3] * m[3];
   if (!(flags & SART_CF_IGNORE_CONV_PROB)) {
     // vacuum: conv_k pathCB^2, pathCB ~ lengthB (:363-365); gas: see gas_prob_bound
-    b *= P.stage_gas ? gas_prob_bound(c, dm2_abs) : P.conv_k * P.length_b * P.length_b;
+    b *= P.stage_gas ? prob_bound : P.conv_k * P.length_b * P.length_b;
   }
   if (!(flags & SART_CF_IGNORE_DET_WINDOW)) b *= std::max(m[0], m[1]);
   if (!(flags & SART_CF_IGNORE_GAS_ABS)) b *= m[2];
   if (!(flags & SART_CF_XRAY_TEST)) b *= P.exposure;
   return b;
+}
+
+double weight_bound_of(const sart_context* c, uint32_t flags, double dm2_abs) {
+  const DevParams& P = c->params;
+  const double* m = c->etab_max.data() + (P.test_active ? 4 : 0);   // the test source has ONE energy: its row, not the maxima
+  return weight_bound_with(c, flags, m, P.stage_gas && !(flags & SART_CF_IGNORE_CONV_PROB) ? gas_prob_bound(c, dm2_abs) : 0.0);
 }
 
 // The exponents of the FIXED64 quanta for a weight bound b < 2^e: weights (pixels, SUM_WEIGHTS, weight spectra) in units of
@@ -1998,6 +2032,204 @@ int sart_trace_mass_scan(sart_context* c, const sart_trace_params_t* p, const do
     if (int rc = c->d_scan_fin.resize(len)) return rc;
     if (int rc = sart_finalize_mass_scan_device(c, p, masses, n_masses, c->d_scan.p, c->d_scan_fin.p)) return rc;
     src = c->d_scan_fin.p;
+  }
+  SART_HIP(hipMemcpyAsync(out_host, src, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  SART_HIP(hipStreamSynchronize(c->stream));
+  return status_take(c);
+}
+
+// ---- fused energy scan (include/sart.h) ----------------------------------------------------------------------------------------
+namespace {
+
+int escan_check(sart_context* c, const sart_trace_params_t* p, const double* energies, int32_t n) {
+  if (!c || !p || !energies) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (n < 1 || n > 65536) return fail(SART_ERR_INVALID_ARGUMENT, "n_energies must be in [1, 65536]");
+  for (int32_t k = 0; k < n; ++k)
+    if (!std::isfinite(energies[k]) || !(energies[k] > 0.0)) return fail(SART_ERR_INVALID_ARGUMENT, "energies must be finite and > 0 keV");
+  return 0;
+}
+
+// The checks every entry point makes, then the context's derived state; refuses the solar source.
+int escan_prepare(sart_context* c, const sart_trace_params_t* p, const double* energies, int32_t n) {
+  if (int rc = escan_check(c, p, energies, n)) return rc;
+  SART_HIP(hipSetDevice(c->device));
+  if (int rc = refresh_derived(c)) return rc;
+  if (int rc = sync_blob(c)) return rc;
+  if (!c->params.test_active)
+    return fail(SART_ERR_INVALID_ARGUMENT, "sart_trace_energy_scan needs the X-ray test source (sart_setup_t::test_active): the solar "
+                                           "source samples radius and energy jointly (raytracer.nim:425-471); its energy response is "
+                                           "the energy spectrum of sart_trace_histogram_spectra");
+  return 0;
+}
+
+// The per-energy rows of a scan on the host (cached: same energies, same context tables -> nothing to do); `upload`: also the
+// reflectivity rows on the device.
+int escan_tables(sart_context* c, const double* energies, int32_t n, bool upload) {
+  const bool same = c->escan_gen == c->tables_gen && c->escan_energies.size() == static_cast<size_t>(n) &&
+                    std::memcmp(c->escan_energies.data(), energies, static_cast<size_t>(n) * sizeof(double)) == 0;
+  if (!same) {
+    const int nA = c->refl_na, nC = c->refl_nc;
+    // the kernel addresses the scan's reflectivity rows with 32-bit byte offsets built from 24-bit multiplicands
+    if (nA >= (1 << 24) || static_cast<size_t>(nC) * static_cast<size_t>(n) * static_cast<size_t>(nA) >= (size_t(1) << 29))
+      return fail(SART_ERR_UNSUPPORTED, "energy scan: n_coatings * n_energies * n_angles must stay below 2^29");
+    c->escan_gen = ~0ull;
+    c->escan_uploaded = false;
+    c->escan_rows.resize(n);
+    c->escan_max.assign(4 * static_cast<size_t>(n), 0.0);
+    c->escan_refl.assign(static_cast<size_t>(nC) * n * nA, 0.0);
+    for (int32_t k = 0; k < n; ++k) {
+      const EnergyDev e = energy_row_of(c, energies[k]);   // the test source's row: no 0.03 keV floor (hoist_energy_tables, row nE)
+      c->escan_rows[k] = e;
+      double* m = &c->escan_max[4 * static_cast<size_t>(k)];
+      m[0] = std::fabs(e.t_window);
+      m[1] = std::fabs(e.t_strongback);
+      m[2] = std::fabs(e.a_gas);
+      m[3] = std::max(0.0, refl_rows_of(c, energies[k], c->escan_refl.data() + static_cast<size_t>(k) * nA, static_cast<size_t>(n) * nA));
+    }
+    c->escan_energies.assign(energies, energies + n);
+    c->escan_gen = c->tables_gen;
+  }
+  if (upload && !c->escan_uploaded) {
+    SART_HIP(hipStreamSynchronize(c->stream));   // launches still running on the context's stream read the previous rows
+    if (int rc = c->d_escan_refl.upload(c->escan_refl.data(), c->escan_refl.size())) return rc;
+    c->escan_uploaded = true;
+  }
+  return 0;
+}
+
+// Upper bound of a ray's weight at scan energy k: weight_bound_of with that energy's rows in place of the test source's row nE.
+double escan_weight_bound(const sart_context* c, uint32_t flags, int32_t k) {
+  const bool gas_prob = c->params.stage_gas && !(flags & SART_CF_IGNORE_CONV_PROB);
+  return weight_bound_with(c, flags, &c->escan_max[4 * static_cast<size_t>(k)],
+                           gas_prob ? gas_prob_bound_rows(c, c->params.gas_dm2_abs, &c->escan_rows[k], 1) : 0.0);
+}
+
+// Balanced groups of at most kEScanMaxEnergies: group g of n_groups starts at first_of(g) (99 -> 25 + 25 + 25 + 24).
+struct EScanGroups {
+  int32_t n, n_groups;
+  explicit EScanGroups(int32_t n_) : n(n_), n_groups((n_ + kEScanMaxEnergies - 1) / kEScanMaxEnergies) {}
+  int32_t first_of(int32_t g) const { return g * (n / n_groups) + std::min(g, n % n_groups); }
+  int32_t size_of(int32_t g) const { return first_of(g + 1) - first_of(g); }
+};
+
+}  // namespace
+
+size_t sart_energy_scan_len(int32_t n_energies) { return (static_cast<size_t>(n_energies) + 1u) * static_cast<size_t>(SART_ESCAN_ROW); }
+
+int sart_trace_energy_scan_device(sart_context* c, const sart_trace_params_t* p, const double* energies, int32_t n_energies, double* scan_dev) {
+  if (int rc = escan_check(c, p, energies, n_energies)) return rc;
+  if (!scan_dev) return fail(SART_ERR_INVALID_ARGUMENT, "scan accumulator is NULL");
+  if (int rc = escan_prepare(c, p, energies, n_energies)) return rc;
+  sart_trace_params_t q = *p;   // a scan accumulates no image: whatever the caller left in the image fields is not read
+  q.image_nx = q.image_ny = 1;
+  q.image_x_min = q.image_y_min = 0.0;
+  q.image_x_max = q.image_y_max = 1.0;
+  q.spectra = 0;
+  TraceArgs a;
+  if (int rc = make_args(c, &q, a)) return rc;
+  a.fx_scale_w = a.fx_scale_w2 = 0.0;
+  const bool fixed = c->accum_mode == SART_ACCUM_FIXED64;
+  if (int rc = escan_tables(c, energies, n_energies, true)) return rc;
+  EScanArgs en;
+  std::memset(&en, 0, sizeof en);
+  en.row_stride = n_energies;
+  const EScanGroups groups(n_energies);
+  std::vector<EScanEnergy> rows(n_energies);
+  for (int32_t k = 0; k < n_energies; ++k) {
+    const EnergyDev& e = c->escan_rows[k];
+    EScanEnergy& r = rows[k];
+    std::memset(&r, 0, sizeof r);
+    r.t_window = e.t_window; r.t_strongback = e.t_strongback; r.a_gas = e.a_gas;
+    r.gamma = e.gamma; r.inv_two_e_ev = e.inv_two_e_ev; r.mu_pipe = e.mu_pipe; r.mu_magnet = e.mu_magnet;
+    if (fixed) {   // the quanta a single launch at this energy freezes (sart_trace_histogram_device, accumulate == 0)
+      QuantaExp qe;
+      if (int rc = quanta_exp_of(c, escan_weight_bound(c, p->flags, k), qe)) return rc;
+      r.fx_scale_w = std::ldexp(1.0, -qe.w);
+      r.fx_scale_w2 = std::ldexp(1.0, -qe.w2);
+    }
+  }
+  if (!p->accumulate) SART_HIP(hipMemsetAsync(scan_dev, 0, sart_energy_scan_len(n_energies) * sizeof(double), c->stream));
+  if (p->n_rays == 0) return 0;
+  const bool rotated = c->params.rotated != 0;   // hist_variant_of: 1 / 2 for the test source
+  if (c->blocks_per_cu_escan[rotated] == 0) {
+    c->blocks_per_cu_escan[rotated] = std::max(1, energy_scan_blocks_per_cu(rotated));
+    if (c->knobs.hist_blocks_per_cu > 0) c->blocks_per_cu_escan[rotated] = c->knobs.hist_blocks_per_cu;
+  }
+  // ray indices inside one launch are 32-bit: pieces of at most 2^31 rays; every piece runs once per group of energies
+  for (uint64_t done = 0; done < p->n_rays;) {
+    const uint64_t n = std::min<uint64_t>(p->n_rays - done, 1ull << 31);
+    a.n_rays = n;
+    a.ray_id_offset = p->ray_id_offset + done;
+    const int n_blocks = grid_for(n, c->n_cu, c->blocks_per_cu_escan[rotated], 1024);
+    const size_t rows_min = std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4);
+    if (c->d_partials.n < static_cast<size_t>(n_blocks) * SART_ACC_COUNT) {
+      SART_HIP(hipStreamSynchronize(c->stream));
+      if (int rc = c->d_partials.resize(rows_min * SART_ACC_COUNT)) return rc;
+    }
+    if (c->d_escan_partials.n < static_cast<size_t>(n_blocks) * kEScanMaxEnergies * kScanPartialSlots) {
+      SART_HIP(hipStreamSynchronize(c->stream));
+      if (int rc = c->d_escan_partials.resize(rows_min * kEScanMaxEnergies * kScanPartialSlots)) return rc;
+    }
+    a.partials = c->d_partials.p;
+    for (int32_t g = 0; g < groups.n_groups; ++g) {
+      const int32_t k0 = groups.first_of(g);
+      en.n_energies = groups.size_of(g);
+      en.partials = c->d_escan_partials.p;
+      en.refl = c->d_escan_refl.p + static_cast<size_t>(k0) * c->refl_na;
+      for (int32_t k = 0; k < en.n_energies; ++k) en.e[k] = rows[k0 + k];
+      double* const out_rows = scan_dev + static_cast<size_t>(k0) * SART_ESCAN_ROW;
+      double* const shared = (g == 0) ? scan_dev + static_cast<size_t>(n_energies) * SART_ESCAN_ROW : nullptr;   // counters: once per piece
+      {
+        TimedLaunch tl(c);
+        launch_trace_energy_scan(c->hot, c->hotb, c->d_blob.p, a, en, out_rows, shared, n_blocks, c->stream, rotated, fixed);
+      }
+      SART_HIP(hipGetLastError());
+    }
+    done += n;
+  }
+  return 0;
+}
+
+int sart_finalize_energy_scan_device(sart_context* c, const sart_trace_params_t* p, const double* energies, int32_t n_energies,
+                                     const void* raw_dev, double* out_dev) {
+  if (int rc = escan_check(c, p, energies, n_energies)) return rc;
+  if (!raw_dev || !out_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (int rc = escan_prepare(c, p, energies, n_energies)) return rc;
+  if (int rc = status_ensure(c)) return rc;
+  if (int rc = escan_tables(c, energies, n_energies, false)) return rc;
+  const EScanGroups groups(n_energies);
+  for (int32_t g = 0; g < groups.n_groups; ++g) {
+    const int32_t k0 = groups.first_of(g), n = groups.size_of(g);
+    double q_w[kScanMaxMasses], q_w2[kScanMaxMasses];
+    static_assert(kEScanMaxEnergies <= kScanMaxMasses, "finalize_scan_kernel takes the quanta of one group");
+    for (int k = 0; k < n; ++k) {
+      QuantaExp qe;
+      if (int rc = quanta_exp_of(c, escan_weight_bound(c, p->flags, k0 + k), qe)) return rc;
+      q_w[k] = std::ldexp(1.0, qe.w);
+      q_w2[k] = std::ldexp(1.0, qe.w2);
+    }
+    const size_t off = static_cast<size_t>(k0) * SART_ESCAN_ROW;
+    launch_finalize_scan(static_cast<const long long*>(raw_dev) + off, out_dev + off, n, q_w, q_w2, (k0 + n == n_energies) ? n : -1,
+                         c->d_status.p, c->stream, (1u << SART_ESCAN_N_PASSED) | (1u << SART_ESCAN_N_PASSED_TILL_WINDOW));
+    SART_HIP(hipGetLastError());
+  }
+  return status_enqueue_copy(c);
+}
+
+int sart_trace_energy_scan(sart_context* c, const sart_trace_params_t* p, const double* energies, int32_t n_energies, double* out_host) {
+  if (int rc = escan_check(c, p, energies, n_energies)) return rc;
+  if (!out_host) return fail(SART_ERR_INVALID_ARGUMENT, "output is NULL");
+  if (int rc = escan_prepare(c, p, energies, n_energies)) return rc;
+  const size_t len = sart_energy_scan_len(n_energies);
+  if (int rc = c->d_escan.reserve(len)) return rc;
+  sart_trace_params_t q = *p;
+  q.accumulate = 0;   // the blocking form has no accumulator the caller could add into
+  if (int rc = sart_trace_energy_scan_device(c, &q, energies, n_energies, c->d_escan.p)) return rc;
+  const double* src = c->d_escan.p;
+  if (c->accum_mode == SART_ACCUM_FIXED64) {
+    if (int rc = c->d_escan_fin.reserve(len)) return rc;
+    if (int rc = sart_finalize_energy_scan_device(c, p, energies, n_energies, c->d_escan.p, c->d_escan_fin.p)) return rc;
+    src = c->d_escan_fin.p;
   }
   SART_HIP(hipMemcpyAsync(out_host, src, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   SART_HIP(hipStreamSynchronize(c->stream));

@@ -288,6 +288,30 @@ static_assert(sizeof(AScanAngle) == 80 && sizeof(AScanArgs) == 16 + 80 * kAScanM
 // (angle 0 only) N_REACHED_TELESCOPE of the workgroup, unused
 constexpr int kAScanPartialSlots = 8;
 
+// Fused energy scan (include/sart.h: sart_trace_energy_scan): with the X-ray test source the energy is a constant of the setup
+// (raytracer.nim:1771) that enters a ray's weight only, so trace_energy_scan_kernel traces every ray ONCE and forms its weight for
+// every energy of this table.  One launch takes up to kEScanMaxEnergies energies: what the weight needs of energy k (the E-only
+// factors of its EnergyDev row, hoisted by the host exactly as row n_energies of the single launch) travels here and is read with
+// scalar loads; the reflectivity rows of the scan are a table of their own ([n_coatings][row_stride][n_angles], `refl`).  Per energy
+// a workgroup keeps [sum of w, sum of w^2][kScanLanes] f64 / int64 cells in ring 0's space (the test source runs no stage A0) and two
+// counters in LDS.
+constexpr int kEScanMaxEnergies = 32;
+struct EScanEnergy {
+  double t_window, t_strongback, a_gas;           // EnergyDev of this energy
+  double gamma, inv_two_e_ev, mu_pipe, mu_magnet;
+  double fx_scale_w, fx_scale_w2;                 // SART_ACCUM_FIXED64: 1 / quantum of the weights and squared weights of THIS energy
+  double _pad;
+};
+struct EScanArgs {
+  int32_t n_energies;             // energies of this launch (1 .. kEScanMaxEnergies)
+  int32_t row_stride;             // energies of the scan's reflectivity table (rows per coating)
+  double* partials;               // [n_blocks][kEScanMaxEnergies][kScanPartialSlots] {sum w, sum w^2, N_PASSED, N_PASSED_TILL_WINDOW}
+  const double* refl;             // first row of this launch's energies in the scan's reflectivity table (coating 0)
+  double _pad;
+  EScanEnergy e[kEScanMaxEnergies];
+};
+static_assert(sizeof(EScanEnergy) == 80 && sizeof(EScanArgs) == 32 + 80 * kEScanMaxEnergies, "the kernel re-reads EScanArgs with scalar loads at these offsets");
+
 constexpr double kFixedPositionScale = 4294967296.0;        // 2^32 per mm
 constexpr double kFixedReflectScale = 1099511627776.0;      // 2^40
 constexpr int kFixedLimbBits = 40;                          // two-limb sums: value = hi * 2^40 + lo

@@ -962,9 +962,20 @@ struct RayOut {
 // weight, out.gas what gas_conversion_prob() needs of this ray, out.m_passed the rays on the chip for which that factor is not
 // zero; the caller applies the probability per mass.
 // NODRAW: the caller always hands the energy index in (fused angular scan: drawn once per ray in front of the angle loop).
-template <bool RECORDS, bool FAST, int GAS, bool ZEXT, bool SCAN = false, bool NODRAW = false>
+// ESCAN (fused energy scan, X-ray test source): phase B stops once the geometry is known - mirrors, reflection-angle cells,
+// detector plane, chip and strips - and hands what the weight needs of the ray to the caller in *geo (EScanGeo); no energy row,
+// no reflectivity gather, no weight.  out.m_nickel is set as usual.
+struct EScanGeo {
+  double cos_ya, path_cb, distance_pipe_m, xu1, xu2;
+  int ia1, ia2;
+  uint64_t m_live;      // rays alive behind the mirrors (the lanes N_PASSED_TILL_WINDOW counts, given a non-zero weight)
+  uint64_t m_chip;      // ... and on the chip (the lanes N_PASSED counts, given a non-zero final weight)
+  uint64_t m_strip;     // rays inside a strongback strip
+};
+template <bool RECORDS, bool FAST, int GAS, bool ZEXT, bool SCAN = false, bool NODRAW = false, bool ESCAN = false>
 __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, const HotB& HB, const TraceArgs& A,
-                                        const RayState& st, int e_idx_in, bool live, RayOut& out, sart_axion_t* rec) {
+                                        const RayState& st, int e_idx_in, bool live, RayOut& out, sart_axion_t* rec,
+                                        EScanGeo* geo = nullptr) {
 #ifdef SART_STAGE_TIMING
 #define SART_B_STAMP(k, dep) do { asm volatile("" :: "v"(dep)); out.tb[k] = __builtin_readcyclecounter(); } while (0)
 #else
@@ -1081,9 +1092,9 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
   const int e_idx = draw_energy ? energy_draw_finish(HB, ed) : e_idx_in;
 #endif
   SART_B_STAMP(3, e_idx);
-  const EnergyDev en = load_energy_row(HB, e_idx);
+  const EnergyDev en = ESCAN ? EnergyDev{} : load_energy_row(HB, e_idx);
   d2 g1 = {1.0, 1.0}, g2 = {1.0, 1.0};
-  if (use_refl) {
+  if (!ESCAN && use_refl) {
     // row (coating, e_idx) of refl[][n_angles]: 32-bit element offset (the table is < 4 GB, checked on the host)
     const uint32_t row = __umul24((uint32_t)(sh.refl_row0 + e_idx), (uint32_t)HB.refl_n_angles);
     g1 = gload<d2>(HB.refl, (row + (uint32_t)ia1) * 8u);   // g[i], g[i + 1] (8-byte aligned pair)
@@ -1133,6 +1144,19 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
   const double yt = fabs(fma(pdy, P.theta_c, -pdx * P.theta_s));
   bool in_strip = false;
   for (int i = 0; i < n_half_strips; ++i) in_strip = in_strip | ((yt > P.strip_lo[i]) & (yt < P.strip_hi[i]));
+  if constexpr (ESCAN) {
+    static_assert(!RECORDS && !SCAN && !FAST, "the energy scan accumulates, and it runs on the generic variants");
+    geo->cos_ya = cos_ya;
+    geo->path_cb = st.path_cb;
+    geo->distance_pipe_m = distance_pipe_m;
+    geo->xu1 = xu1; geo->xu2 = xu2;
+    geo->ia1 = ia1; geo->ia2 = ia2;
+    geo->m_live = live_m;
+    geo->m_chip = live_m & on_chip_m;
+    geo->m_strip = ballot64(in_strip);
+    (void)en; (void)g1; (void)g2; (void)on_chip;
+    return;
+  }
 
   // ---- weights (:2116-2128) ----
   const double path_cb = st.path_cb;
@@ -1880,6 +1904,285 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
     for (int w = 0; w < BLOCK / 64; ++w) t += red[w][threadIdx.x];
     reinterpret_cast<Sum*>(A.partials)[(size_t)blockIdx.x * SART_ACC_COUNT + threadIdx.x] = t;
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// fused energy scan (include/sart.h: sart_trace_energy_scan)
+// ------------------------------------------------------------------------------------------------
+// With the X-ray test source (sart_setup_t::test_active) the energy is a constant of the setup (energyAx = testSource.energy,
+// raytracer.nim:1771) and nothing geometric depends on it: it enters a ray through the reflectivities (:2126), the magnet
+// transmission - conversion and absorption in gas (:1582-1625) -, the window / strongback transmission (:2170, :2179) and the
+// gas absorption in the detector (:2190), all of them weight factors.  This kernel therefore runs phase A and the geometric part of
+// phase B (mirrors, the reflection angles' cells and the fractions inside them, detector plane, chip, strips: phase_b<ESCAN>) ONCE
+// per ray and then walks the launch's energies (wave-uniform; EScanArgs in the kernel arguments, read with scalar loads): gathers
+// the two reflectivity pairs of energy k from the scan's own table (those of energy k + 1 are requested before the arithmetic of
+// energy k), forms the weight with the arithmetic of the single launch in its order (the bitwise contract of the FIXED64 mode) and
+// adds w, w^2 into per-energy LDS cells ([k][2][kScanLanes] in ring 0's space: the test source runs no stage A0) and the two
+// energy-dependent counters N_PASSED, N_PASSED_TILL_WINDOW (weight != 0, :2135, :2220) into per-energy LDS counters; both are folded
+// once per workgroup.  The energy-independent counters (N_REACHED_TELESCOPE, N_SHELL_SELECTED, N_HIT_NICKEL) go to the scalar
+// partials of the histogram kernels.  Generic variants only (hist_variant_of 1 / 2: ROT), the stage read at run time.
+struct EScanKernArgs {
+  HotA H;
+  const DevBlob* blob;
+  TraceArgs A;
+  double* unused;      // (keeps the argument offsets of trace_histogram_kernel: the reload_* helpers are shared)
+  HotB HB;
+  EScanArgs EN;
+};
+static_assert(offsetof(EScanKernArgs, A) == offsetof(HistKernArgs, A) && offsetof(EScanKernArgs, HB) == offsetof(HistKernArgs, HB) &&
+                  offsetof(EScanKernArgs, EN) == offsetof(HistKernArgs, SC),
+              "the energy-scan kernel shares the argument offsets of the histogram kernel");
+static_assert(kEScanMaxEnergies * 2 * kScanLanes <= kTileRingCells, "the per-energy sums live in ring 0's 128 doubles per wave");
+
+template <int BLOCK, bool ROT, bool FIXED>
+__global__ __launch_bounds__(BLOCK) void energy_scan_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
+                                                                  double* __restrict__ unused, HotB HBarg, EScanArgs ENarg) {
+  struct LdsLayout {
+    TablesLds S;
+    DevBlob B;
+    TraceArgs Ab;
+    uint32_t cnt[kEScanMaxEnergies][2];   // per energy: N_PASSED, N_PASSED_TILL_WINDOW of this workgroup
+    uint32_t shared_cnt[4];                // N_REACHED_TELESCOPE, N_SHELL_SELECTED, N_HIT_NICKEL of this workgroup
+    alignas(512) QueueLds<BLOCK / 64> Q;
+  };
+  __shared__ LdsLayout lds;
+  TablesLds& S = lds.S;
+  QueueLds<BLOCK / 64>& Q = lds.Q;
+  static_assert((offsetof(LdsLayout, Q) % 512) == 0, "the rings are addressed with ds_*2st64 offsets");
+  static_assert(BLOCK == 1024, "[energy][2][32] cells fill ring 0 of 16 waves");
+  // cell t of the per-energy sums: ring 0 (ray + u3hi columns, 128 doubles per wave), unused without stage A0
+  auto cell = [&](uint32_t t) -> double* { return reinterpret_cast<double*>(&Q.w[t >> 7].ray[0]) + (t & 127u); };
+  DevBlob& B = lds.B;
+  TraceArgs& Ab = lds.Ab;
+  {
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(blob);
+    uint64_t* dst = reinterpret_cast<uint64_t*>(&B);
+    for (int i = threadIdx.x; i < (int)(sizeof(DevBlob) / 8); i += BLOCK) dst[i] = src[i];
+    if (threadIdx.x == 0) Ab = A;
+    uint64_t* q = reinterpret_cast<uint64_t*>(&Q);
+    for (int i = threadIdx.x; i < (int)(sizeof(Q) / 8); i += BLOCK) q[i] = 0ull;
+    if (threadIdx.x < 2 * kEScanMaxEnergies) lds.cnt[threadIdx.x >> 1][threadIdx.x & 1] = 0u;
+    if (threadIdx.x < 4) lds.shared_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+  }
+  const DevParams& Pb = B.P;
+  const DevTables& Tb = B.T;
+  stage_tables<BLOCK>(S, Pb, Tb);
+  const LdsTables L{S.sincos, S.rcdf_hi, Tb.flux_radius_cdf, S.rguide, S.shells, S.lut};
+
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint64_t waves_total = (uint64_t)gridDim.x * (BLOCK / 64);
+  const uint64_t wave_global = (uint64_t)blockIdx.x * (BLOCK / 64) + wave;
+  const uint64_t first_chunk = A.ray_id_offset >> 8;
+  uint64_t id_base = first_chunk << 8;
+  asm volatile("" : "+s"(id_base));
+  const uint32_t rel_begin = (uint32_t)(A.ray_id_offset & 255u);
+  const uint32_t rel_end = rel_begin + (uint32_t)A.n_rays;
+  const uint32_t n_chunks = (rel_end + 255u) >> 8;
+
+  uint32_t n_reached = 0, n_shell = 0, n_nickel = 0;   // wave-uniform
+  uint32_t h1 = 0, t1 = 0;   // ring 1 (A1 -> B)
+  auto ring_sync = [] {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
+  auto prefix_of = [](uint64_t mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+  };
+
+  // phase A as in trace_histogram_kernel (generic variants: no stage A0, the path carried through ring 1)
+  auto run_phase_a = [&](uint32_t rel, bool valid, uint32_t u3_hi) {
+    SART_STAGE_MARK("A1");
+    __builtin_amdgcn_s_setprio(SART_PRIO_A1);
+    RayState st;
+    bool sampled = false, reached = false;
+    double radial;
+    HotA Hl;
+    reload_hot(Hl);
+    LaneMasks M;
+    (void)phase_a<false, ROT ? 1 : 0, false, false>(Hl, Pb, L, A.seed_lo, A.seed_hi, id_base + (uint64_t)rel, u3_hi, st, sampled, reached, radial, M);
+    const uint64_t valid_m = ballot64(valid);
+    n_reached += (uint32_t)__popcll(valid_m & M.reached);
+    const uint64_t selected = valid_m & M.ok;
+    n_shell += (uint32_t)__popcll(selected);
+    const uint64_t mask = selected & ~ballot64(radial < Pb.shell0_miss_radius);
+    const uint32_t cnt = (uint32_t)__popcll(mask);
+    if (__builtin_amdgcn_inverse_ballot_w64(mask)) {
+      const uint32_t slot = (t1 + prefix_of(mask)) % kQueue;
+      Q.w[wave].X0[slot] = st.X0; Q.w[wave].Y0[slot] = st.Y0;
+      Q.w[wave].tsx[slot] = st.tsx; Q.w[wave].tsy[slot] = st.tsy;
+      Q.w[wave].path[slot] = st.path_cb;
+      Q.w[wave].u5[slot] = st.u5;
+      Q.w[wave].idx[slot] = st.r_idx | (st.shell << 16);
+    }
+    t1 += cnt;
+    __builtin_amdgcn_s_setprio(0);
+  };
+
+  auto run_phase_b = [&](uint32_t n_valid) {
+    SART_STAGE_MARK("B");
+    __builtin_amdgcn_s_setprio(SART_PRIO_B);
+    RayState st;
+    const bool valid = (uint32_t)lane < n_valid;
+    const uint32_t slot = (h1 + (uint32_t)lane) % kQueue;
+    RayOut out;
+    EScanGeo geo;
+    st.X0 = Q.w[wave].X0[slot]; st.Y0 = Q.w[wave].Y0[slot];
+    st.tsx = Q.w[wave].tsx[slot]; st.tsy = Q.w[wave].tsy[slot];
+    st.path_cb = Q.w[wave].path[slot];
+    st.u5 = Q.w[wave].u5[slot];
+    if (!ROT) {
+      st.zcb = -(H.dz3 - H.dz1);
+    } else {
+      st.zcb = zcb_rotated(Pb.rx_s, -Pb.rx_c * Pb.ry_s, Pb.rx_c * Pb.ry_c, Pb.half_length_telescope, st.X0 + Pb.entrance_x,
+                           st.Y0 + Pb.entrance_y, st.tsx, st.tsy, H.dz3 - H.dz1);
+    }
+    const int packed = Q.w[wave].idx[slot];
+    st.r_idx = packed & 0xFFFF;
+    st.shell = packed >> 16;
+    const DevBlob& Bo = lds_opaque(B);
+    {
+      HotB HB;
+      reload_kernarg(HB, offsetof(EScanKernArgs, HB));
+      phase_b<false, false, -1, false, false, true, true>(Bo.P, L, HB, lds_opaque(Ab), st, 0, valid, out, nullptr, &geo);
+    }
+    h1 += n_valid;
+    n_nickel += (uint32_t)__popcll(out.m_nickel);
+    if (!geo.m_live) { __builtin_amdgcn_s_setprio(0); return; }   // wave-uniform: no ray behind the mirrors, nothing counts
+
+    SART_STAGE_MARK("ESCAN");
+    asm volatile("; hot: per-energy loop of the fused energy scan");
+    struct { int32_t n_energies, row_stride; const double* partials; const double* refl; } hdr;
+    reload_kernarg(hdr, offsetof(EScanKernArgs, EN));
+    const DevParams& P = Bo.P;
+    const uint32_t flags = (uint32_t)__builtin_amdgcn_readfirstlane((int)Ab.flags);
+    const int stage_gas = __builtin_amdgcn_readfirstlane(P.stage_gas);
+    const int n_half_strips = __builtin_amdgcn_readfirstlane(P.n_half_strips);
+    const int n_angles = __builtin_amdgcn_readfirstlane(P.refl_n_angles);
+    const bool use_refl = !(flags & SART_CF_IGNORE_REFLECTION);
+    const bool use_prob = !(flags & SART_CF_IGNORE_CONV_PROB);
+    // the energy-independent factors, as phase_b forms them
+    const double path_cb = geo.path_cb;
+    double prob_vac = 1.0;
+    if (!stage_gas && use_prob) prob_vac = P.conv_k * path_cb * path_cb;   // conversionProb (:363-365)
+    const double path_len = path_cb;
+    const double Lnat = path_len * P.gas_inv_hbarc_m;
+    const double dist = geo.distance_pipe_m;
+    const double term1 = P.gas_term1, dm2_abs = P.gas_dm2_abs;
+    const GasCos cos_lead = GasCos::make();
+    const bool strip = __builtin_amdgcn_inverse_ballot_w64(geo.m_strip);
+    // refl[coating][row][angle] of the scan's table: 32-bit byte offsets (the table is < 4 GB, checked on the host)
+    const uint32_t step = (uint32_t)n_angles * 8u;
+    const uint32_t row0 = __umul24((uint32_t)(L.shells[st.shell].coating * hdr.row_stride), (uint32_t)n_angles);
+    uint32_t off1 = (row0 + (uint32_t)geo.ia1) * 8u, off2 = (row0 + (uint32_t)geo.ia2) * 8u;
+    d2 n1 = {1.0, 1.0}, n2 = {1.0, 1.0};
+    if (use_refl) { n1 = gload<d2>(hdr.refl, off1); n2 = gload<d2>(hdr.refl, off2); }
+    for (int k = 0; k < hdr.n_energies; ++k) {   // wave-uniform
+      const d2 g1 = n1, g2 = n2;
+      if (use_refl & (k + 1 < hdr.n_energies)) {   // energy k + 1's pairs in flight behind energy k's arithmetic
+        off1 += step; off2 += step;
+        n1 = gload<d2>(hdr.refl, off1);
+        n2 = gload<d2>(hdr.refl, off2);
+      }
+      EScanEnergy E;
+      reload_kernarg(E, offsetof(EScanKernArgs, EN) + offsetof(EScanArgs, e) + (size_t)k * sizeof(EScanEnergy));
+      // ---- weights (:2116-2128), phase_b's arithmetic in its order ----
+      double trans_magnet;
+      GasRay gas = {0.0, 0.0, 0.0, 0.0, 0.0};
+      if (!stage_gas) {
+        trans_magnet = geo.cos_ya * prob_vac;   // (x absorb = 1: exact)
+      } else {
+        if (use_prob) {
+          const double g = E.gamma;
+          const double eh = exp_neg(-g * Lnat * 0.5);
+          gas = GasRay{E.inv_two_e_ev, g * g * 0.25, -2.0 * eh, fma(eh, eh, 1.0), Lnat};
+        }
+        const double absorb = exp_neg(-fma(E.mu_pipe, dist, E.mu_magnet * (path_len * 1e-3)));
+        trans_magnet = geo.cos_ya * absorb;
+      }
+      const double reflectv = fma(geo.xu1, g1.y - g1.x, g1.x) * fma(geo.xu2, g2.y - g2.x, g2.x);
+      double w = reflectv * trans_magnet;
+      uint64_t till_m = geo.m_live & ballot64(w != 0.0);
+      const double trans_window = (n_half_strips > 0) ? (strip ? E.t_strongback : E.t_window) : 0.0;
+      if (!(flags & SART_CF_IGNORE_DET_WINDOW)) { asm volatile(""); w *= trans_window; }
+      if (!(flags & SART_CF_IGNORE_GAS_ABS)) { asm volatile(""); w *= E.a_gas; }
+      if (!(flags & SART_CF_XRAY_TEST)) { asm volatile(""); w *= P.exposure; }
+      if (stage_gas & use_prob) {
+        const double prob = gas_conversion_prob(dm2_abs, gas, term1, L.sincos, cos_lead);
+        w *= prob;
+        till_m &= ballot64(prob != 0.0);
+      }
+      const uint64_t passed_m = geo.m_chip & ballot64(w != 0.0);
+      if (lane == 0) {
+        if (passed_m) __hip_atomic_fetch_add(&lds.cnt[k][0], (uint32_t)__popcll(passed_m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (till_m) __hip_atomic_fetch_add(&lds.cnt[k][1], (uint32_t)__popcll(till_m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      if (__builtin_amdgcn_inverse_ballot_w64(passed_m)) {
+        // cell [k][0][lane % 32], [k][1][.] kScanLanes further on (the mass scan's layout)
+        const uint32_t t = (uint32_t)k * (2u * kScanLanes) + ((uint32_t)lane & (kScanLanes - 1u));
+        if constexpr (FIXED) {
+          __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(cell(t)), (unsigned long long)to_fixed(w, E.fx_scale_w),
+                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(cell(t + kScanLanes)), (unsigned long long)to_fixed(w * w, E.fx_scale_w2),
+                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        } else {
+          __hip_atomic_fetch_add(cell(t), w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          __hip_atomic_fetch_add(cell(t + kScanLanes), w * w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+      }
+    }
+    __builtin_amdgcn_s_setprio(0);
+  };
+
+  uint32_t chunk = (uint32_t)wave_global;
+  const uint32_t lane4 = 4u * (uint32_t)lane;
+  uint32_t pass = 0;
+  U4 stream = U4{0u, 0u, 0u, 0u};
+  for (;;) {
+    const bool have_new = chunk < n_chunks;   // wave-uniform
+    if (have_new) {
+      if (pass == 0u) stream = stream_block(((first_chunk + (uint64_t)chunk) << 6) + (uint64_t)lane, A.seed_lo, A.seed_hi);
+      const uint32_t w = word_of(stream, pass);
+      const uint32_t rel = ((chunk << 8) + pass) + lane4;
+      run_phase_a(rel, (rel >= rel_begin) & (rel < rel_end), w);
+      pass = (pass + 1u) & 3u;
+      if (pass == 0u) chunk += (uint32_t)waves_total;
+      ring_sync();
+    }
+    const uint32_t n1 = t1 - h1;
+    if ((n1 >= 64u) | (!have_new & (n1 > 0u))) {
+      run_phase_b(min(n1, 64u));
+      ring_sync();
+    }
+    if (!have_new & (t1 == h1)) break;
+  }
+
+  // per-energy sums of this workgroup: a wave adds up the cells of an energy (lanes 0 .. 31: sum of w, 32 .. 63: sum of w^2; a fixed
+  // order) -> plain stores, folded by fold_escan_kernel
+  using Sum = std::conditional_t<FIXED, long long, double>;
+  if (lane == 0) {
+    if (n_reached) atomicAdd(&lds.shared_cnt[0], n_reached);
+    if (n_shell) atomicAdd(&lds.shared_cnt[1], n_shell);
+    if (n_nickel) atomicAdd(&lds.shared_cnt[2], n_nickel);
+  }
+  __syncthreads();
+  for (int k = wave; k < ENarg.n_energies; k += BLOCK / 64) {
+    Sum* const dst = reinterpret_cast<Sum*>(ENarg.partials) + ((size_t)blockIdx.x * kEScanMaxEnergies + (size_t)k) * kScanPartialSlots;
+    const double c = *cell((uint32_t)k * 64u + (uint32_t)lane);
+    Sum v;
+    if constexpr (FIXED) v = __double_as_longlong(c); else v = c;
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);   // within each half of the wave
+    if (lane == 0) { dst[0] = v; dst[2] = (Sum)lds.cnt[k][0]; dst[3] = (Sum)lds.cnt[k][1]; }
+    if (lane == 32) dst[1] = v;
+  }
+  if (threadIdx.x < 4) {
+    Sum* const r = reinterpret_cast<Sum*>(A.partials) + (size_t)blockIdx.x * 4;
+    r[threadIdx.x] = (Sum)lds.shared_cnt[threadIdx.x];
+  }
+  (void)unused; (void)HBarg;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2802,6 +3105,67 @@ __global__ __launch_bounds__(1024) void fold_scan_kernel(double* __restrict__ ro
   }
 }
 
+// Fused energy scan: rows of the scan accumulator (include/sart.h: SART_ESCAN_*) += the per-workgroup sums of one launch.  1024
+// threads = 128 (energy, quantity) pairs x 8 groups of workgroups, summed in a fixed order like fold_scan_kernel.  `shared_row`
+// (first group of energies of a scan only, else nullptr): the energy-independent counters from shared_partials[n_blocks][4].
+// FIXED: integers; the two sums in two limbs (hi 2^40 + lo, lo in [0, 2^40)) like fold_scalars_fixed_kernel.
+template <bool FIXED>
+__global__ __launch_bounds__(1024) void fold_escan_kernel(double* __restrict__ rows_, double* __restrict__ shared_row_,
+                                                          const double* __restrict__ shared_partials_, const double* __restrict__ escan_partials_,
+                                                          int n_blocks, int n_energies, double n_rays) {
+  using Sum = std::conditional_t<FIXED, long long, double>;
+  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
+  constexpr int kPairs = kEScanMaxEnergies * kScanPartialSlots, kGroups = 8;
+  static_assert(kPairs * kGroups == 1024, "one thread per (energy, partial slot, group of workgroups)");
+  Sum* const rows = reinterpret_cast<Sum*>(rows_);
+  Sum* const shared_row = reinterpret_cast<Sum*>(shared_row_);
+  const Sum* const shp = reinterpret_cast<const Sum*>(shared_partials_);
+  const Sum* const esp = reinterpret_cast<const Sum*>(escan_partials_);
+  __shared__ Sum red_lo[kGroups][kPairs], red_hi[kGroups][kPairs], red_cnt[kGroups][4];
+  const int pair = threadIdx.x % kPairs, g = threadIdx.x / kPairs;
+  const int k = pair >> 2, j = pair & 3;
+  Sum lo = 0, hi = 0;
+  if (k < n_energies) {
+    for (int b = g; b < n_blocks; b += kGroups) {
+      const Sum p = esp[((size_t)b * kEScanMaxEnergies + k) * kScanPartialSlots + j];
+      if constexpr (FIXED) { lo += p & kMask; hi += p >> kFixedLimbBits; } else lo += p;
+    }
+  }
+  red_lo[g][pair] = lo;
+  red_hi[g][pair] = hi;
+  if (pair < 4) {
+    Sum t = 0;
+    if (shared_row && pair < 3)
+      for (int b = g; b < n_blocks; b += kGroups) t += shp[(size_t)b * 4 + pair];
+    red_cnt[g][pair] = t;
+  }
+  __syncthreads();
+  if (g != 0) return;
+  if (k < n_energies) {
+    lo = 0; hi = 0;
+    for (int i = 0; i < kGroups; ++i) { lo += red_lo[i][pair]; hi += red_hi[i][pair]; }
+    Sum* const row = rows + (size_t)k * SART_ESCAN_ROW;
+    if (j >= 2) {
+      const int dst = j == 2 ? SART_ESCAN_N_PASSED : SART_ESCAN_N_PASSED_TILL_WINDOW;
+      if constexpr (FIXED) row[dst] += (hi << kFixedLimbBits) + lo; else row[dst] += lo;
+    } else if constexpr (FIXED) {
+      const int s = j == 0 ? SART_ESCAN_SUM_WEIGHTS : SART_ESCAN_SUM_WEIGHTS_SQ, sh = j == 0 ? SART_ESCAN_SUM_WEIGHTS_HI : SART_ESCAN_SUM_WEIGHTS_SQ_HI;
+      lo += row[s];
+      row[s] = lo & kMask;
+      row[sh] += hi + (lo >> kFixedLimbBits);
+    } else {
+      row[j == 0 ? SART_ESCAN_SUM_WEIGHTS : SART_ESCAN_SUM_WEIGHTS_SQ] += lo;
+    }
+  }
+  if (shared_row && pair < 3) {
+    const int dst = pair == 0 ? SART_ESCAN_N_REACHED_TELESCOPE : pair == 1 ? SART_ESCAN_N_SHELL_SELECTED : SART_ESCAN_N_HIT_NICKEL;
+    Sum t = 0;
+    for (int i = 0; i < kGroups; ++i) t += red_cnt[i][pair];
+    shared_row[dst] += t;
+    if (pair == 0) shared_row[SART_ESCAN_N_RAYS] += (Sum)n_rays;
+  }
+}
+
 // What the finalize kernels report about a raw SART_ACCUM_FIXED64 accumulator (OR-ed into a word of the context that the next
 // sart_synchronize reads): integers that no longer mean what they should.
 constexpr uint32_t kFixedStatusWrapped = 1u;       // a slot is negative or >= 2^62: wrapped, or about to (weights and counts are >= 0)
@@ -3307,6 +3671,29 @@ void launch_trace_angular_scan(const HotA& H, const HotB& HB, const DevBlob* blo
     hipLaunchKernelGGL(fold_ascan_kernel<true>, dim3(1), dim3(1024), 0, stream, rows, shared_row, AN.partials, n_blocks, AN.n_angles, (double)A.n_rays);
   else
     hipLaunchKernelGGL(fold_ascan_kernel<false>, dim3(1), dim3(1024), 0, stream, rows, shared_row, AN.partials, n_blocks, AN.n_angles, (double)A.n_rays);
+}
+
+// The fused energy scan of one launch group: the kernel (generic variants: `rotated` = hist_variant_of 2), then the fold into
+// `rows` (the group's first row of the scan accumulator) and, if `shared_row`, into the scan's counter row.
+int energy_scan_blocks_per_cu(bool rotated) {
+  int n = 0;
+  const hipError_t e = rotated ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, energy_scan_kernel<1024, true, false>, 1024, 0)
+                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, energy_scan_kernel<1024, false, false>, 1024, 0);
+  return (e == hipSuccess && n > 0) ? n : 1;
+}
+void launch_trace_energy_scan(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, const EScanArgs& EN, double* rows,
+                              double* shared_row, int n_blocks, hipStream_t stream, bool rotated, bool fixed) {
+  double* const no_acc = nullptr;
+  switch ((rotated ? 2 : 0) + (fixed ? 1 : 0)) {
+    case 0: hipLaunchKernelGGL((energy_scan_kernel<1024, false, false>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, no_acc, HB, EN); break;
+    case 1: hipLaunchKernelGGL((energy_scan_kernel<1024, false, true>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, no_acc, HB, EN); break;
+    case 2: hipLaunchKernelGGL((energy_scan_kernel<1024, true, false>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, no_acc, HB, EN); break;
+    default: hipLaunchKernelGGL((energy_scan_kernel<1024, true, true>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, no_acc, HB, EN); break;
+  }
+  if (fixed)
+    hipLaunchKernelGGL(fold_escan_kernel<true>, dim3(1), dim3(1024), 0, stream, rows, shared_row, A.partials, EN.partials, n_blocks, EN.n_energies, (double)A.n_rays);
+  else
+    hipLaunchKernelGGL(fold_escan_kernel<false>, dim3(1), dim3(1024), 0, stream, rows, shared_row, A.partials, EN.partials, n_blocks, EN.n_energies, (double)A.n_rays);
 }
 
 int ascan_images_blocks_per_cu(bool fast) {

@@ -416,6 +416,30 @@ class RayTracer:
         _lib.check(self.lib.sart_finalize_mass_scan_device(self.handle, C.byref(params), _lib.as_dp(masses), masses.size,
                                                            C.c_void_p(raw_ptr), C.c_void_p(out_ptr if out_ptr is not None else raw_ptr)))
 
+    # -- fused energy scan (X-ray test source; include/sart.h "fused energy scan") --------------
+    def trace_energy_scan(self, energies_kev, n_rays: int, seed: int = 299792458, ray_id_offset: int = 0, flags: int | None = None):
+        """Every ray of [ray_id_offset, ray_id_offset + n_rays) traced ONCE and weighed at every X-ray energy (keV) of the test
+        source.  Returns (per-energy dict of arrays SUM_WEIGHTS / SUM_WEIGHTS_SQ / N_PASSED / N_PASSED_TILL_WINDOW, dict of the
+        energy-independent counters)."""
+        energies = np.ascontiguousarray(energies_kev, dtype=np.float64)
+        p = self.trace_params(n_rays, seed, ray_id_offset, flags)
+        out = np.empty(_lib.energy_scan_len(energies.size))
+        _lib.check(self.lib.sart_trace_energy_scan(self.handle, C.byref(p), _lib.as_dp(energies), energies.size, _lib.as_dp(out)))
+        return _lib.split_energy_scan(out, energies.size)
+
+    def trace_energy_scan_device(self, params: TraceParams, energies_kev, scan_acc_ptr: int):
+        """Asynchronous form: adds into a device scan accumulator of energy_scan_len(n) 8-byte slots (raw int64 in fixed64 mode)."""
+        energies = np.ascontiguousarray(energies_kev, dtype=np.float64)
+        _lib.check(self.lib.sart_trace_energy_scan_device(self.handle, C.byref(params), _lib.as_dp(energies), energies.size,
+                                                          C.c_void_p(scan_acc_ptr)))
+
+    def finalize_energy_scan_device(self, params: TraceParams, energies_kev, raw_ptr: int, out_ptr: int | None = None):
+        """Raw FIXED64 energy-scan accumulator (device) -> doubles (device; in place by default).  Asynchronous; what the
+        conversion finds wrong is raised by the next ``synchronize()``."""
+        energies = np.ascontiguousarray(energies_kev, dtype=np.float64)
+        _lib.check(self.lib.sart_finalize_energy_scan_device(self.handle, C.byref(params), _lib.as_dp(energies), energies.size,
+                                                             C.c_void_p(raw_ptr), C.c_void_p(out_ptr if out_ptr is not None else raw_ptr)))
+
     # -- fused angular scan (include/sart.h "fused angular scan") -------------------------------
     def trace_angular_scan(self, turned_y_deg, n_rays: int, seed: int = 299792458, ray_id_offset: int = 0, flags: int | None = None):
         """Every ray of [ray_id_offset, ray_id_offset + n_rays) sampled and taken through bore and pipes ONCE and turned through
@@ -624,6 +648,25 @@ def performAxionMassScanHostLoop(tracer: RayTracer, masses_ev, n_rays_per_mass: 
     finally:
         tracer.set_axion_mass(m0)
     return out
+
+
+def performEnergyScan(tracer: RayTracer, energies_kev, n_rays: int = 1_000_000, seed: int = 299792458, flags: int | None = None,
+                      ray_id_offset: int = 0) -> dict:
+    """Detection efficiency - and, for a parallel beam, the effective area - of the X-ray test source as a function of its
+    energy, through the fused energy scan (sart_trace_energy_scan: every ray traced once and weighed at every energy, the same
+    rays for all energies).  Returns a dict of arrays: ``energies`` [keV], ``sum_weights``, ``sigma`` = sqrt(sum of squared
+    weights), ``n_passed``, ``efficiency`` = sum_weights / N_RAYS and ``effective_area_cm2`` = pi (test_radius / 10)^2 x efficiency
+    when the source is a parallel beam (None otherwise: a point source's efficiency is no area), plus ``shared`` (the
+    energy-independent counters)."""
+    energies = np.ascontiguousarray(energies_kev, dtype=np.float64)
+    rows, shared = tracer.trace_energy_scan(energies, n_rays, seed, ray_id_offset, flags)
+    n = shared["N_RAYS"]
+    eff = rows["SUM_WEIGHTS"] / n if n > 0 else np.full(energies.size, np.nan)
+    cur = _lib.Setup()
+    _lib.check(tracer.lib.sart_get_setup(tracer.handle, C.byref(cur)))
+    area = np.pi * (cur.test_radius / 10.0) ** 2 * eff if cur.test_parallel else None
+    return dict(energies=energies, sum_weights=rows["SUM_WEIGHTS"], sigma=np.sqrt(rows["SUM_WEIGHTS_SQ"]), n_passed=rows["N_PASSED"],
+                efficiency=eff, effective_area_cm2=area, shared=shared)
 
 
 def performAngularScan(tracer: RayTracer, angularScanMin: float, angularScanMax: float, numAngularScanPoints: int = 50,
