@@ -670,6 +670,58 @@ int sart_trace_energy_scan(sart_context* ctx, const sart_trace_params_t* params,
 int sart_finalize_energy_scan_device(sart_context* ctx, const sart_trace_params_t* params, const double* energies_kev,
                                      int32_t n_energies, const void* scan_fixed_device, double* out_f64_device);
 
+/* ---- per-shell breakdown of the histogram trace -------------------------------- */
+/*
+ * Axion.shellNumber (raytracer.nim:218, set at :2198) is what generateResultPlots breaks the result down by (dfDet's "Shell"
+ * column :2351-2354, energies_by_shell :2361-2376): which shells deliver the flux, at which energies, and where each loses its
+ * rays.  These entry points are sart_trace_histogram_device plus, per shell s < n_shells, the counters and sums of the rays that
+ * selected shell s at shell selection (:1910-1957):
+ *   accumulator_device  what sart_trace_histogram_device accumulates for the same params (image, scalars, spectra with
+ *                       params->spectra; flux-only launches included): bit for bit in SART_ACCUM_FIXED64 against the generic kernel
+ *                       variants (every setup with the X-ray test source, a hole loop or a rotated gas-stage telescope, and any
+ *                       setup with SART_FORCE_GENERIC set) - the solar-source specialisations round a few operations differently
+ *                       and agree to ~1e-12 with the same counters; up to the summation order in SART_ACCUM_F64
+ *   shells_device       the block: n_shells rows of SART_SHELL_ROW 8-byte slots (f64, or int64 when raw SART_ACCUM_FIXED64)
+ *                         SART_SHELL_N_SELECTED            rays that selected shell s (sum over shells = SART_ACC_N_SHELL_SELECTED;
+ *                                                          rays that stage A0 or the shell0_miss_radius shortcut end there count
+ *                                                          as shell 0, where they are)
+ *                         SART_SHELL_N_HIT_NICKEL          stopped by shell s's nickel (:2040-2057)   (= SART_ACC_N_HIT_NICKEL)
+ *                         SART_SHELL_N_PASSED_TILL_WINDOW                                             (= SART_ACC_N_PASSED_TILL_WINDOW)
+ *                         SART_SHELL_N_PASSED                                                         (= SART_ACC_N_PASSED)
+ *                         SART_SHELL_SUM_WEIGHTS, _SUM_WEIGHTS_SQ                                     (= SART_ACC_SUM_WEIGHTS, _SQ)
+ *                         raw FIXED64: + the high limbs SART_SHELL_SUM_WEIGHTS_HI / _SQ_HI, value = (hi 2^40 + lo) quantum
+ *                       and with params->spectra two [n_shells][n_energies + 1] arrays behind the rows: energy counts and energy
+ *                       weights per shell, in the bins of the accumulator's energy spectrum (their sum over shells is that spectrum).
+ * Every "=" above is the sum over shells: exact as integers in FIXED64 (each passed ray adds the same integer to its shell's slot as
+ * to the global one), up to the summation order in f64.  FIXED64 quanta: the accumulator's (frozen for the context in the same way);
+ * params->accumulate applies to both buffers.  Multi-GPU: the block is a flat array of 8-byte slots that ranks reduce as it is -
+ * sart_reduce_across_devices with n_doubles = sart_shell_block_len(...), as int64 in FIXED64 - then finalize.
+ * SART_ERR_INVALID_ARGUMENT, with the context unchanged: a NULL pointer, an invalid image or spectra specification.
+ * Cost: trace_histogram's generic variants plus per selected ray one LDS atomic and per ray behind the mirrors up to five (folded
+ * once per workgroup), two global atomics per passed ray with spectra; the LDS image tile is 53 x 53 instead of 56 x 56.
+ */
+enum { SART_SHELL_N_SELECTED = 0, SART_SHELL_N_HIT_NICKEL = 1, SART_SHELL_N_PASSED_TILL_WINDOW = 2, SART_SHELL_N_PASSED = 3,
+       SART_SHELL_SUM_WEIGHTS = 4, SART_SHELL_SUM_WEIGHTS_SQ = 5, SART_SHELL_SUM_WEIGHTS_HI = 6, SART_SHELL_SUM_WEIGHTS_SQ_HI = 7,
+       SART_SHELL_ROW = 8 };
+/* 8-byte slots of a shell block: n_shells SART_SHELL_ROW, + 2 n_shells (n_energies + 1) with spectra != 0.  (Exported like
+ * sart_energy_scan_len, so that every binding can call it by name.) */
+size_t sart_shell_block_len(int32_t n_shells, int32_t n_energies, int32_t spectra);
+/* accumulator_device: sart_accumulator_len[_spectra] slots; shells_device: sart_shell_block_len(setup n_shells, n_energies,
+ * params->spectra) slots; DEVICE memory.  Asynchronous on the context's stream (the LDS tile's pilot launch as in
+ * sart_trace_histogram_device). */
+int sart_trace_histogram_shells_device(sart_context* ctx, const sart_trace_params_t* params, double* accumulator_device,
+                                       double* shells_device);
+/* Blocking form with HOST outputs (each may be NULL): image, summary, spectra (with params->spectra) as sart_trace_histogram_spectra,
+ * and the block (finalized in FIXED64 mode).  Starts from zero: params->accumulate is not read. */
+int sart_trace_histogram_shells(sart_context* ctx, const sart_trace_params_t* params, double* image_out_host, sart_summary_t* summary_out,
+                                double* spectra_out_host, double* shells_out_host);
+/* Raw FIXED64 block -> doubles with the context's frozen quanta (device pointers; in place allowed); asynchronous.  Checks as the
+ * other finalize kernels ("accumulation mode"): a slot negative or >= 2^62; a shell whose squared weights are not resolved reads NaN
+ * in its SUM_WEIGHTS_SQ; with spectra, a shell whose energy bins do not add up exactly to its N_PASSED / SUM_WEIGHTS; unresolved
+ * weights - surfacing as SART_ERR_ACCUMULATOR from the next sart_synchronize. */
+int sart_finalize_shells_device(sart_context* ctx, const sart_trace_params_t* params, const void* shells_fixed_device,
+                                double* out_f64_device);
+
 /* ---- multi-GPU ---------------------------------------------------------- */
 /*
  * Sum the fused accumulators of n contexts (one per GPU of this process) into the one of contexts[root]:

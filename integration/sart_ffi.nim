@@ -167,6 +167,16 @@ proc sart_trace_energy_scan*(ctx: ptr SartContext, p: ptr SartTraceParams, energ
                              scanOutHost: ptr cdouble): cint {.importc, header: sartH.}
 proc sart_finalize_energy_scan_device*(ctx: ptr SartContext, p: ptr SartTraceParams, energiesKev: ptr cdouble, nEnergies: int32,
                                        scanFixedDevice: pointer, outF64Device: ptr cdouble): cint {.importc, header: sartH.}
+## per-shell breakdown of the histogram trace (Axion.shellNumber): the accumulator of sart_trace_histogram_device plus a block of
+## nShells rows of 8 slots (N_SELECTED, N_HIT_NICKEL, N_PASSED_TILL_WINDOW, N_PASSED, sum w, sum w^2, their FIXED64 high limbs) and,
+## with spectra, [nShells][nEnergies + 1] energy counts and weights
+proc sart_shell_block_len*(nShells, nEnergies, spectra: int32): csize_t {.importc, header: sartH.}
+proc sart_trace_histogram_shells_device*(ctx: ptr SartContext, p: ptr SartTraceParams, accumulatorDevice: ptr cdouble,
+                                         shellsDevice: ptr cdouble): cint {.importc, header: sartH.}
+proc sart_trace_histogram_shells*(ctx: ptr SartContext, p: ptr SartTraceParams, imageOutHost: ptr cdouble, summaryOut: ptr SartSummary,
+                                  spectraOutHost: ptr cdouble, shellsOutHost: ptr cdouble): cint {.importc, header: sartH.}
+proc sart_finalize_shells_device*(ctx: ptr SartContext, p: ptr SartTraceParams, shellsFixedDevice: pointer,
+                                  outF64Device: ptr cdouble): cint {.importc, header: sartH.}
 proc sart_reduce_across_devices*(contexts: ptr ptr SartContext, accumulatorsDevice: ptr ptr cdouble, n: int32, nDoubles: csize_t,
                                  root: int32): cint {.importc, header: sartH.}
 proc sart_enable_kernel_timing*(ctx: ptr SartContext, enable: cint): cint {.importc, header: sartH.}

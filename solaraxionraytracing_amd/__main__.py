@@ -6,6 +6,7 @@
         [--noPlots] [--config FILE | --configPath DIR]  [--rays N] [--seed S] [--outpath DIR]
         [--massScanMin M0 --massScanMax M1 --numMassScanPoints K]     (not in the reference: see below)
         [--energyScanMin E0 --energyScanMax E1 --numEnergyScanPoints K]  (not in the reference: see below)
+        [--shellBreakdown]                                               (not in the reference: see below)
 
 Same switches, same two modes (full run = calculateFluxFractions, :2755-2776; angular scan, :2778-2815).  What differs:
 `--rays` replaces the compile-time constant NumberOfPointsSun (:251, default 1e6), plots are never made (the numbers
@@ -17,7 +18,10 @@ not depend on the mass) and write `axion_mass_scan.csv`.
 A fourth: --energyScanMin / --energyScanMax / --numEnergyScanPoints (keV) run the fused energy scan of the X-ray test source
 (`--xrayTest` or the config's [TestXraySource]; every ray traced once, weighed at every energy) and write `energy_scan.csv`: the
 detection efficiency per energy and, for a parallel beam, the effective area (the quantity of the reference's
-llnl_xray_telescope_cast_effective_area_parallel_light_DTU_thesis.csv).  It cannot be combined with the other scans."""
+llnl_xray_telescope_cast_effective_area_parallel_light_DTU_thesis.csv).  It cannot be combined with the other scans.
+--shellBreakdown (full-run mode only) also breaks the result down by mirror shell (Axion.shellNumber, :218; the data of
+generateResultPlots' dfDet "Shell" column and energies_by_shell plot, :2351-2376) and writes `shell_breakdown_{year}.csv` and
+`energies_by_shell_{year}.csv` beside the image CSV."""
 from __future__ import annotations
 
 import argparse
@@ -28,7 +32,7 @@ import numpy as np
 
 from . import _lib, config as cfgmod
 from .raytracer import (RayTracer, angle_image_names, containment_radii, initFullSetup, performAngularScan, performAxionMassScan,
-                        performEnergyScan, write_image_csv)
+                        performEnergyScan, write_image_csv, write_shell_csvs)
 
 WINDOW_YEAR = {_lib.DK_INGRID2017: "2017", _lib.DK_INGRID2018: "2018", _lib.DK_INGRIDIAXO: "IAXO"}   # WindowYearKind, :1468-1484
 
@@ -56,6 +60,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--energyScanMin", type=float, default=0.0, help="keV (extension: fused energy scan of the X-ray test source)")
     ap.add_argument("--energyScanMax", type=float, default=0.0, help="keV")
     ap.add_argument("--numEnergyScanPoints", type=int, default=32)
+    ap.add_argument("--shellBreakdown", action="store_true",
+                    help="extension (full-run mode): the result per mirror shell, shell_breakdown_{year}.csv and energies_by_shell_{year}.csv")
     ap.add_argument("--config", default="", help="path of a config.toml")
     ap.add_argument("--configPath", default="", help="directory that holds config.toml")
     ap.add_argument("--rays", type=float, default=1e6, help="NumberOfPointsSun (raytracer.nim:251)")
@@ -71,7 +77,10 @@ def energy_scan_requested(args) -> bool:
 
 def check_scan_args(ap: argparse.ArgumentParser, args) -> None:
     """The energy scan is a mode of its own: exits 2 (argparse's usage error) when it is combined with another scan or asks for
-    no valid energies."""
+    no valid energies.  --shellBreakdown belongs to the full-run mode: exits 2 beside any scan."""
+    if getattr(args, "shellBreakdown", False) and (energy_scan_requested(args) or args.massScanMax > args.massScanMin
+                                                   or args.angularScanMin != args.angularScanMax):
+        ap.error("--shellBreakdown belongs to the full run: it cannot be combined with a mass, angular or energy scan")
     if not energy_scan_requested(args):
         return
     if args.massScanMax > args.massScanMin or args.angularScanMin != args.angularScanMax:
@@ -142,9 +151,15 @@ def main(argv=None) -> int:
             print("wrote", out)
         elif args.angularScanMin == args.angularScanMax:
             # calculateFluxFractions + the numbers of generateResultPlots (:2252-2257, :2459-2527, :885-921)
-            img, s, spec = rt.trace_spectra(n, seed=args.seed, flags=flags)
             year = WINDOW_YEAR.get(full.setup.detector_kind, "IAXO")
+            if args.shellBreakdown:
+                img, s, spec, shells = rt.trace_shells(n, seed=args.seed, flags=flags)
+            else:
+                img, s, spec = rt.trace_spectra(n, seed=args.seed, flags=flags)
             write_result(os.path.join(args.outpath, "axion_image_%s.csv" % year), img, s, spec, full.setup.chip_x_max)
+            if args.shellBreakdown:
+                for path in write_shell_csvs(args.outpath, year, shells, full.energies, s["N_RAYS"]):
+                    print("wrote", path)
         else:
             res = performAngularScan(rt, args.angularScanMin, args.angularScanMax, args.numAngularScanPoints, n, seed=args.seed, flags=flags,
                                      fused=args.fusedAngularScan, errors=args.fusedAngularScan, images=args.angularImages)

@@ -55,11 +55,36 @@ ESCAN_HI = dict(SUM_WEIGHTS=4, SUM_WEIGHTS_SQ=5)
 ESCAN_SHARED = dict(N_RAYS=0, N_REACHED_TELESCOPE=1, N_SHELL_SELECTED=2, N_HIT_NICKEL=3)
 ESCAN_MAX_ENERGIES = 32   # csrc/sart_device.h: kEScanMaxEnergies (energies per kernel launch)
 FIXED_LIMB_BITS = 40
+# per-shell breakdown (include/sart.h: SART_SHELL_*): n_shells rows of SHELL_ROW slots, then (spectra) the per-shell energy counts and weights
+SHELL_ROW = 8
+SHELL = dict(N_SELECTED=0, N_HIT_NICKEL=1, N_PASSED_TILL_WINDOW=2, N_PASSED=3, SUM_WEIGHTS=4, SUM_WEIGHTS_SQ=5)
+SHELL_HI = dict(SUM_WEIGHTS=6, SUM_WEIGHTS_SQ=7)
 
 
 def energy_scan_len(n_energies: int) -> int:
     """sart_energy_scan_len: 8-byte slots of an energy-scan accumulator."""
     return (int(n_energies) + 1) * ESCAN_ROW
+
+
+def shell_block_len(n_shells: int, n_energies: int, spectra: bool) -> int:
+    """sart_shell_block_len: 8-byte slots of a per-shell block."""
+    n_shells, n_energies = max(int(n_shells), 0), max(int(n_energies), 0)
+    return n_shells * SHELL_ROW + (2 * n_shells * (n_energies + 1) if spectra else 0)
+
+
+def split_shells(block, n_shells: int, n_energies: int, spectra: bool) -> dict:
+    """Dict of per-shell arrays (keys of SHELL) from a finalized shell block; with ``spectra`` also ``energy_counts`` and
+    ``energy_weights`` [n_shells][n_energies + 1]."""
+    import numpy as np
+    block = np.asarray(block, dtype=np.float64)
+    assert block.size == shell_block_len(n_shells, n_energies, spectra)
+    rows = block[:n_shells * SHELL_ROW].reshape(n_shells, SHELL_ROW)
+    out = {k: rows[:, i].copy() for k, i in SHELL.items()}
+    if spectra:
+        ne1 = int(n_energies) + 1
+        tail = block[n_shells * SHELL_ROW:].reshape(2, n_shells, ne1)
+        out["energy_counts"], out["energy_weights"] = tail[0].copy(), tail[1].copy()
+    return out
 
 
 def split_energy_scan(acc, n_energies: int):
@@ -244,6 +269,10 @@ SART_SYMBOLS = {
     "sart_trace_energy_scan_device": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, C.c_void_p]),
     "sart_trace_energy_scan": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, _dp]),
     "sart_finalize_energy_scan_device": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, C.c_void_p, C.c_void_p]),
+    "sart_shell_block_len": (C.c_size_t, [_i, _i, _i]),
+    "sart_trace_histogram_shells_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p, C.c_void_p]),
+    "sart_trace_histogram_shells": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _P(Summary), _dp, _dp]),
+    "sart_finalize_shells_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p, C.c_void_p]),
     "sart_reduce_across_devices": (C.c_int, [_P(C.c_void_p), _P(C.c_void_p), _i, C.c_size_t, _i]),
     "sart_enable_kernel_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "sart_get_kernel_timing": (C.c_int, [C.c_void_p, _dp, _P(C.c_int64)]),

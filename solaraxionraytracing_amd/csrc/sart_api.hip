@@ -46,6 +46,11 @@ int ascan_images_blocks_per_cu(bool fast);
 int energy_scan_blocks_per_cu(bool rotated);
 void launch_trace_energy_scan(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, const EScanArgs& EN, double* rows,
                               double* shared_row, int n_blocks, hipStream_t stream, bool rotated, bool fixed);
+int shell_histogram_blocks_per_cu(bool rotated);
+void launch_shell_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, double* acc, const ShellArgs& SH,
+                            int n_blocks, hipStream_t stream, bool rotated, bool fixed);
+void launch_finalize_shells(const void* in, double* out, int n_shells, int n_energies1, int spectra, double q_w, double q_w2,
+                            void* check_dev, hipStream_t stream);
 int histogram_block_of(int variant);
 void launch_trace_records(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, sart_axion_t* out, int n_blocks,
                           hipStream_t stream, const double* uniforms_dev);
@@ -275,6 +280,9 @@ struct sart_context {
   bool escan_uploaded = false;
   DevBuf<double> d_escan_refl, d_escan_partials, d_escan, d_escan_fin;
   int blocks_per_cu_escan[2] = {0, 0};
+  // per-shell breakdown: per-workgroup shell tables; scratch accumulator / block of the blocking form and their f64 images
+  DevBuf<double> d_shell_partials, d_sacc, d_sacc_fin, d_sblock, d_sblock_fin;
+  int blocks_per_cu_shells[2] = {0, 0};
 
   // timing
   bool timing = false;
@@ -1663,8 +1671,15 @@ int sart_release_scratch(sart_context* c) {
   return 0;
 }
 
-int sart_trace_histogram_device(sart_context* c, const sart_trace_params_t* p, double* acc_dev) {
-  if (!c || !acc_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+namespace {
+
+size_t shell_block_len_of(const sart_context* c, const sart_trace_params_t* p) {
+  return sart_shell_block_len(c->setup.n_shells, c->n_energies, p->spectra);
+}
+
+// sart_trace_histogram_device, and with `shells_dev` sart_trace_histogram_shells_device: the same host path (quanta, replicas, LDS
+// tile, partials) around trace_histogram_kernel or shell_histogram_kernel.
+int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_dev, double* shells_dev) {
   SART_HIP(hipSetDevice(c->device));
   if (int rc = refresh_derived(c)) return rc;
   if (int rc = sync_blob(c)) return rc;
@@ -1679,6 +1694,7 @@ int sart_trace_histogram_device(sart_context* c, const sart_trace_params_t* p, d
     a.fx_scale_w2 = std::ldexp(1.0, -c->weight_sq_exp);
   }
   if (!p->accumulate) SART_HIP(hipMemsetAsync(acc_dev, 0, acc_len_of(c, p) * sizeof(double), c->stream));
+  if (shells_dev && !p->accumulate) SART_HIP(hipMemsetAsync(shells_dev, 0, shell_block_len_of(c, p) * sizeof(double), c->stream));
   if (a.n_rays == 0) return 0;
   if (a.n_rays > (1ull << 31)) {   // ray indices inside one launch are 32-bit (stage A0 ring): split
     sart_trace_params_t q = *p;
@@ -1687,7 +1703,7 @@ int sart_trace_histogram_device(sart_context* c, const sart_trace_params_t* p, d
       const uint64_t n = std::min<uint64_t>(p->n_rays - done, 1ull << 31);
       q.n_rays = n;
       q.ray_id_offset = p->ray_id_offset + done;
-      if (int rc = sart_trace_histogram_device(c, &q, acc_dev)) return rc;
+      if (int rc = histogram_launch(c, &q, acc_dev, shells_dev)) return rc;
       done += n;
     }
     return 0;
@@ -1774,11 +1790,49 @@ int sart_trace_histogram_device(sart_context* c, const sart_trace_params_t* p, d
         }
         a.tile_x0 = t.x0; a.tile_y0 = t.y0; a.tile_n = t.n;
         a.tile_base = ring_cells_free ? 0 : kTileRingCells;
+        if (shells_dev) {
+          // the shell kernel (generic: its ring 0 is free without stage A0 only) keeps its shell table in the last cells of the
+          // tile space: the same tile, narrowed about its centre
+          const bool free_s = c->hot.n_zones == 0;
+          const int n = std::min(t.n, free_s ? kShellImageTileMax : kShellImageTileExtraMax);
+          a.tile_x0 = t.x0 + (t.n - n) / 2; a.tile_y0 = t.y0 + (t.n - n) / 2; a.tile_n = n;
+          a.tile_base = free_s ? 0 : kTileRingCells;
+        }
       }
     } else {
       a.replicas = acc_dev;
       a.replica_mask = 0u;
     }
+  }
+  if (shells_dev) {
+    const bool rotated = c->params.rotated != 0;   // generic variants: hist_variant_of 1 / 2
+    if (c->blocks_per_cu_shells[rotated] == 0) {
+      c->blocks_per_cu_shells[rotated] = std::max(1, shell_histogram_blocks_per_cu(rotated));
+      if (c->knobs.hist_blocks_per_cu > 0) c->blocks_per_cu_shells[rotated] = c->knobs.hist_blocks_per_cu;
+    }
+    const int n_blocks = grid_for(a.n_rays, c->n_cu, c->blocks_per_cu_shells[rotated], 1024);
+    const size_t rows = std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4);
+    if (c->d_partials.n < static_cast<size_t>(n_blocks) * SART_ACC_COUNT) {
+      SART_HIP(hipStreamSynchronize(c->stream));
+      if (int rc = c->d_partials.resize(rows * SART_ACC_COUNT)) return rc;
+    }
+    if (c->d_shell_partials.n < static_cast<size_t>(n_blocks) * kMaxShells * kShellPartialSlots) {
+      SART_HIP(hipStreamSynchronize(c->stream));
+      if (int rc = c->d_shell_partials.resize(rows * kMaxShells * kShellPartialSlots)) return rc;
+    }
+    a.partials = c->d_partials.p;
+    ShellArgs sh;
+    std::memset(&sh, 0, sizeof sh);
+    sh.block = shells_dev;
+    sh.partials = c->d_shell_partials.p;
+    sh.n_shells = c->setup.n_shells;
+    sh.n_energies1 = c->n_energies + 1;
+    {
+      TimedLaunch tl(c);
+      launch_shell_histogram(c->hot, c->hotb, c->d_blob.p, a, acc_dev, sh, n_blocks, c->stream, rotated, fixed);
+    }
+    SART_HIP(hipGetLastError());
+    return 0;
   }
   if (c->blocks_per_cu_hist[variant] == 0) {
     c->blocks_per_cu_hist[variant] = std::max(1, histogram_blocks_per_cu(variant));
@@ -1797,6 +1851,79 @@ int sart_trace_histogram_device(sart_context* c, const sart_trace_params_t* p, d
   }
   SART_HIP(hipGetLastError());
   return 0;
+}
+
+// params that a shell launch and its finalize accept (the context stays as it is otherwise)
+int shells_check(sart_context* c, const sart_trace_params_t* p) {
+  if ((p->image_nx < 1 || p->image_ny < 1) && !(p->image_nx == 0 && p->image_ny == 0)) return fail(SART_ERR_INVALID_ARGUMENT, "invalid image specification");
+  if (p->image_nx > 0 && (!(p->image_x_max > p->image_x_min) || !(p->image_y_max > p->image_y_min)))
+    return fail(SART_ERR_INVALID_ARGUMENT, "invalid image specification");
+  if (p->spectra && (p->n_radial_bins < 1 || !(p->radial_max > 0.0) || !c->have_solar))
+    return fail(SART_ERR_INVALID_ARGUMENT, "invalid spectra specification");
+  if (!c->have_setup) return fail(SART_ERR_NOT_READY, "no setup");
+  return 0;
+}
+
+}  // namespace
+
+int sart_trace_histogram_device(sart_context* c, const sart_trace_params_t* p, double* acc_dev) {
+  if (!c || !acc_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  return histogram_launch(c, p, acc_dev, nullptr);
+}
+
+size_t sart_shell_block_len(int32_t n_shells, int32_t n_energies, int32_t spectra) {
+  const size_t ns = n_shells > 0 ? static_cast<size_t>(n_shells) : 0u;
+  return ns * static_cast<size_t>(SART_SHELL_ROW) + (spectra ? 2u * ns * (static_cast<size_t>(n_energies > 0 ? n_energies : 0) + 1u) : 0u);
+}
+
+int sart_trace_histogram_shells_device(sart_context* c, const sart_trace_params_t* p, double* acc_dev, double* shells_dev) {
+  if (!c || !p || !acc_dev || !shells_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (int rc = shells_check(c, p)) return rc;
+  return histogram_launch(c, p, acc_dev, shells_dev);
+}
+
+int sart_finalize_shells_device(sart_context* c, const sart_trace_params_t* p, const void* raw_dev, double* out_dev) {
+  if (!c || !p || !raw_dev || !out_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (int rc = shells_check(c, p)) return rc;
+  if (!c->quanta_frozen) return fail(SART_ERR_NOT_READY, "no FIXED64 launch has fixed the quanta yet");
+  SART_HIP(hipSetDevice(c->device));
+  if (int rc = status_ensure(c)) return rc;
+  launch_finalize_shells(raw_dev, out_dev, c->setup.n_shells, c->n_energies + 1, p->spectra ? 1 : 0, std::ldexp(1.0, c->weight_exp),
+                         std::ldexp(1.0, c->weight_sq_exp), c->d_status.p, c->stream);
+  SART_HIP(hipGetLastError());
+  return status_enqueue_copy(c);
+}
+
+int sart_trace_histogram_shells(sart_context* c, const sart_trace_params_t* p, double* image_out, sart_summary_t* summary,
+                                double* spectra_out, double* shells_out) {
+  if (!c || !p) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (int rc = shells_check(c, p)) return rc;
+  SART_HIP(hipSetDevice(c->device));
+  const size_t len = acc_len_of(c, p), slen = shell_block_len_of(c, p);
+  if (int rc = c->d_sacc.reserve(len)) return rc;
+  if (int rc = c->d_sblock.reserve(slen)) return rc;
+  sart_trace_params_t q = *p;
+  q.accumulate = 0;   // the blocking form has no accumulator the caller could add into
+  if (int rc = histogram_launch(c, &q, c->d_sacc.p, c->d_sblock.p)) return rc;
+  const double* src = c->d_sacc.p;
+  const double* ssrc = c->d_sblock.p;
+  if (c->accum_mode == SART_ACCUM_FIXED64) {
+    if (int rc = c->d_sacc_fin.reserve(len)) return rc;
+    if (int rc = c->d_sblock_fin.reserve(slen)) return rc;
+    if (int rc = sart_finalize_accumulator_device(c, p, c->d_sacc.p, c->d_sacc_fin.p)) return rc;
+    if (int rc = sart_finalize_shells_device(c, p, c->d_sblock.p, c->d_sblock_fin.p)) return rc;
+    src = c->d_sacc_fin.p;
+    ssrc = c->d_sblock_fin.p;
+  }
+  const size_t nimg = static_cast<size_t>(p->image_nx) * p->image_ny;
+  if (image_out && nimg) SART_HIP(hipMemcpyAsync(image_out, src, nimg * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (summary) SART_HIP(hipMemcpyAsync(summary->v, src + nimg, SART_ACC_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (spectra_out && p->spectra)
+    SART_HIP(hipMemcpyAsync(spectra_out, src + nimg + SART_ACC_COUNT, (len - nimg - SART_ACC_COUNT) * sizeof(double),
+                            hipMemcpyDeviceToHost, c->stream));
+  if (shells_out) SART_HIP(hipMemcpyAsync(shells_out, ssrc, slen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  SART_HIP(hipStreamSynchronize(c->stream));
+  return status_take(c);
 }
 
 int sart_trace_histogram(sart_context* c, const sart_trace_params_t* p, double* image_out, sart_summary_t* summary) {

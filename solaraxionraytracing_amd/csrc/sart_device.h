@@ -322,4 +322,20 @@ constexpr int kTileExtraCells = 1090;
 constexpr int kImageTileMax = 56;
 constexpr int kImageTileExtraMax = 33;   // 33 x 33 <= kTileExtraCells: the tile of the variants whose rings are all in use
 
+// Per-shell breakdown of the histogram trace (include/sart.h: sart_trace_histogram_shells_device).  shell_histogram_kernel keeps,
+// per workgroup and shell, four u32 counters and two sums in LDS - in the last kShellTableCells cells behind the tables, where the
+// histogram kernels keep the end of the image tile (its tile is therefore at most kShellImageTileMax / kShellImageTileExtraMax wide)
+// - and stores them once to partials[n_blocks][kMaxShells][kShellPartialSlots]; fold_shells_kernel adds those to the caller's block.
+constexpr int kShellPartialSlots = 6;   // N_SELECTED, N_HIT_NICKEL, N_PASSED_TILL_WINDOW, N_PASSED, sum of w, sum of w^2
+constexpr int kShellTableCells = kMaxShells * 4 / 2 + kMaxShells * 2;   // the u32 counters and the 8-byte sums, in 8-byte cells
+constexpr int kShellImageTileMax = 53;        // 53 x 53 <= kTileRingCells + kTileExtraCells - kShellTableCells
+constexpr int kShellImageTileExtraMax = 28;   // 28 x 28 <= kTileExtraCells - kShellTableCells
+struct ShellArgs {
+  double* block;          // the caller's block: rows of SART_SHELL_ROW slots, then (spectra) the per-shell energy counts and weights
+  double* partials;       // [n_blocks][kMaxShells][kShellPartialSlots] per-workgroup counters and sums (plain stores)
+  int32_t n_shells, n_energies1;
+  double _pad;
+};
+static_assert(sizeof(ShellArgs) == 32, "the kernel re-reads ShellArgs with scalar loads");
+
 }  // namespace sart

@@ -1907,6 +1907,383 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
 }
 
 // ------------------------------------------------------------------------------------------------
+// per-shell breakdown of the histogram trace (include/sart.h: sart_trace_histogram_shells_device)
+// ------------------------------------------------------------------------------------------------
+// trace_histogram_kernel's generic variants (stage read at run time, the path carried through ring 1; ROT: rotated telescope) with
+// the same accumulator - image, scalars, spectra - plus, per shell, the counters and sums of the rays that selected it.  Shells
+// differ from lane to lane, so those go to a per-workgroup table in LDS (ds_add_u32 for the counters, ds_add_f64 / ds_add_u64 for
+// the sums) that is stored once per workgroup and folded by fold_shells_kernel; the per-shell energy spectra spread over
+// n_shells x (n_energies + 1) slots and take global atomics like the existing spectra.  The table lives in the last
+// kShellTableCells cells behind the tables, so the LDS image tile is at most kShellImageTileMax wide (host: sart_api.hip).
+struct ShellKernArgs {
+  HotA H;
+  const DevBlob* blob;
+  TraceArgs A;
+  double* acc;
+  HotB HB;
+  ShellArgs SH;
+};
+static_assert(offsetof(ShellKernArgs, A) == offsetof(HistKernArgs, A) && offsetof(ShellKernArgs, HB) == offsetof(HistKernArgs, HB) &&
+                  offsetof(ShellKernArgs, SH) == offsetof(HistKernArgs, SC),
+              "the shell kernel shares the argument offsets of the histogram kernel");
+static_assert(kShellImageTileMax * kShellImageTileMax <= kTileRingCells + kTileExtraCells - kShellTableCells &&
+                  kShellImageTileExtraMax * kShellImageTileExtraMax <= kTileExtraCells - kShellTableCells,
+              "the shell kernel's image tile leaves the shell table alone");
+
+template <int BLOCK, bool ROT, bool FIXED>
+__global__ __launch_bounds__(BLOCK) void shell_histogram_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
+                                                                double* __restrict__ acc, HotB HBarg, ShellArgs SHarg) {
+  using Sum = std::conditional_t<FIXED, long long, double>;   // per-lane sums: quanta (FIXED) or f64
+  struct LdsLayout {
+    TablesLds S;
+    double tile_extra[kTileExtraCells - kShellTableCells];   // cells kTileRingCells .. of the image tile
+    uint32_t shell_cnt[kMaxShells][4];                       // per shell: N_SELECTED, N_HIT_NICKEL, N_PASSED_TILL_WINDOW, N_PASSED
+    Sum shell_sum[kMaxShells][2];                            // per shell: sum of w, sum of w^2
+    DevBlob B;
+    TraceArgs Ab;
+    QueueLds<BLOCK / 64> Q;
+  };
+  __shared__ LdsLayout lds;
+  TablesLds& S = lds.S;
+  QueueLds<BLOCK / 64>& Q = lds.Q;
+  static_assert((offsetof(LdsLayout, Q) % 512) == 0, "the rings are addressed with ds_*2st64 offsets");
+  static_assert((BLOCK / 64) * kQueue == kTileRingCells, "ring 0 of this workgroup is the first part of the tile space");
+  static_assert(sizeof(lds.shell_cnt) + sizeof(lds.shell_sum) == kShellTableCells * sizeof(double), "the shell table's cells");
+  // cell t of the LDS image tile: ring 0 (stage A0 off: ray + u3hi columns, 128 doubles per wave), then the cells behind the tables
+  auto tile_cell = [&](uint32_t t) -> double* {
+    return t < (uint32_t)kTileRingCells ? reinterpret_cast<double*>(&Q.w[t >> 7].ray[0]) + (t & 127u)
+                                        : &lds.tile_extra[t - (uint32_t)kTileRingCells];
+  };
+  DevBlob& B = lds.B;
+  TraceArgs& Ab = lds.Ab;
+  {
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(blob);
+    uint64_t* dst = reinterpret_cast<uint64_t*>(&B);
+    for (int i = threadIdx.x; i < (int)(sizeof(DevBlob) / 8); i += BLOCK) dst[i] = src[i];
+    if (threadIdx.x == 0) Ab = A;
+    __syncthreads();
+  }
+  const DevParams& Pb = B.P;
+  const DevTables& Tb = B.T;
+  {
+    uint64_t* q = reinterpret_cast<uint64_t*>(&Q);
+    for (int i = threadIdx.x; i < (int)(sizeof(Q) / 8); i += BLOCK) q[i] = 0ull;
+    for (int i = threadIdx.x; i < kTileExtraCells - kShellTableCells; i += BLOCK) lds.tile_extra[i] = 0.0;
+    for (int i = threadIdx.x; i < kMaxShells * 4; i += BLOCK) lds.shell_cnt[i >> 2][i & 3] = 0u;
+    for (int i = threadIdx.x; i < kMaxShells * 2; i += BLOCK) lds.shell_sum[i >> 1][i & 1] = 0;
+  }
+  stage_tables<BLOCK>(S, Pb, Tb);   // (its barrier orders the zeroing above before the first use)
+  const LdsTables L{S.sincos, S.rcdf_hi, Tb.flux_radius_cdf, S.rguide, S.shells, S.lut};
+
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint64_t waves_total = (uint64_t)gridDim.x * (BLOCK / 64);
+  const uint64_t wave_global = (uint64_t)blockIdx.x * (BLOCK / 64) + wave;
+  const bool early_reject = H.n_zones > 0;   // wave-uniform; the host builds no zones for the X-ray test source
+  const uint64_t first_chunk = A.ray_id_offset >> 8;
+  uint64_t id_base = first_chunk << 8;
+  asm volatile("" : "+s"(id_base));
+  const uint32_t rel_begin = (uint32_t)(A.ray_id_offset & 255u);
+  const uint32_t rel_end = rel_begin + (uint32_t)A.n_rays;
+  const uint32_t n_chunks = (rel_end + 255u) >> 8;
+
+  uint32_t n_reached = 0, n_shell = 0, n_nickel = 0, n_till = 0, n_passed = 0;   // wave-uniform
+  uint32_t n_outside = 0;    // per lane: passed rays outside the image
+  Sum sum_w = 0, sum_w2 = 0, sum_x = 0, sum_y = 0, sum_r = 0;
+  long long sum_wo = 0;      // FIXED: weights of the passed rays outside the image
+  uint32_t h0 = 0, t0 = 0;   // ring 0 (A0 -> A1)
+  uint32_t h1 = 0, t1 = 0;   // ring 1 (A1 -> B)
+  auto ring_sync = [] {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
+  auto prefix_of = [](uint64_t mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+  };
+  auto shell_of = [](int shell) { return min((uint32_t)shell, (uint32_t)(kMaxShells - 1)); };   // (phase A: shell < n_shells <= 64)
+
+  // phase A as in trace_histogram_kernel's generic variants; every selected ray counts for its shell, those that the
+  // shell0_miss_radius compare ends here included (their shell is shell 0)
+  auto run_phase_a = [&](uint32_t rel, bool valid, uint32_t u3_hi) {
+    SART_STAGE_MARK("A1");
+    __builtin_amdgcn_s_setprio(SART_PRIO_A1);
+    RayState st;
+    bool sampled = false, reached = false;
+    double radial;
+    HotA Hl;
+    reload_hot(Hl);
+    LaneMasks M;
+    (void)phase_a<false, ROT ? 1 : 0, false, false>(Hl, Pb, L, A.seed_lo, A.seed_hi, id_base + (uint64_t)rel, u3_hi, st, sampled, reached, radial, M);
+    const uint64_t valid_m = ballot64(valid);
+    n_reached += (uint32_t)__popcll(valid_m & M.reached);
+    const uint64_t selected = valid_m & M.ok;
+    n_shell += (uint32_t)__popcll(selected);
+    if (__builtin_amdgcn_inverse_ballot_w64(selected))
+      __hip_atomic_fetch_add(&lds.shell_cnt[shell_of(st.shell)][0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    const uint64_t mask = selected & ~ballot64(radial < Pb.shell0_miss_radius);
+    const uint32_t cnt = (uint32_t)__popcll(mask);
+    if (__builtin_amdgcn_inverse_ballot_w64(mask)) {
+      const uint32_t slot = (t1 + prefix_of(mask)) % kQueue;
+      Q.w[wave].X0[slot] = st.X0; Q.w[wave].Y0[slot] = st.Y0;
+      Q.w[wave].tsx[slot] = st.tsx; Q.w[wave].tsy[slot] = st.tsy;
+      Q.w[wave].path[slot] = st.path_cb;
+      Q.w[wave].u5[slot] = st.u5;
+      Q.w[wave].idx[slot] = st.r_idx | (st.shell << 16);
+    }
+    t1 += cnt;
+    __builtin_amdgcn_s_setprio(0);
+  };
+
+  auto run_phase_b = [&](uint32_t n_valid) {
+    SART_STAGE_MARK("B");
+    __builtin_amdgcn_s_setprio(SART_PRIO_B);
+    RayState st;
+    const bool valid = (uint32_t)lane < n_valid;
+    const uint32_t slot = (h1 + (uint32_t)lane) % kQueue;
+    RayOut out;
+    {
+      st.X0 = Q.w[wave].X0[slot]; st.Y0 = Q.w[wave].Y0[slot];
+      st.tsx = Q.w[wave].tsx[slot]; st.tsy = Q.w[wave].tsy[slot];
+      st.path_cb = Q.w[wave].path[slot];
+      st.u5 = Q.w[wave].u5[slot];
+      if (!ROT) {
+        st.zcb = -(H.dz3 - H.dz1);
+      } else {
+        st.zcb = zcb_rotated(Pb.rx_s, -Pb.rx_c * Pb.ry_s, Pb.rx_c * Pb.ry_c, Pb.half_length_telescope, st.X0 + Pb.entrance_x,
+                             st.Y0 + Pb.entrance_y, st.tsx, st.tsy, H.dz3 - H.dz1);
+      }
+      const int packed = Q.w[wave].idx[slot];
+      st.r_idx = packed & 0xFFFF;
+      st.shell = packed >> 16;
+      const DevBlob& Bo = lds_opaque(B);
+      HotB HB;
+      reload_kernarg(HB, offsetof(ShellKernArgs, HB));
+      asm volatile("" :: "s"(HB.cdf_hi32), "s"(HB.energy_guide), "s"(HB.energy_tab), "s"(HB.refl), "s"(HB.refl_n_angles), "s"(HB.cdf_stride));
+      phase_b<false, false, -1, false>(Bo.P, L, HB, lds_opaque(Ab), st, H.test_active ? Pb.n_energies : -1, valid, out, nullptr);
+    }
+    h1 += n_valid;
+    __builtin_amdgcn_s_setprio(SART_PRIO_ACC);
+    n_nickel += (uint32_t)__popcll(out.m_nickel);
+    n_till += (uint32_t)__popcll(out.m_till);
+    n_passed += (uint32_t)__popcll(out.m_passed);
+    const uint32_t sh = shell_of(st.shell);
+    if (__builtin_amdgcn_inverse_ballot_w64(out.m_nickel))
+      __hip_atomic_fetch_add(&lds.shell_cnt[sh][1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (__builtin_amdgcn_inverse_ballot_w64(out.m_till))
+      __hip_atomic_fetch_add(&lds.shell_cnt[sh][2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (out.passed) {
+      SART_STAGE_MARK("ACC");
+      TraceArgs Al;
+      reload_kernarg(Al, offsetof(ShellKernArgs, A));
+      asm volatile("" :: "s"(Al.replicas), "s"(Al.replica_mask), "s"(Al.replica_stride), "s"(Al.image_nx), "s"(Al.image_ny),
+                   "s"(Al.image_x_min), "s"(Al.image_y_min), "s"(Al.image_inv_step_x), "s"(Al.image_inv_step_y), "s"(Al.spectra),
+                   "s"(Al.tile_x0), "s"(Al.tile_y0), "s"(Al.tile_n), "s"(Al.tile_base));
+      __hip_atomic_fetch_add(&lds.shell_cnt[sh][3], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      long long w_fx = 0;   // FIXED: this ray's weight in quanta (what the image, the sums and the spectra add)
+      if constexpr (FIXED) {
+        w_fx = to_fixed(out.weight, Al.fx_scale_w);
+        const long long w2_fx = to_fixed(out.weight * out.weight, Al.fx_scale_w2);
+        sum_w += w_fx;
+        sum_w2 += w2_fx;
+        sum_x += to_fixed(out.px, kFixedPositionScale);
+        sum_y += to_fixed(out.py, kFixedPositionScale);
+        sum_r += to_fixed(out.rdet, kFixedPositionScale);
+        // the same integers the scalars add: the per-shell sums add up to SUM_WEIGHTS / SUM_WEIGHTS_SQ exactly
+        __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(&lds.shell_sum[sh][0]), (unsigned long long)w_fx, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(&lds.shell_sum[sh][1]), (unsigned long long)w2_fx, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_WORKGROUP);
+      } else {
+        sum_w += out.weight;
+        sum_w2 = fma(out.weight, out.weight, sum_w2);
+        sum_x += out.px;
+        sum_y += out.py;
+        sum_r += out.rdet;
+        __hip_atomic_fetch_add(&lds.shell_sum[sh][0], out.weight, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(&lds.shell_sum[sh][1], out.weight * out.weight, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      // prepareHeatmap (:838-842), as trace_histogram_kernel bins it
+      const double fx = (out.px - Al.image_x_min) * Al.image_inv_step_x;
+      const double fy = (out.py - Al.image_y_min) * Al.image_inv_step_y;
+      const int nx = Al.image_nx, ny = Al.image_ny;
+      const uint64_t inside_m = ballot64(fx >= 0.0) & ballot64(fx < (double)nx) & ballot64(fy >= 0.0) & ballot64(fy < (double)ny);
+      const bool inside = __builtin_amdgcn_inverse_ballot_w64(inside_m);
+      n_outside += inside ? 0u : 1u;
+      if constexpr (FIXED) {
+        if (out.m_passed & ~inside_m) sum_wo += inside ? 0ll : w_fx;
+      }
+      double* const img = Al.replicas + (size_t)((uint32_t)wave_global & Al.replica_mask) * (size_t)Al.replica_stride;
+      if (inside) {
+        const uint32_t ix = (uint32_t)(int)fx, iy = (uint32_t)(int)fy;
+        const uint32_t tn = (uint32_t)Al.tile_n;
+        const uint32_t tx = ix - (uint32_t)Al.tile_x0, ty = iy - (uint32_t)Al.tile_y0;
+        if ((tx < tn) & (ty < tn)) {
+          const uint32_t t = ty * tn + tx + (uint32_t)Al.tile_base;   // < kTileRingCells + kTileExtraCells - kShellTableCells (host)
+          if constexpr (FIXED)
+            __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(tile_cell(t)), (unsigned long long)w_fx, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+          else
+            __hip_atomic_fetch_add(tile_cell(t), out.weight, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        } else {
+          const uint32_t pix = iy * (uint32_t)nx + ix;
+          typedef __attribute__((address_space(1))) char* gbytes;
+          if constexpr (FIXED) atomic_add_slot_i64((double*)((gbytes)img + pix * 8u), w_fx);
+          else unsafeAtomicAdd((double*)((gbytes)img + pix * 8u), out.weight);
+        }
+      }
+      if (Al.spectra) {   // wave-uniform: the spectra behind the scalars, and the same energy bins per shell in the block
+        double* rad = acc + (size_t)nx * (size_t)ny + SART_ACC_COUNT;
+        double* en = rad + 2 * (size_t)Al.n_radial_bins;
+        const size_t ne1 = (size_t)Pb.n_energies + 1;
+        const int rb = min((int)(out.rdet * Al.radial_inv_bin), Al.n_radial_bins - 1);
+        ShellArgs SHl;
+        reload_kernarg(SHl, offsetof(ShellKernArgs, SH));
+        double* const sen = SHl.block + (size_t)SHl.n_shells * SART_SHELL_ROW + (size_t)sh * ne1 + (size_t)out.e_idx;   // counts[sh][e]
+        const size_t sw_off = (size_t)SHl.n_shells * ne1;                                                             // -> weights[sh][e]
+        if constexpr (FIXED) {
+          atomic_add_slot_i64(&rad[rb], 1);
+          atomic_add_slot_i64(&rad[(size_t)Al.n_radial_bins + rb], w_fx);
+          atomic_add_slot_i64(&en[out.e_idx], 1);
+          atomic_add_slot_i64(&en[ne1 + out.e_idx], w_fx);
+          atomic_add_slot_i64(&en[2 * ne1 + out.e_idx], to_fixed(out.reflect, kFixedReflectScale));
+          atomic_add_slot_i64(sen, 1);
+          atomic_add_slot_i64(sen + sw_off, w_fx);
+        } else {
+          unsafeAtomicAdd(&rad[rb], 1.0);
+          unsafeAtomicAdd(&rad[(size_t)Al.n_radial_bins + rb], out.weight);
+          unsafeAtomicAdd(&en[out.e_idx], 1.0);
+          unsafeAtomicAdd(&en[ne1 + out.e_idx], out.weight);
+          unsafeAtomicAdd(&en[2 * ne1 + out.e_idx], out.reflect);
+          unsafeAtomicAdd(sen, 1.0);
+          unsafeAtomicAdd(sen + sw_off, out.weight);
+        }
+      }
+    }
+    __builtin_amdgcn_s_setprio(0);
+  };
+
+  // stage A0 as in the generic histogram variants (zone bounds re-read from the kernel arguments per pass)
+  uint32_t chunk = (uint32_t)wave_global;
+  const uint32_t lane4 = 4u * (uint32_t)lane;
+  uint32_t pass = 0;
+  U4 stream = U4{0u, 0u, 0u, 0u};
+  for (;;) {
+    const bool have_new = chunk < n_chunks;   // wave-uniform
+    SART_STAGE_MARK("LOOP");
+    if (have_new) {
+      SART_STAGE_MARK("A0");
+      if (pass == 0u) stream = stream_block(((first_chunk + (uint64_t)chunk) << 6) + (uint64_t)lane, A.seed_lo, A.seed_hi);
+      const uint32_t w = word_of(stream, pass);
+      const uint32_t rel = ((chunk << 8) + pass) + lane4;
+      if (early_reject) {
+        ZoneTable Z;
+        reload_zones(Z);
+        uint64_t dead_m = 0, reached_m = 0;
+#pragma unroll
+        for (int z = 0; z < kMaxZones; ++z) {
+          const uint64_t in = ballot64(w >= Z.lo[z]) & ballot64(w <= Z.hi[z]);
+          dead_m |= in;
+          reached_m |= ((Z.zone_reached >> z) & 1u) ? in : 0ull;
+        }
+        const uint32_t chunk_lo = chunk << 8;
+        uint64_t valid_m = ~0ull;
+        if ((chunk_lo < rel_begin) | (chunk_lo + 256u > rel_end)) valid_m = ballot64(rel >= rel_begin) & ballot64(rel < rel_end);
+        n_reached += (uint32_t)__popcll(valid_m & reached_m);
+        const uint64_t mask = valid_m & ~dead_m;
+        if (__builtin_amdgcn_inverse_ballot_w64(mask)) {
+          const uint32_t slot = (t0 + prefix_of(mask)) % kQueue;
+          Q.w[wave].ray[slot] = rel;
+          Q.w[wave].u3hi[slot] = w;
+        }
+        t0 += (uint32_t)__popcll(mask);
+      } else {
+        run_phase_a(rel, (rel >= rel_begin) & (rel < rel_end), w);
+      }
+      pass = (pass + 1u) & 3u;
+      if (pass == 0u) chunk += (uint32_t)waves_total;
+      ring_sync();
+    }
+    if (early_reject) {
+      const uint32_t n0 = t0 - h0;
+      if ((n0 >= 64u) | (!have_new & (n0 > 0u))) {
+        const uint32_t m = min(n0, 64u);
+        const bool v = (uint32_t)lane < m;
+        const uint32_t slot = (h0 + (uint32_t)lane) % kQueue;
+        const uint32_t rel = Q.w[wave].ray[slot];
+        const uint32_t w = Q.w[wave].u3hi[slot];
+        h0 += m;
+        run_phase_a(rel, v, w);
+        ring_sync();
+      }
+    }
+    const uint32_t n1 = t1 - h1;
+    const bool draining = !have_new & (t0 == h0);
+    if ((n1 >= 64u) | (draining & (n1 > 0u))) {
+      run_phase_b(min(n1, 64u));
+      ring_sync();
+    }
+    if (draining & (t1 == h1)) break;
+  }
+
+  SART_STAGE_MARK("EPILOGUE");
+  // flush of the LDS image tile: one global atomic per non-empty tile pixel and workgroup
+  if (A.tile_n > 0) {
+    __syncthreads();
+    const uint32_t tn = (uint32_t)A.tile_n, n_tile = tn * tn;
+    double* const img = A.replicas + (size_t)((uint32_t)wave_global & A.replica_mask) * (size_t)A.replica_stride;
+    for (uint32_t t = threadIdx.x; t < n_tile; t += BLOCK) {
+      const double v = *tile_cell(t + (uint32_t)A.tile_base);
+      if (__double_as_longlong(v) != 0ll) {
+        const uint32_t ty = t / tn, tx = t - ty * tn;
+        double* const px = &img[(size_t)((uint32_t)A.tile_y0 + ty) * (size_t)A.image_nx + ((uint32_t)A.tile_x0 + tx)];
+        if constexpr (FIXED) atomic_add_slot_i64(px, __double_as_longlong(v));
+        else unsafeAtomicAdd(px, v);
+      }
+    }
+  }
+  // scalars: as trace_histogram_kernel (wave reduction -> LDS staging in wave 0's first ring columns -> one store per workgroup)
+  __syncthreads();
+  Sum (*const red)[SART_ACC_COUNT] = reinterpret_cast<Sum (*)[SART_ACC_COUNT]>(&Q.w[0].X0[0]);
+  Sum sw, sw2, sxx, syy, srr;
+  if constexpr (FIXED) {
+    sw = wave_sum_i64(sum_w); sw2 = wave_sum_i64(sum_w2); sxx = wave_sum_i64(sum_x); syy = wave_sum_i64(sum_y); srr = wave_sum_i64(sum_r);
+  } else {
+    sw = wave_sum(sum_w); sw2 = wave_sum(sum_w2); sxx = wave_sum(sum_x); syy = wave_sum(sum_y); srr = wave_sum(sum_r);
+  }
+  const long long swo = FIXED ? wave_sum_i64(sum_wo) : 0ll;
+  const long long n_out = wave_sum_i64((long long)n_outside);
+  if (lane == 0) {
+    Sum* r = red[wave];
+    for (int k = 0; k < SART_ACC_COUNT; ++k) r[k] = 0;
+    r[SART_ACC_SUM_WEIGHTS] = sw;
+    r[SART_ACC_SUM_WEIGHTS_SQ] = sw2;
+    r[SART_ACC_SUM_X] = sxx;
+    r[SART_ACC_SUM_Y] = syy;
+    r[SART_ACC_SUM_R] = srr;
+    r[SART_ACC_N_PASSED] = (Sum)n_passed;
+    r[SART_ACC_N_PASSED_TILL_WINDOW] = (Sum)n_till;
+    r[SART_ACC_N_HIT_NICKEL] = (Sum)n_nickel;
+    r[SART_ACC_N_REACHED_TELESCOPE] = (Sum)n_reached;
+    r[SART_ACC_N_SHELL_SELECTED] = (Sum)n_shell;
+    r[SART_ACC_N_OUTSIDE_IMAGE] = (Sum)n_out;
+    if constexpr (FIXED) r[SART_ACC_SUM_WEIGHTS_OUTSIDE] = swo;
+  }
+  __syncthreads();
+  if (threadIdx.x < SART_ACC_COUNT) {
+    Sum t = 0;
+    for (int w = 0; w < BLOCK / 64; ++w) t += red[w][threadIdx.x];
+    reinterpret_cast<Sum*>(A.partials)[(size_t)blockIdx.x * SART_ACC_COUNT + threadIdx.x] = t;
+  }
+  // the shell table of this workgroup (every wave has left the loop: the barriers above)
+  for (int i = threadIdx.x; i < kMaxShells * kShellPartialSlots; i += BLOCK) {
+    const int s = i / kShellPartialSlots, j = i - s * kShellPartialSlots;
+    const Sum v = j < 4 ? (Sum)lds.shell_cnt[s][j] : lds.shell_sum[s][j - 4];
+    reinterpret_cast<Sum*>(SHarg.partials)[(size_t)blockIdx.x * (kMaxShells * kShellPartialSlots) + i] = v;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // fused energy scan (include/sart.h: sart_trace_energy_scan)
 // ------------------------------------------------------------------------------------------------
 // With the X-ray test source (sart_setup_t::test_active) the energy is a constant of the setup (energyAx = testSource.energy,
@@ -3367,6 +3744,108 @@ __global__ __launch_bounds__(64) void finalize_scan_kernel(const long long* in, 
   }
 }
 
+// Per-shell block (include/sart.h: SART_SHELL_*) += the per-workgroup shell tables of one shell_histogram_kernel launch.  One
+// workgroup per shell, 64 threads = 8 slots (6 used) x 8 groups of workgroups; group g sums the partials g, g + 8, ... in that order
+// and slot j's first thread adds the eight group sums in order: the summation tree is fixed for a given grid.  FIXED: integers, the
+// two sums in two limbs (hi 2^40 + lo, lo in [0, 2^40)) like fold_scalars_fixed_kernel.
+template <bool FIXED>
+__global__ __launch_bounds__(64) void fold_shells_kernel(double* __restrict__ block_, const double* __restrict__ partials_, int n_blocks) {
+  using Sum = std::conditional_t<FIXED, long long, double>;
+  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
+  Sum* const row = reinterpret_cast<Sum*>(block_) + (size_t)blockIdx.x * SART_SHELL_ROW;
+  const Sum* const part = reinterpret_cast<const Sum*>(partials_);
+  __shared__ Sum red_lo[8][8], red_hi[8][8];
+  const int j = threadIdx.x & 7, g = threadIdx.x >> 3;
+  Sum lo = 0, hi = 0;
+  if (j < kShellPartialSlots)
+    for (int b = g; b < n_blocks; b += 8) {
+      const Sum p = part[((size_t)b * kMaxShells + blockIdx.x) * kShellPartialSlots + j];
+      if constexpr (FIXED) { lo += p & kMask; hi += p >> kFixedLimbBits; } else lo += p;
+    }
+  red_lo[g][j] = lo;
+  red_hi[g][j] = hi;
+  __syncthreads();
+  if (g != 0 || j >= kShellPartialSlots) return;
+  lo = 0; hi = 0;
+  for (int i = 0; i < 8; ++i) { lo += red_lo[i][j]; hi += red_hi[i][j]; }
+  // partial slots 0 .. 3 are the counters SART_SHELL_N_*, 4 / 5 the sums
+  if (j < 4) {
+    if constexpr (FIXED) row[j] += (hi << kFixedLimbBits) + lo; else row[j] += lo;
+  } else {
+    const int s = j == 4 ? SART_SHELL_SUM_WEIGHTS : SART_SHELL_SUM_WEIGHTS_SQ, sh = j == 4 ? SART_SHELL_SUM_WEIGHTS_HI : SART_SHELL_SUM_WEIGHTS_SQ_HI;
+    if constexpr (FIXED) {
+      lo += row[s];
+      row[s] = lo & kMask;
+      row[sh] += hi + (lo >> kFixedLimbBits);
+    } else {
+      row[s] += lo;
+    }
+  }
+}
+
+// Raw FIXED64 shell block -> doubles (sart_finalize_shells_device).  One workgroup per shell: its row and, with spectra, its two
+// energy arrays.  Each slot is read and written by the same thread (in place allowed).  Checks, as finalize_fixed_kernel and
+// finalize_scan_kernel do them: every slot in [0, 2^62); the shell's weights resolved (its SUM_WEIGHTS_SQ reads NaN where the squared
+// weights are not); and, with spectra, the exact conservation laws of the block itself - every passed ray of the shell adds the same
+// integer to SUM_WEIGHTS and to one energy-weight bin, and 1 to N_PASSED and to one energy-count bin.
+struct FinalizeShellsArgs {
+  int32_t n_shells, n_energies1, spectra, _pad;
+  double q_w, q_w2;
+};
+__global__ __launch_bounds__(256) void finalize_shells_kernel(const long long* in, double* out, FinalizeShellsArgs F, FixedCheck* C) {
+  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
+  uint32_t* const status = &C->status;
+  const int s = blockIdx.x;
+  const long long* const row = in + (size_t)s * SART_SHELL_ROW;
+  long long v[SART_SHELL_ROW];
+  for (int j = 0; j < SART_SHELL_ROW; ++j) v[j] = row[j];   // (every thread: read before the block's first write)
+  __shared__ long long cnt_sum, w_lo, w_hi;
+  if (threadIdx.x == 0) { cnt_sum = 0; w_lo = 0; w_hi = 0; }
+  __syncthreads();
+  if (F.spectra) {
+    const size_t ne = (size_t)F.n_energies1;
+    const size_t c0 = (size_t)F.n_shells * SART_SHELL_ROW + (size_t)s * ne, w0 = c0 + (size_t)F.n_shells * ne;
+    long long c = 0, lo = 0, hi = 0;
+    for (size_t e = threadIdx.x; e < ne; e += 256) {
+      const long long n = in[c0 + e], w = in[w0 + e];
+      fixed_status_check_slot(n, status);
+      fixed_status_check_slot(w, status);
+      c += n;
+      lo += w & kMask;
+      hi += w >> kFixedLimbBits;
+      out[c0 + e] = (double)n;
+      out[w0 + e] = (double)w * F.q_w;
+    }
+    c = wave_sum_i64(c); lo = wave_sum_i64(lo); hi = wave_sum_i64(hi);
+    if ((threadIdx.x & 63) == 0) {
+      atomicAdd(reinterpret_cast<unsigned long long*>(&cnt_sum), (unsigned long long)c);
+      atomicAdd(reinterpret_cast<unsigned long long*>(&w_lo), (unsigned long long)lo);
+      atomicAdd(reinterpret_cast<unsigned long long*>(&w_hi), (unsigned long long)hi);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  for (int j = 0; j < SART_SHELL_ROW; ++j) fixed_status_check_slot(v[j], status);
+  const double two40 = (double)(1ll << kFixedLimbBits);
+  const double sw = (double)v[SART_SHELL_SUM_WEIGHTS_HI] * two40 + (double)v[SART_SHELL_SUM_WEIGHTS];
+  const double sw2 = (double)v[SART_SHELL_SUM_WEIGHTS_SQ_HI] * two40 + (double)v[SART_SHELL_SUM_WEIGHTS_SQ];
+  const bool sq_ok = fixed_status_check_means(sw, sw2, (double)v[SART_SHELL_N_PASSED], status);
+  if (F.spectra) {
+    const long long hi = w_hi + (w_lo >> kFixedLimbBits), lo = w_lo & kMask;
+    const long long want_hi = v[SART_SHELL_SUM_WEIGHTS_HI] + (v[SART_SHELL_SUM_WEIGHTS] >> kFixedLimbBits);
+    const long long want_lo = v[SART_SHELL_SUM_WEIGHTS] & kMask;
+    if (cnt_sum != v[SART_SHELL_N_PASSED] || hi != want_hi || lo != want_lo) atomicOr(status, kFixedStatusNotConserved);
+  }
+  double* const o = out + (size_t)s * SART_SHELL_ROW;
+  for (int j = 0; j < SART_SHELL_ROW; ++j) o[j] = 0.0;
+  o[SART_SHELL_N_SELECTED] = (double)v[SART_SHELL_N_SELECTED];
+  o[SART_SHELL_N_HIT_NICKEL] = (double)v[SART_SHELL_N_HIT_NICKEL];
+  o[SART_SHELL_N_PASSED_TILL_WINDOW] = (double)v[SART_SHELL_N_PASSED_TILL_WINDOW];
+  o[SART_SHELL_N_PASSED] = (double)v[SART_SHELL_N_PASSED];
+  o[SART_SHELL_SUM_WEIGHTS] = sw * F.q_w;
+  o[SART_SHELL_SUM_WEIGHTS_SQ] = sq_ok ? sw2 * F.q_w2 : __builtin_nan("");
+}
+
 // Literal drop-in for traceAxionWrapper: one Axion record per ray, in ray order (no compaction).
 constexpr int kRecBlock = 256;
 // `uniforms` != nullptr (sart_internal_trace_records_uniforms, a test entry): ray i takes its six uniforms from
@@ -3726,6 +4205,46 @@ void launch_ascan_images(const HotA& H, const HotB& HB, const DevBlob* blob, con
     else
       hipLaunchKernelGGL(fold_scalars_kernel, dim3(1), dim3(256), 0, stream, scalars, part, n_blocks, (double)A.n_rays);
   }
+}
+
+// The per-shell histogram launch (generic variants: `rotated` = hist_variant_of 2): the kernel, then the folds of
+// launch_trace_histogram (scalars, replicas) and the fold of the shell table into the caller's block.
+int shell_histogram_blocks_per_cu(bool rotated) {
+  int n = 0;
+  const hipError_t e = rotated ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, shell_histogram_kernel<1024, true, false>, 1024, 0)
+                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, shell_histogram_kernel<1024, false, false>, 1024, 0);
+  return (e == hipSuccess && n > 0) ? n : 1;
+}
+void launch_shell_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, double* acc, const ShellArgs& SH,
+                            int n_blocks, hipStream_t stream, bool rotated, bool fixed) {
+  switch ((rotated ? 2 : 0) + (fixed ? 1 : 0)) {
+    case 0: hipLaunchKernelGGL((shell_histogram_kernel<1024, false, false>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, SH); break;
+    case 1: hipLaunchKernelGGL((shell_histogram_kernel<1024, false, true>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, SH); break;
+    case 2: hipLaunchKernelGGL((shell_histogram_kernel<1024, true, false>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, SH); break;
+    default: hipLaunchKernelGGL((shell_histogram_kernel<1024, true, true>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, SH); break;
+  }
+  const int n_img = A.image_nx * A.image_ny;
+  if (fixed) {
+    long long* const acc_i = reinterpret_cast<long long*>(acc);
+    hipLaunchKernelGGL(fold_scalars_fixed_kernel, dim3(1), dim3(256), 0, stream, acc_i + n_img,
+                       reinterpret_cast<const long long*>(A.partials), n_blocks, (long long)A.n_rays);
+    if (A.replica_mask != 0u)
+      hipLaunchKernelGGL(fold_replicas_kernel<long long>, dim3((n_img + 255) / 256), dim3(256), 0, stream, acc_i,
+                         reinterpret_cast<long long*>(A.replicas), n_img, (int)A.replica_mask + 1, A.replica_stride);
+    hipLaunchKernelGGL(fold_shells_kernel<true>, dim3(SH.n_shells), dim3(64), 0, stream, SH.block, SH.partials, n_blocks);
+    return;
+  }
+  hipLaunchKernelGGL(fold_scalars_kernel, dim3(1), dim3(256), 0, stream, acc + n_img, A.partials, n_blocks, (double)A.n_rays);
+  if (A.replica_mask != 0u)
+    hipLaunchKernelGGL(fold_replicas_kernel<double>, dim3((n_img + 255) / 256), dim3(256), 0, stream, acc, A.replicas, n_img,
+                       (int)A.replica_mask + 1, A.replica_stride);
+  hipLaunchKernelGGL(fold_shells_kernel<false>, dim3(SH.n_shells), dim3(64), 0, stream, SH.block, SH.partials, n_blocks);
+}
+void launch_finalize_shells(const void* in, double* out, int n_shells, int n_energies1, int spectra, double q_w, double q_w2,
+                            void* check_dev, hipStream_t stream) {
+  FinalizeShellsArgs F{n_shells, n_energies1, spectra, 0, q_w, q_w2};
+  hipLaunchKernelGGL(finalize_shells_kernel, dim3(n_shells), dim3(256), 0, stream, reinterpret_cast<const long long*>(in), out, F,
+                     static_cast<FixedCheck*>(check_dev));
 }
 
 size_t fixed_check_bytes() { return sizeof(FixedCheck); }

@@ -393,6 +393,50 @@ class RayTracer:
         """Asynchronous form: adds into a device accumulator (e.g. ``torch_tensor.data_ptr()``)."""
         _lib.check(self.lib.sart_trace_histogram_device(self.handle, C.byref(params), C.c_void_p(accumulator_ptr)))
 
+    # -- per-shell breakdown (include/sart.h "per-shell breakdown of the histogram trace") -----
+    def shell_block_len(self, spectra: bool = True) -> int:
+        """sart_shell_block_len for this context's setup and energy table."""
+        return int(self.lib.sart_shell_block_len(self.full.setup.n_shells, self.full.energies.size, 1 if spectra else 0))
+
+    def shells_params(self, n_rays: int, seed: int = 299792458, ray_id_offset: int = 0, flags: int | None = None, image_n: int = 256,
+                      spectra: bool = True, n_radial_bins: int = 10_000, radial_max: float = 10.0, accumulate: bool = False) -> TraceParams:
+        """The TraceParams of trace_shells (for the _device form)."""
+        p = self.trace_params(n_rays, seed, ray_id_offset, flags, image_n, accumulate)
+        if spectra:
+            p.spectra, p.n_radial_bins, p.radial_max = 1, n_radial_bins, radial_max
+        return p
+
+    def trace_shells(self, n_rays: int, seed: int = 299792458, ray_id_offset: int = 0, flags: int | None = None, image_n: int = 256,
+                     spectra: bool = True, n_radial_bins: int = 10_000, radial_max: float = 10.0):
+        """trace_histogram (trace_spectra with ``spectra``) plus the per-shell breakdown (sart_trace_histogram_shells).  Returns
+        (image, summary, spectra dict or None, shells dict of per-shell arrays keyed like _lib.SHELL, with ``spectra`` also
+        ``energy_counts`` / ``energy_weights`` [n_shells][n_energies + 1], and ``coating`` / ``R1``)."""
+        p = self.shells_params(n_rays, seed, ray_id_offset, flags, image_n, spectra, n_radial_bins, radial_max)
+        n_e1 = self.full.energies.size + 1
+        img = np.empty((image_n, image_n))
+        summ = Summary()
+        spec = np.empty(2 * n_radial_bins + 3 * n_e1) if spectra else None
+        block = np.empty(self.shell_block_len(spectra))
+        _lib.check(self.lib.sart_trace_histogram_shells(self.handle, C.byref(p), _lib.as_dp(img) if image_n else None, C.byref(summ),
+                                                        _lib.as_dp(spec) if spectra else None, _lib.as_dp(block)))
+        shells = split_shells(block, self.full.setup.n_shells, self.full.energies.size, spectra)
+        shells["coating"] = shell_coatings(self.full.setup)
+        shells["R1"] = np.array(self.full.setup.all_r1[:self.full.setup.n_shells])
+        return (img, {k: summ.v[i] for k, i in _lib.ACC.items()},
+                split_spectra(spec, n_radial_bins, n_e1, radial_max) if spectra else None, shells)
+
+    def trace_shells_device(self, params: TraceParams, accumulator_ptr: int, shells_ptr: int):
+        """Asynchronous form: adds into a device accumulator and a device block of shell_block_len(params.spectra) slots (raw int64 in
+        fixed64 mode)."""
+        _lib.check(self.lib.sart_trace_histogram_shells_device(self.handle, C.byref(params), C.c_void_p(accumulator_ptr),
+                                                               C.c_void_p(shells_ptr)))
+
+    def finalize_shells_device(self, params: TraceParams, raw_ptr: int, out_ptr: int | None = None):
+        """Raw FIXED64 shell block (device) -> doubles (device; in place by default).  Asynchronous; what the conversion finds
+        wrong is raised by the next ``synchronize()``."""
+        _lib.check(self.lib.sart_finalize_shells_device(self.handle, C.byref(params), C.c_void_p(raw_ptr),
+                                                        C.c_void_p(out_ptr if out_ptr is not None else raw_ptr)))
+
     # -- fused axion-mass scan (gas stage; include/sart.h "fused axion-mass scan") -------------
     def trace_mass_scan(self, masses_ev, n_rays: int, seed: int = 299792458, ray_id_offset: int = 0, flags: int | None = None):
         """Every ray of [ray_id_offset, ray_id_offset + n_rays) traced ONCE and weighed for every axion mass.  Returns
@@ -530,6 +574,57 @@ def split_spectra(spec: np.ndarray, n_radial_bins: int, n_e1: int, radial_max: f
     return out
 
 
+shell_block_len = _lib.shell_block_len
+split_shells = _lib.split_shells
+
+
+def shell_coatings(setup: Setup) -> np.ndarray:
+    """Coating index of every shell as the library assigns it: layers.lowerBound(shell) over coating_layers for a multi-coating
+    telescope (raytracer.nim:1573, the first boundary >= the shell index), coating 0 otherwise."""
+    n = setup.n_shells
+    if setup.reflectivity_kind != _lib.RK_MULTI_COATING:
+        return np.zeros(n, dtype=np.int64)
+    layers = np.array(setup.coating_layers[:setup.n_coatings])
+    return np.searchsorted(layers, np.arange(n), side="left").astype(np.int64)
+
+
+def write_shell_csvs(outpath: str, year: str, shells: dict, energies: np.ndarray, n_rays: float):
+    """`shell_breakdown_{year}.csv` (per shell: coating, R1, the counters, flux, its Monte-Carlo error and its fraction of the
+    total flux) and, with energy arrays in ``shells``, `energies_by_shell_{year}.csv` (the data of the reference's energies_by_shell
+    plot, raytracer.nim:2361-2376: rays and flux per shell and energy bin; the last bin is the X-ray test source's energy).  Returns
+    both paths (the second None without energy arrays)."""
+    import os
+    n = len(shells["N_PASSED"])
+    flux = shells["SUM_WEIGHTS"]
+    total = float(flux.sum())
+    p1 = os.path.join(outpath, "shell_breakdown_%s.csv" % year)
+    with open(p1, "w") as f:
+        f.write("shell,coating,R1 [mm],selected,hit nickel,passed till window,passed,flux,flux error,flux fraction\n")
+        for s in range(n):
+            f.write("%d,%d,%.17g,%d,%d,%d,%d,%.17g,%.17g,%.17g\n" % (
+                s, int(shells["coating"][s]), float(shells["R1"][s]), int(shells["N_SELECTED"][s]), int(shells["N_HIT_NICKEL"][s]),
+                int(shells["N_PASSED_TILL_WINDOW"][s]), int(shells["N_PASSED"][s]), float(flux[s]), float(np.sqrt(shells["SUM_WEIGHTS_SQ"][s])),
+                float(flux[s]) / total if total > 0 else 0.0))
+    p2 = None
+    if "energy_counts" in shells:
+        p2 = os.path.join(outpath, "energies_by_shell_%s.csv" % year)
+        e = np.append(np.asarray(energies, dtype=np.float64), np.nan)   # index n_energies: the X-ray test source's energy
+        with open(p2, "w") as f:
+            f.write("shell,energy index,energy [keV],rays,flux\n")
+            for s in range(n):
+                for k in np.nonzero(shells["energy_counts"][s])[0]:
+                    f.write("%d,%d,%.17g,%d,%.17g\n" % (s, k, e[k], int(shells["energy_counts"][s][k]), float(shells["energy_weights"][s][k])))
+    return p1, p2
+
+
+def read_shell_breakdown_csv(path: str) -> dict:
+    """The columns of a shell_breakdown_{year}.csv as arrays, keyed by the header."""
+    with open(path) as f:
+        header = f.readline().strip().split(",")
+    data = np.loadtxt(path, delimiter=",", skiprows=1, ndmin=2)
+    return {h: data[:, i] for i, h in enumerate(header)}
+
+
 def containment_radii(spectra: dict):
     """rSigma1, rSigma2 (unweighted) and rSigma1W, rSigma2W (weighted) of generateResultPlots (raytracer.nim:2459-2527)."""
     host = _lib.load_host()
@@ -606,9 +701,12 @@ def angle_image_names(year: str, angles) -> list:
 
 
 def calculateFluxFractions(tracer: RayTracer, n_rays: int = 1_000_000, seed: int = 299792458,
-                           ray_id_offset: int = 0):
+                           ray_id_offset: int = 0, shells: bool = False):
     """calculateFluxFractions (raytracer.nim:2755-2776) in histogram form: NumberOfPointsSun rays ->
-    256x256 focal-plane image (heatmaptable2, :2629) + counters (:2252-2257) + total flux (:885)."""
+    256x256 focal-plane image (heatmaptable2, :2629) + counters (:2252-2257) + total flux (:885).  ``shells``: the same trace
+    with the per-shell breakdown (RayTracer.trace_shells): (image, summary, spectra, shells)."""
+    if shells:
+        return tracer.trace_shells(n_rays, seed, ray_id_offset)
     return tracer.trace_histogram(n_rays, seed, ray_id_offset)
 
 
