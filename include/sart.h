@@ -698,7 +698,7 @@ int sart_finalize_energy_scan_device(sart_context* ctx, const sart_trace_params_
  * sart_reduce_across_devices with n_doubles = sart_shell_block_len(...), as int64 in FIXED64 - then finalize.
  * SART_ERR_INVALID_ARGUMENT, with the context unchanged: a NULL pointer, an invalid image or spectra specification.
  * Cost: trace_histogram's generic variants plus per selected ray one LDS atomic and per ray behind the mirrors up to five (folded
- * once per workgroup), two global atomics per passed ray with spectra; the LDS image tile is 53 x 53 instead of 56 x 56.
+ * once per workgroup), two global atomics per passed ray with spectra; the LDS image tile is 53 x 53 instead of 64 x 64.
  */
 enum { SART_SHELL_N_SELECTED = 0, SART_SHELL_N_HIT_NICKEL = 1, SART_SHELL_N_PASSED_TILL_WINDOW = 2, SART_SHELL_N_PASSED = 3,
        SART_SHELL_SUM_WEIGHTS = 4, SART_SHELL_SUM_WEIGHTS_SQ = 5, SART_SHELL_SUM_WEIGHTS_HI = 6, SART_SHELL_SUM_WEIGHTS_SQ_HI = 7,

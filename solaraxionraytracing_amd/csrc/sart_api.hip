@@ -188,6 +188,7 @@ struct sart_context {
     bool force_generic = false;      // SART_FORCE_GENERIC: never use the specialised kernel variant
     int image_replicas = 0;          // SART_IMAGE_REPLICAS: 0 = chosen from the plate scale
     int hist_blocks_per_cu = 0;      // SART_HIST_BLOCKS_PER_CU: 0 = occupancy query
+    int image_tile_max = 0;          // SART_IMAGE_TILE_MAX: upper bound of the LDS image tile's width (0 = what LDS holds); results do not depend on it
   } knobs;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
@@ -1051,6 +1052,7 @@ int sart_create(int device_ordinal, sart_context** out) {
     c->knobs.force_generic = flag("SART_FORCE_GENERIC");
     c->knobs.image_replicas = number("SART_IMAGE_REPLICAS");
     c->knobs.hist_blocks_per_cu = number("SART_HIST_BLOCKS_PER_CU");
+    c->knobs.image_tile_max = number("SART_IMAGE_TILE_MAX");
   }
   *out = c;
   return 0;
@@ -1746,8 +1748,8 @@ int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_
       a.replicas = reps.p;
       a.replica_mask = static_cast<uint32_t>(R - 1);
       // No stage A0 (its ring space in LDS is free) or the constant-path variant (the path column of ring 1 is free):
-      // accumulate the centre of the spot in a per-workgroup LDS tile (56 x 56: CAST / LLNL 82 % of the hits, BabyIAXO / XMM 34 %;
-      // 33 x 33 behind the tables alone for the variants whose rings are all in use: stage A0 on and the path carried).
+      // accumulate the centre of the spot in a per-workgroup LDS tile (64 x 64: CAST / LLNL 89 % of the hits, BabyIAXO / XMM 39 %;
+      // 45 x 45 behind the tables alone for the variants whose rings are all in use: stage A0 on and the path carried).
       // The tile is centred on the spot's centroid, measured once per setup and image binning by a pilot launch of 2e5 rays
       // into a one-pixel image (only SUM_X / SUM_Y / N_PASSED are read).
       const bool ring_cells_free = c->hot.n_zones == 0 || variant == 5 || variant == 6;
@@ -1781,7 +1783,8 @@ int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_
           if (sc[SART_ACC_N_PASSED] >= 100.0) {
             const double cx = (sc[SART_ACC_SUM_X] / sc[SART_ACC_N_PASSED] - p->image_x_min) * a.image_inv_step_x;
             const double cy = (sc[SART_ACC_SUM_Y] / sc[SART_ACC_N_PASSED] - p->image_y_min) * a.image_inv_step_y;
-            const int n = std::min({static_cast<int>(ring_cells_free ? kImageTileMax : kImageTileExtraMax), p->image_nx, p->image_ny});
+            int n = std::min({static_cast<int>(ring_cells_free ? kImageTileMax : kImageTileExtraMax), p->image_nx, p->image_ny});
+            if (c->knobs.image_tile_max > 0) n = std::min(n, c->knobs.image_tile_max);
             const int x0 = std::clamp(static_cast<int>(std::floor(cx)) - n / 2, 0, p->image_nx - n);
             const int y0 = std::clamp(static_cast<int>(std::floor(cy)) - n / 2, 0, p->image_ny - n);
             t.x0 = x0; t.y0 = y0; t.n = n;

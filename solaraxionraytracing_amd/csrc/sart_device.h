@@ -315,12 +315,16 @@ static_assert(sizeof(EScanEnergy) == 80 && sizeof(EScanArgs) == 32 + 80 * kEScan
 constexpr double kFixedPositionScale = 4294967296.0;        // 2^32 per mm
 constexpr double kFixedReflectScale = 1099511627776.0;      // 2^40
 constexpr int kFixedLimbBits = 40;                          // two-limb sums: value = hi * 2^40 + lo
-// LDS image tile: 16 waves x 128 doubles of ring space (ring 0, or ring 1's path column) + kTileExtraCells doubles behind the tables
-// (what the radius CDF leaves free in LDS as 32-bit words, and the end of the 160 KB): 56 x 56 <= 2048 + 1090 cells
+// LDS image tile of the histogram kernels: 16 waves x 128 doubles of ring space (ring 0, or ring 1's path column) + kTileExtraCells
+// doubles behind the tables: what the radius CDF leaves free in LDS as 32-bit words and the end of the 160 KB (kRingExtraCells, all
+// that the kernels whose rings are WaveRings have there), and 512 bytes per wave that ring 1 of the histogram kernels does not need
+// (HistRings: the energy draw's uniform travels as its 32-bit word): 64 x 64 <= 2048 + 2114 cells
 constexpr int kTileRingCells = 2048;
-constexpr int kTileExtraCells = 1090;
-constexpr int kImageTileMax = 56;
-constexpr int kImageTileExtraMax = 33;   // 33 x 33 <= kTileExtraCells: the tile of the variants whose rings are all in use
+constexpr int kRingExtraCells = 1090;
+constexpr int kTileExtraCells = 2114;
+static_assert(kTileExtraCells == kRingExtraCells + 16 * 512 / 8, "16 waves x 512 bytes");
+constexpr int kImageTileMax = 64;
+constexpr int kImageTileExtraMax = 45;   // 45 x 45 <= kTileExtraCells: the tile of the variants whose rings are all in use
 
 // Per-shell breakdown of the histogram trace (include/sart.h: sart_trace_histogram_shells_device).  shell_histogram_kernel keeps,
 // per workgroup and shell, four u32 counters and two sums in LDS - in the last kShellTableCells cells behind the tables, where the
@@ -328,8 +332,8 @@ constexpr int kImageTileExtraMax = 33;   // 33 x 33 <= kTileExtraCells: the tile
 // - and stores them once to partials[n_blocks][kMaxShells][kShellPartialSlots]; fold_shells_kernel adds those to the caller's block.
 constexpr int kShellPartialSlots = 6;   // N_SELECTED, N_HIT_NICKEL, N_PASSED_TILL_WINDOW, N_PASSED, sum of w, sum of w^2
 constexpr int kShellTableCells = kMaxShells * 4 / 2 + kMaxShells * 2;   // the u32 counters and the 8-byte sums, in 8-byte cells
-constexpr int kShellImageTileMax = 53;        // 53 x 53 <= kTileRingCells + kTileExtraCells - kShellTableCells
-constexpr int kShellImageTileExtraMax = 28;   // 28 x 28 <= kTileExtraCells - kShellTableCells
+constexpr int kShellImageTileMax = 53;        // 53 x 53 <= kTileRingCells + kRingExtraCells - kShellTableCells
+constexpr int kShellImageTileExtraMax = 28;   // 28 x 28 <= kRingExtraCells - kShellTableCells
 struct ShellArgs {
   double* block;          // the caller's block: rows of SART_SHELL_ROW slots, then (spectra) the per-shell energy counts and weights
   double* partials;       // [n_blocks][kMaxShells][kShellPartialSlots] per-workgroup counters and sums (plain stores)

@@ -430,6 +430,7 @@ struct RayState {
   double tsx, tsy;   // slopes dX/dz, dY/dz in the telescope frame
   double path_cb;    // path length inside the magnetic field
   double u5;         // uniform of the energy draw
+  uint32_t u5_hi;    // its random word: u5 = u5_hi / 2^32 = u52(u5_hi, 0) when the uniforms come from the ray's Philox block
   double zcb;        // z of pointExitCB in the telescope frame (z0 of :2051)
   int r_idx;         // sampled solar radius index (row of diffFluxCDFs)
   int shell;         // hit layer
@@ -585,6 +586,7 @@ __device__ __forceinline__ double spoke_measure(int n, double c) {
 struct Uniforms {
   double u0, u1, u2, u3, u4, u5;
   uint32_t u2_hi;   // floor(u2 2^32): the radius draw's guide bucket, and what it compares with the 32-bit copy of the CDF in LDS
+  uint32_t u5_hi = 0u;   // uniforms_of: the word behind u5 (u5 = u52(u5_hi, 0)); unused for uniforms handed in from outside
 };
 // u2_hi of a uniform that does not come with its random words (the test entry of the record kernel)
 __device__ __forceinline__ uint32_t upper32_of_uniform(double u) {
@@ -621,6 +623,7 @@ __device__ __forceinline__ void phase_a_bore(const HotA& H, const DevParams& P, 
   const bool cfg_test = FAST ? false : (H.test_active != 0);
   const double u0 = U.u0, u1 = U.u1, u2 = U.u2, u3 = U.u3, u4 = U.u4;
   st.u5 = U.u5;
+  st.u5_hi = U.u5_hi;
   st.r_idx = 0;
 
   bool ok = true;
@@ -917,6 +920,7 @@ __device__ __forceinline__ Uniforms uniforms_of(uint32_t seed_lo, uint32_t seed_
   U.u2 = u52(b0.x, 0u);
   U.u2_hi = b0.x;   // floor(u2 2^32) is the word itself
   U.u5 = u52(b0.z, 0u);
+  U.u5_hi = b0.z;
   U.u0 = u52(b0.y & 0xFFFFF800u, 0u);
   U.u1 = u52(b0.w & 0xFFFFF800u, 0u);
   U.u4 = u52((b0.y << 21) | ((b0.w & 0x7FFu) << 10), 0u);
@@ -965,6 +969,11 @@ struct RayOut {
 // ESCAN (fused energy scan, X-ray test source): phase B stops once the geometry is known - mirrors, reflection-angle cells,
 // detector plane, chip and strips - and hands what the weight needs of the ray to the caller in *geo (EScanGeo); no energy row,
 // no reflectivity gather, no weight.  out.m_nickel is set as usual.
+// 1: phase B of the accumulating kernels gathers the energy row and the reflectivities for live lanes only (0: for every lane;
+// experiment builds)
+#ifndef SART_GATHER_LIVE
+#define SART_GATHER_LIVE 1
+#endif
 struct EScanGeo {
   double cos_ya, path_cb, distance_pipe_m, xu1, xu2;
   int ia1, ia2;
@@ -1092,13 +1101,22 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
   const int e_idx = draw_energy ? energy_draw_finish(HB, ed) : e_idx_in;
 #endif
   SART_B_STAMP(3, e_idx);
-  const EnergyDev en = ESCAN ? EnergyDev{} : load_energy_row(HB, e_idx);
+  // Accumulating kernels: only the lanes whose ray is still alive behind both mirrors (nickel, no-hit tests: `live` is settled
+  // here; lanes beyond the pass' valid rays included) request them - the others would fetch three cache lines for values that
+  // live_m discards below.  Their row reads as zero and their reflectivities as (1, 1).  ONE predicated region; every ballot of
+  // this function stays outside it (a ballot in there would see the live lanes only).  Record mode gathers for every lane.
+  EnergyDev en = {};
   d2 g1 = {1.0, 1.0}, g2 = {1.0, 1.0};
-  if (!ESCAN && use_refl) {
-    // row (coating, e_idx) of refl[][n_angles]: 32-bit element offset (the table is < 4 GB, checked on the host)
-    const uint32_t row = __umul24((uint32_t)(sh.refl_row0 + e_idx), (uint32_t)HB.refl_n_angles);
-    g1 = gload<d2>(HB.refl, (row + (uint32_t)ia1) * 8u);   // g[i], g[i + 1] (8-byte aligned pair)
-    g2 = gload<d2>(HB.refl, (row + (uint32_t)ia2) * 8u);
+  const bool gather = (RECORDS || !SART_GATHER_LIVE) ? true : __builtin_amdgcn_inverse_ballot_w64(live_m);
+  if (!ESCAN && gather) {
+    asm volatile("; hot: gathers of the live lanes");
+    en = load_energy_row(HB, e_idx);
+    if (use_refl) {
+      // row (coating, e_idx) of refl[][n_angles]: 32-bit element offset (the table is < 4 GB, checked on the host)
+      const uint32_t row = __umul24((uint32_t)(sh.refl_row0 + e_idx), (uint32_t)HB.refl_n_angles);
+      g1 = gload<d2>(HB.refl, (row + (uint32_t)ia1) * 8u);   // g[i], g[i + 1] (8-byte aligned pair)
+      g2 = gload<d2>(HB.refl, (row + (uint32_t)ia2) * 8u);
+    }
   }
 
   // ---- detector plane: getPointDetectorWindow (:797-814, :2070-2083) ----
@@ -1287,9 +1305,23 @@ struct __align__(16) WaveRings {
   uint32_t ray[kQueue];                   // ring 0: rays that passed stage A0 (ray id relative to the launch's first chunk)
   uint32_t u3hi[kQueue];                  //         and their word of the shared stream (high word of u3)
 };
-template <int WAVES>
+// The rings of trace_histogram_kernel: ring 1 carries the energy draw's uniform as the 32-bit word it is made of (u5 = z / 2^32
+// exactly, uniforms_of) in one 8-byte cell beside the packed indices - one LDS store and one LDS load per entry instead of two, and
+// 512 bytes per wave less than WaveRings, which the image tile gets (sart_device.h: kTileExtraCells).  The other kernels keep
+// WaveRings: their u5 column holds a workgroup's scan cells.
+struct __align__(16) HistRings {
+  double X0[kQueue], Y0[kQueue], tsx[kQueue], tsy[kQueue];
+  double path[kQueue];
+  uint2 cell[kQueue];                     // {r_idx | shell << 16, z}
+  uint32_t ray[kQueue];                   // ring 0, as in WaveRings
+  uint32_t u3hi[kQueue];
+};
+static_assert(sizeof(WaveRings) - sizeof(HistRings) == kQueue * sizeof(uint32_t) && sizeof(HistRings) % 512 == 0 &&
+                  (kTileRingCells / kQueue * (sizeof(WaveRings) - sizeof(HistRings))) / sizeof(double) == kTileExtraCells - kRingExtraCells,
+              "what ring 1's packed cell frees is what the histogram kernels' image tile grows by");
+template <int WAVES, typename Rings = WaveRings>
 struct __align__(16) QueueLds {
-  WaveRings w[WAVES];
+  Rings w[WAVES];
 };
 
 template <int BLOCK>
@@ -1342,7 +1374,8 @@ struct ZoneTable {
   uint32_t lo[kMaxZones], hi[kMaxZones];
 };
 static_assert(sizeof(ZoneTable) == sizeof(HotA) - offsetof(HotA, n_zones), "ZoneTable mirrors the tail of HotA");
-static_assert(offsetof(WaveRings, u3hi) == offsetof(WaveRings, ray) + kQueue * sizeof(uint32_t) && offsetof(WaveRings, ray) % 8 == 0,
+static_assert(offsetof(WaveRings, u3hi) == offsetof(WaveRings, ray) + kQueue * sizeof(uint32_t) && offsetof(WaveRings, ray) % 8 == 0 &&
+                  offsetof(HistRings, u3hi) == offsetof(HistRings, ray) + kQueue * sizeof(uint32_t) && offsetof(HistRings, ray) % 8 == 0,
               "the image tile uses ray + u3hi of every wave as 128 contiguous doubles");
 __device__ __forceinline__ void reload_zones(ZoneTable& dst) {
   typedef const __attribute__((address_space(4))) uint32_t* kernarg_ptr;
@@ -1407,17 +1440,17 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
     double tile_extra[kTileExtraCells];   // cells kTileRingCells .. of the image tile
     DevBlob B;
     TraceArgs Ab;
-    QueueLds<BLOCK / 64> Q;
+    QueueLds<BLOCK / 64, HistRings> Q;
   };
   __shared__ LdsLayout lds;
   TablesLds& S = lds.S;
-  QueueLds<BLOCK / 64>& Q = lds.Q;
+  QueueLds<BLOCK / 64, HistRings>& Q = lds.Q;
   static_assert(!PATHC || (FAST && !ROT && GAS >= 0), "the constant-path form belongs to the unrotated specialisations");
   static_assert(!SCAN || GAS != 0, "a mass scan needs the gas stage");
   static_assert(!SCAN || kScanMaxMasses * 2 * kScanLanes <= (BLOCK / 64) * kQueue, "the scan accumulators live in the image tile's 128 doubles per wave");
   __shared__ uint32_t scan_zero[kScanMaxMasses];   // SCAN: rays whose weight vanishes for one mass only (conversion probability exactly 0)
   static_assert((BLOCK / 64) * kQueue == kTileRingCells && kImageTileMax * kImageTileMax <= kTileRingCells + kTileExtraCells &&
-                    kImageTileExtraMax * kImageTileExtraMax <= kTileExtraCells,
+                    kImageTileExtraMax * kImageTileExtraMax <= kTileExtraCells && BLOCK / 64 == kTileRingCells / kQueue,
                 "the LDS image tile (host: kImageTileMax): 128 doubles per wave of this workgroup's rings + the cells behind the tables");
   static_assert((offsetof(LdsLayout, Q) % 512) == 0, "the rings are addressed with ds_*2st64 offsets (units of 512 bytes for 64-bit columns)");
   // cell t < kTileRingCells of the tile space: 128 doubles per wave, in the space of ring 0 (stage A0 off) or of ring 1's path
@@ -1525,8 +1558,7 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
       Q.w[wave].X0[slot] = st.X0; Q.w[wave].Y0[slot] = st.Y0;
       Q.w[wave].tsx[slot] = st.tsx; Q.w[wave].tsy[slot] = st.tsy;
       if (!PATHC) Q.w[wave].path[slot] = st.path_cb;
-      Q.w[wave].u5[slot] = st.u5;
-      Q.w[wave].idx[slot] = st.r_idx | (st.shell << 16);
+      Q.w[wave].cell[slot] = make_uint2((uint32_t)(st.r_idx | (st.shell << 16)), st.u5_hi);
     }
     t1 += cnt;
     __builtin_amdgcn_s_setprio(0);
@@ -1545,7 +1577,8 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
       st.X0 = Q.w[wave].X0[slot]; st.Y0 = Q.w[wave].Y0[slot];
       st.tsx = Q.w[wave].tsx[slot]; st.tsy = Q.w[wave].tsy[slot];
       st.path_cb = PATHC ? H.length_b : Q.w[wave].path[slot];   // PATHC: z extent of the path = lengthB for every ray
-      st.u5 = Q.w[wave].u5[slot];
+      const uint2 cell = Q.w[wave].cell[slot];
+      st.u5 = u52(cell.y, 0u);   // the same bits phase A would have carried as a double
       if (!ROT) {
         st.zcb = -(H.dz3 - H.dz1);
       } else {
@@ -1553,7 +1586,7 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
         st.zcb = zcb_rotated(Pb.rx_s, -Pb.rx_c * Pb.ry_s, Pb.rx_c * Pb.ry_c, Pb.half_length_telescope, st.X0 + Pb.entrance_x,
                              st.Y0 + Pb.entrance_y, st.tsx, st.tsy, H.dz3 - H.dz1);
       }
-      const int packed = Q.w[wave].idx[slot];
+      const int packed = (int)cell.x;
       st.r_idx = packed & 0xFFFF;
       st.shell = packed >> 16;
       const DevBlob& Bo = lds_opaque(B);
@@ -1862,8 +1895,8 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
   // (FIXED: the slots hold int64 - sums in quanta, counters as integers - and are added as integers all the way)
   // (the staging area is the head of wave 0's rings - X0, Y0, tsx: dead once every wave has left the loop, and apart from the
   // image tile / the scan accumulators, which live in the path or the ring-0 columns)
-  static_assert(sizeof(Sum) * (BLOCK / 64) * SART_ACC_COUNT <= 3 * kQueue * sizeof(double) && offsetof(WaveRings, Y0) == kQueue * sizeof(double) &&
-                    offsetof(WaveRings, tsx) == 2 * kQueue * sizeof(double), "the scalar staging area fits the first three ring columns of wave 0");
+  static_assert(sizeof(Sum) * (BLOCK / 64) * SART_ACC_COUNT <= 3 * kQueue * sizeof(double) && offsetof(HistRings, Y0) == kQueue * sizeof(double) &&
+                    offsetof(HistRings, tsx) == 2 * kQueue * sizeof(double), "the scalar staging area fits the first three ring columns of wave 0");
   __syncthreads();
   Sum (*const red)[SART_ACC_COUNT] = reinterpret_cast<Sum (*)[SART_ACC_COUNT]>(&Q.w[0].X0[0]);
   Sum sw, sw2, sxx, syy, srr;
@@ -1926,8 +1959,8 @@ struct ShellKernArgs {
 static_assert(offsetof(ShellKernArgs, A) == offsetof(HistKernArgs, A) && offsetof(ShellKernArgs, HB) == offsetof(HistKernArgs, HB) &&
                   offsetof(ShellKernArgs, SH) == offsetof(HistKernArgs, SC),
               "the shell kernel shares the argument offsets of the histogram kernel");
-static_assert(kShellImageTileMax * kShellImageTileMax <= kTileRingCells + kTileExtraCells - kShellTableCells &&
-                  kShellImageTileExtraMax * kShellImageTileExtraMax <= kTileExtraCells - kShellTableCells,
+static_assert(kShellImageTileMax * kShellImageTileMax <= kTileRingCells + kRingExtraCells - kShellTableCells &&
+                  kShellImageTileExtraMax * kShellImageTileExtraMax <= kRingExtraCells - kShellTableCells,
               "the shell kernel's image tile leaves the shell table alone");
 
 template <int BLOCK, bool ROT, bool FIXED>
@@ -1936,7 +1969,7 @@ __global__ __launch_bounds__(BLOCK) void shell_histogram_kernel(HotA H, const De
   using Sum = std::conditional_t<FIXED, long long, double>;   // per-lane sums: quanta (FIXED) or f64
   struct LdsLayout {
     TablesLds S;
-    double tile_extra[kTileExtraCells - kShellTableCells];   // cells kTileRingCells .. of the image tile
+    double tile_extra[kRingExtraCells - kShellTableCells];   // cells kTileRingCells .. of the image tile
     uint32_t shell_cnt[kMaxShells][4];                       // per shell: N_SELECTED, N_HIT_NICKEL, N_PASSED_TILL_WINDOW, N_PASSED
     Sum shell_sum[kMaxShells][2];                            // per shell: sum of w, sum of w^2
     DevBlob B;
@@ -1968,7 +2001,7 @@ __global__ __launch_bounds__(BLOCK) void shell_histogram_kernel(HotA H, const De
   {
     uint64_t* q = reinterpret_cast<uint64_t*>(&Q);
     for (int i = threadIdx.x; i < (int)(sizeof(Q) / 8); i += BLOCK) q[i] = 0ull;
-    for (int i = threadIdx.x; i < kTileExtraCells - kShellTableCells; i += BLOCK) lds.tile_extra[i] = 0.0;
+    for (int i = threadIdx.x; i < kRingExtraCells - kShellTableCells; i += BLOCK) lds.tile_extra[i] = 0.0;
     for (int i = threadIdx.x; i < kMaxShells * 4; i += BLOCK) lds.shell_cnt[i >> 2][i & 3] = 0u;
     for (int i = threadIdx.x; i < kMaxShells * 2; i += BLOCK) lds.shell_sum[i >> 1][i & 1] = 0;
   }
@@ -2119,7 +2152,7 @@ __global__ __launch_bounds__(BLOCK) void shell_histogram_kernel(HotA H, const De
         const uint32_t tn = (uint32_t)Al.tile_n;
         const uint32_t tx = ix - (uint32_t)Al.tile_x0, ty = iy - (uint32_t)Al.tile_y0;
         if ((tx < tn) & (ty < tn)) {
-          const uint32_t t = ty * tn + tx + (uint32_t)Al.tile_base;   // < kTileRingCells + kTileExtraCells - kShellTableCells (host)
+          const uint32_t t = ty * tn + tx + (uint32_t)Al.tile_base;   // < kTileRingCells + kRingExtraCells - kShellTableCells (host)
           if constexpr (FIXED)
             __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(tile_cell(t)), (unsigned long long)w_fx, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2600,7 +2633,7 @@ static_assert(offsetof(AScanKernArgs, A) == offsetof(HistKernArgs, A) && offseto
 constexpr int kAScanCells = kAScanMaxAngles * 2 * kScanLanes;          // [angle][sum w, sum w^2][kScanLanes]: ring 1's u5 column, 128 doubles per wave
 constexpr int kAScanMTable = 0;                                        // [angle][mx, my, mz] in the cells behind the tables (the histogram kernels' tile_extra)
 constexpr int kAScanCounters = 3 * kAScanMaxAngles;                    // behind it: (4 kAScanMaxAngles + 4) u32
-static_assert(kAScanMTable + 3 * kAScanMaxAngles + (4 * kAScanMaxAngles + 4 + 1) / 2 <= kTileExtraCells, "rotation columns + counters live where the histogram kernels keep the image tile behind the tables");
+static_assert(kAScanMTable + 3 * kAScanMaxAngles + (4 * kAScanMaxAngles + 4 + 1) / 2 <= kRingExtraCells, "rotation columns + counters live where the histogram kernels keep the image tile behind the tables");
 static_assert(2 * kScanLanes == 64, "one cell per lane in the epilogue");
 // ascan_images_kernel only, behind the counters in the same cells: [angle][SUM_X, SUM_Y, SUM_R][kAImgLanes] f64 / int64 (lanes l, l + 8,
 // ... share a cell), [angle] SUM_WEIGHTS_OUTSIDE (FIXED), [angle] N_OUTSIDE_IMAGE (u32)
@@ -2609,7 +2642,7 @@ constexpr int kAImgPos = kAScanCounters + (4 * kAScanMaxAngles + 4 + 1) / 2;
 constexpr int kAImgOutside = kAImgPos + 3 * kAImgLanes * kAScanMaxAngles;
 constexpr int kAImgNOutside = kAImgOutside + kAScanMaxAngles;
 constexpr int kAImgCellsEnd = kAImgNOutside + kAScanMaxAngles / 2;
-static_assert(kAImgCellsEnd <= kTileExtraCells && kAImgCellsEnd - kAImgPos <= 1024, "the image scan's sums fit the cells behind the tables");
+static_assert(kAImgCellsEnd <= kRingExtraCells && kAImgCellsEnd - kAImgPos <= 1024, "the image scan's sums fit the cells behind the tables");
 static_assert(3 * kAImgLanes == 24, "one cell per lane of lanes 0 .. 23 in the epilogue");
 
 template <int BLOCK, bool FAST, int GAS, bool FIXED>
@@ -2617,7 +2650,7 @@ __global__ __launch_bounds__(BLOCK) void trace_angular_scan_kernel(HotA H, const
                                                                    double* __restrict__ unused, HotB HBarg, AScanArgs ANarg) {
   struct LdsLayout {   // the layout of trace_histogram_kernel (tables first: ds_ offsets)
     TablesLds S;
-    double cells[kTileExtraCells];
+    double cells[kRingExtraCells];
     DevBlob B;
     TraceArgs Ab;
     QueueLds<BLOCK / 64> Q;
@@ -2913,7 +2946,7 @@ __global__ __launch_bounds__(BLOCK) void ascan_images_kernel(HotA H, const DevBl
                                                              double* __restrict__ img_partials, HotB HBarg, AScanArgs ANarg) {
   struct LdsLayout {   // the layout of trace_histogram_kernel (tables first: ds_ offsets)
     TablesLds S;
-    double cells[kTileExtraCells];
+    double cells[kRingExtraCells];
     DevBlob B;
     TraceArgs Ab;
     QueueLds<BLOCK / 64> Q;

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
 """A/B timing of kernel builds: python tools/exp_ab.py lib1.so lib2.so ...  (each in its own subprocess, alternating).
+An entry may carry environment knobs of the library: lib.so,SART_IMAGE_TILE_MAX=56 (read when a context is created).
 Environment: SART_AB_RAYS (rays per launch, default 1e8), SART_AB_REPS (timed launches, default 5), SART_AB_ROUNDS (times the
 list of libraries is gone through, default 1), SART_AB_WORKLOADS (comma list of BabyIAXO,CAST,gas,rot; default the first three)."""
 import sys, os, subprocess
@@ -33,9 +34,11 @@ if "rot" in WL:
     run("rot", full, L.CF_IGNORE_DET_WINDOW | L.CF_IGNORE_GAS_ABS | L.CF_IGNORE_CONV_PROB)
 ''' % ROOT
 for rep in range(int(os.environ.get("SART_AB_ROUNDS", "1"))):
-    for lib in sys.argv[1:]:
+    for entry in sys.argv[1:]:
+        lib, *knobs = entry.split(",")
         env = dict(os.environ)
+        env.update(k.split("=", 1) for k in knobs)
         if lib != "default":
             env["SART_LIBSART"] = os.path.abspath(lib)
-        print(lib, flush=True)
+        print(entry, flush=True)
         subprocess.run([sys.executable, "-c", CHILD], env=env, check=True)
