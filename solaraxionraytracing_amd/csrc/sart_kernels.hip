@@ -96,12 +96,21 @@ __device__ __forceinline__ double scalar_const() {
 // One Horner step p x + C with the coefficient C as a scalar operand: v_fma_f64 v, v, v, s.  Left to itself LLVM selects the
 // two-address v_fmac_f64 for a single-use addend and copies the constant into the destination first (two v_mov_b32 per
 // step, also when the constant already sits in scalar registers).
+// HORNER hands the coefficient to the "s" operand as a plain constant: the COMPILER then writes the two s_mov_b32, as
+// instructions it knows.  (They used to come from scalar_const's own asm statement.  The hazard recogniser treats every
+// register an asm statement defines as if a forwarding-hazard instruction had written it, and counts the asm statements
+// between that definition and its first vector reader as zero wait states: each step carried an s_nop between the moves and
+// the FMA, four issue slots for one FMA.  A compiler-written s_mov_b32 needs none - the hardware interlocks a scalar write
+// against a vector read - and it counts as the wait state between the FMAs of two steps.)  Constants are materialised per basic
+// block at instruction selection, and MachineLICM is off for this file (Makefile): nothing hoists them out of the persistent
+// loop, and within a block equal coefficients are merged - two chains of one polynomial written step by step side by side
+// (asin_small_pair, spoke_measure_pair) share one pair of moves per coefficient.
 __device__ __forceinline__ double fma_vvs(double p, double x, double c_scalar) {
   double r;
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(p), "v"(x), "s"(c_scalar));
   return r;
 }
-#define HORNER(p, x, c) fma_vvs((p), (x), SC(c))
+#define HORNER(p, x, c) fma_vvs((p), (x), (double)(c))
 
 // Uniform in [0, 1) from two words (hi word first): 52 random mantissa bits under the exponent of 1.0,
 // minus 1.0 — the construction of Nim's std/random rand(1.0) (and of the oracle).
@@ -158,6 +167,31 @@ __device__ __forceinline__ double asin_small(double x, double x2) {   // x2 = x^
     r = asin(x);
   }
   return r;
+}
+
+// asin_small of two values at once (the two mirrors of phase B): both series step by step side by side in ONE basic block, so
+// each coefficient is written to scalar registers once and read by two FMAs back to back.  Every chain does asin_small's
+// operations in asin_small's order - the same bits; the library fall-backs stay per value, behind both series.
+__device__ __forceinline__ void asin_small_pair(double xa, double xa2, double xb, double xb2, double& ra, double& rb) {
+  double pa = 0.01396484375, pb = 0.01396484375;   // 143/10240
+#define SART_STEP2(c) pa = HORNER(pa, xa2, c); pb = HORNER(pb, xb2, c)
+  SART_STEP2(0.017352764423076924);                // 231/13312
+  SART_STEP2(0.022372159090909092);                // 63/2816
+  SART_STEP2(0.030381944444444444);                // 35/1152
+  SART_STEP2(0.044642857142857144);                // 5/112
+  SART_STEP2(0.075);                               // 3/40
+  SART_STEP2(0.16666666666666666);                 // 1/6
+#undef SART_STEP2
+  ra = fma(xa * xa2, pa, xa);
+  rb = fma(xb * xb2, pb, xb);
+  if (!(fabs(xa) < 0.06)) {
+    asm volatile("; rare: asin outside the series' range");
+    ra = asin(xa);
+  }
+  if (!(fabs(xb) < 0.06)) {
+    asm volatile("; rare: asin outside the series' range");
+    rb = asin(xb);
+  }
 }
 
 // atan for ray slopes (|x| < 0.05): alternating series to x^15; library outside.
@@ -417,8 +451,8 @@ __device__ __forceinline__ double normal_z_general(const DevParams& P, const She
 // ------------------------------------------------------------------------------------------------
 struct LdsTables {
   const double* sincos;      // (cos, sin)(pi k / 64), k = 0 .. 128
-  const uint32_t* rcdf_hi;   // fluxRadiusCDF as the upper 32 of the 52 bits of floor(cdf 2^52), + 1 (stage_tables)
-  const double* rcdf_f64;    // the f64 table in device memory: decides the ties of the 32-bit compare (one draw in ~1e9)
+  const uint32_t* rcdf_hi;   // fluxRadiusCDF as the upper 32 of the 52 bits of floor(cdf 2^52), saturated (stage_tables)
+  const double* rcdf_f64;    // the f64 table in device memory: decides the ties of the general form's 32-bit compare (one draw in ~1e9)
   const uint16_t* rguide;    // guide table in front of it
   const ShellDev* shells;
   const uint8_t* lut;        // radial look-up table of the shell selection
@@ -483,10 +517,18 @@ struct EnergyDraw {
   uint32_t lo, hi;
   u4v c;               // cdf_hi32 of row[lo .. lo + 3]
 };
-__device__ __forceinline__ void energy_draw_begin(const HotB& HB, int r_idx, double u5, EnergyDraw& d, int r_idx_guide = -1) {
+// WORD (compile time): the uniform is a 32-bit random word over 2^32, u5 = word / 2^32 exactly (uniforms_of: every accumulating
+// kernel).  Then  cdf < u5  <=>  cdf 2^32 < word  <=>  floor(cdf 2^32) < word  for every real cdf (word is an integer), and the
+// saturated table entry 0xFFFFFFFF (cdf >= 1 - 2^-32) is never below a word: cdf_hi32 decides every candidate, there is no
+// undecided case and no tie path; the bucket and the uniform / log split are shifts and compares of the word.  The general form
+// (a uniform handed in from outside: the record kernel) makes no assumption about the bits of u5.
+template <bool WORD = false>
+__device__ __forceinline__ void energy_draw_begin(const HotB& HB, int r_idx, double u5, uint32_t word, EnergyDraw& d, int r_idx_guide = -1) {
   if (r_idx_guide < 0) r_idx_guide = r_idx;   // (experiment builds pass another row for the guide gather: working-set sensitivity)
   d.u = u5;
-  {
+  if (WORD) {
+    d.khi = word;
+  } else {
     // u5 = k 2^-52 exactly (u52: 52 random mantissa bits under the exponent of 1.0, minus 1.0): 1 + u5 carries k in its
     // mantissa, and its upper 32 bits are one funnel shift away.  (A uniform handed in from outside - the test entry - may
     // have bits below 2^-52: the sum then rounds k by at most 1/2, which energy_draw_finish allows for; the clamp keeps a
@@ -494,11 +536,14 @@ __device__ __forceinline__ void energy_draw_begin(const HotB& HB, int r_idx, dou
     const double w = fmin(u5 + 1.0, 1.9999999999999998);
     d.khi = __builtin_amdgcn_alignbit((uint32_t)__double2hiint(w), (uint32_t)__double2loint(w), 20u);
   }
+  static_assert((kEnergyGuideDiv & (kEnergyGuideDiv - 1)) == 0 && kEnergyGuideDiv >= 32, "the word form shifts by log2 of it");
   const double v = 1.0 - u5;
-  const uint32_t ku = (uint32_t)(int)(u5 * (double)kEnergyGuideDiv);
+  // floor(u5 Div): of the word, its upper log2(Div) bits
+  const uint32_t ku = WORD ? word >> (32 - __builtin_ctz((uint32_t)kEnergyGuideDiv)) : (uint32_t)(int)(u5 * (double)kEnergyGuideDiv);
   const uint32_t code = (uint32_t)__double2hiint(v) >> 14;                       // exponent and six mantissa bits of v
   const uint32_t kl = (uint32_t)kEnergyGuideUniform + min(kEnergyGuideCode0 - code, (uint32_t)kEnergyGuideLogMax);
-  const uint32_t k = (v > 0.03125) ? ku : kl;                                    // u5 < 31/32: uniform buckets
+  const bool uniform_bucket = WORD ? word < 0xF8000000u : v > 0.03125;           // u5 < 31/32: uniform buckets
+  const uint32_t k = uniform_bucket ? ku : kl;
   d.row = __umul24((uint32_t)r_idx, (uint32_t)HB.cdf_stride);                    // both < 2^24
   // two adjacent u16 as one (possibly unaligned) 32-bit load
   d.gword = gload<uint32_t>(HB.energy_guide, (__umul24((uint32_t)r_idx_guide, (uint32_t)kEnergyGuideEntries) + k) * 2u);
@@ -510,8 +555,23 @@ __device__ __forceinline__ void energy_draw_candidates(const HotB& HB, EnergyDra
   // 16-byte boundary, global_load_dwordx4 needs 4-byte alignment only
   d.c = gload<u4v>(HB.cdf_hi32, (d.row + d.lo) * 4u);
 }
+template <bool WORD = false>
 __device__ __forceinline__ int energy_draw_finish(const HotB& HB, const EnergyDraw& d) {
   const double u = d.u;
+  if (WORD) {
+    // lowerBound = lo + #{candidates < word}; only a bucket wider than four entries whose first four are all below goes on
+    const uint32_t z = d.khi;
+    uint32_t lo = d.lo + (uint32_t)(d.c.x < z) + (uint32_t)(d.c.y < z) + (uint32_t)(d.c.z < z) + (uint32_t)(d.c.w < z);
+    if ((d.c.w < z) & (d.hi > d.lo + 4u)) {
+      asm volatile("; rare: energy bucket wider than four entries");
+      uint32_t hi = d.hi;
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (gload<double>(HB.diff_flux_cdfs, (d.row + mid) * 8u) < u) lo = mid + 1; else hi = mid;
+      }
+    }
+    return (int)min(lo, (uint32_t)(HB.n_energies - 1));
+  }
   // With T = floor(cdf 2^52) >> 20 (the table) and K = the upper 32 bits of u 2^52 rounded to an integer k':  T < K - 1 =>
   // floor(cdf 2^52) <= k' - 2^20 - 1 => cdf < u;  T > K => cdf 2^52 >= k' + 1 => cdf >= u (u 2^52 lies within 1/2 of k').
   // T in {K - 1, K}: undecided (2^-31 per candidate) - the f64 row decides, as it does in a wide bucket whose first four
@@ -531,11 +591,12 @@ __device__ __forceinline__ int energy_draw_finish(const HotB& HB, const EnergyDr
   return (int)min(lo, (uint32_t)(HB.n_energies - 1));
 }
 // the three steps back to back (record mode)
-__device__ __forceinline__ int sample_energy_index(const HotB& HB, int r_idx, double u5) {
+template <bool WORD = false>
+__device__ __forceinline__ int sample_energy_index(const HotB& HB, int r_idx, double u5, uint32_t word = 0u) {
   EnergyDraw d;
-  energy_draw_begin(HB, r_idx, u5, d);
+  energy_draw_begin<WORD>(HB, r_idx, u5, word, d);
   energy_draw_candidates(HB, d);
-  return energy_draw_finish(HB, d);
+  return energy_draw_finish<WORD>(HB, d);
 }
 
 static_assert(sizeof(EnergyDev) == 8 * sizeof(double), "EnergyDev is loaded as eight f64");
@@ -563,6 +624,22 @@ __device__ __forceinline__ double spoke_measure(int n, double c) {
   }
   const double t3 = c * HORNER(4.0 * c, c, -3.0);
   return HORNER(2.0 * t3, t3, -1.0);
+}
+
+// spoke_measure of two cosines at once (entrance plane and spider plane): the two chains side by side, one pair of scalar
+// moves per addend; the same operations in the same order per chain - the same bits as spoke_measure.
+__device__ __forceinline__ void spoke_measure_pair(int n, double ca, double cb, double& ma, double& mb) {
+  if (n == 16) {
+    const double ua = HORNER(ca, ca, -0.5), ub = HORNER(cb, cb, -0.5);
+    const double va = HORNER(ua, ua, -0.125), vb = HORNER(ub, ub, -0.125);
+    const double wa = HORNER(va, va, -0.0078125), wb = HORNER(vb, vb, -0.0078125);
+    ma = HORNER(wa, wa, -1.0 / 32768.0);
+    mb = HORNER(wb, wb, -1.0 / 32768.0);
+    return;
+  }
+  const double ta = ca * HORNER(4.0 * ca, ca, -3.0), tb = cb * HORNER(4.0 * cb, cb, -3.0);
+  ma = HORNER(2.0 * ta, ta, -1.0);
+  mb = HORNER(2.0 * tb, tb, -1.0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -616,8 +693,49 @@ static_assert(offsetof(DevParams, rx_s) == offsetof(DevParams, rx_c) + 8 && offs
               "TelRot mirrors these five fields of DevParams");
 __device__ __forceinline__ const TelRot& tel_rot_of(const DevParams& P) { return *reinterpret_cast<const TelRot*>(&P.rx_c); }
 
+// The radius draw of phase_a_bore: lowerBound(fluxRadiusCDF, u2) from the staged tables (u2_hi = floor(u2 2^32)).
+template <bool WORD>
+__device__ __forceinline__ int radius_draw(const LdsTables& L, uint32_t u2_hi, double u2) {
+  // lowerBound(fluxRadiusCDF, u2) (:437).  K = floor(u2 2^32) picks the guide bucket (sart_device.h: 2048 buckets, and 1024
+  // finer ones for u2 >= 31/32) whose two entries bracket the index.  The table sits in LDS as T = floor(cdf 2^32), saturated
+  // (half the bytes of the f64 table: the other half is image tile; the 1.0 pads read 0xFFFFFFFF).
+  // WORD: u2 = K / 2^32 exactly, so cdf < u2 <=> T < K: the count of the entries below K IS the lowerBound, nothing is undecided.
+  // General form (u2 with bits below 2^-32), with T' = T + 1 saturated:  T' < K => cdf < u2;  T' > K + 1 => cdf > u2;
+  // T' in {K, K + 1}: undecided, 2^-31 per entry looked at - the f64 table in device memory decides.
+  const uint32_t khi = u2_hi;
+  const uint32_t kb = khi >> 21, kt = (khi >> 17) - ((kRadiusGuideTopStart >> 17) - (uint32_t)(kRadiusGuide + 1));
+  const uint32_t k = khi >= kRadiusGuideTopStart ? kt : kb;
+  const int lo0 = (int)L.rguide[k];
+  const int hi0 = (int)L.rguide[k + 1];
+  auto entry = [&](int i) {   // T (WORD) or T'
+    const uint32_t t = L.rcdf_hi[i];
+    return WORD ? t : t + (uint32_t)(t != 0xFFFFFFFFu);
+  };
+  // four consecutive candidates in ONE round trip to LDS: the table is sorted and rcdf[hi] >= u2, so entries at or beyond hi
+  // never count (the stage pads the table with four entries of 1.0)
+  const uint32_t c0 = entry(lo0), c1 = entry(lo0 + 1), c2 = entry(lo0 + 2), c3 = entry(lo0 + 3);
+  int lo = lo0 + (int)(c0 < khi) + (int)(c1 < khi) + (int)(c2 < khi) + (int)(c3 < khi);
+  // undecided: an entry in {K, K + 1}, i.e. the smallest of the four differences (unsigned: entries below K wrap to huge) < 2
+  bool tie = WORD ? false : min(min(c0 - khi, c1 - khi), min(c2 - khi, c3 - khi)) < 2u;
+  if ((c3 < khi) & (hi0 > lo0 + 4)) {
+    asm volatile("; rare: radius bucket wider than four entries");
+    int hi = hi0;
+    while (lo < hi) {   // first entry that is not (certainly) below u2
+      const int mid = (lo + hi) >> 1;
+      if (entry(mid) < khi) lo = mid + 1; else hi = mid;
+    }
+    if (!WORD) tie = (entry(lo) - khi) < 2u;   // that entry is undecided (everything behind it is >= it; the four in front were certain)
+  }
+  if (!WORD && tie) {
+    asm volatile("; rare: a tie in the upper 32 bits of the radius draw");
+    lo = lower_bound_bracket(as_global(L.rcdf_f64), lo0, hi0, u2);
+  }
+  return lo;
+}
+
 // ---- first half: sample -> bore -> cold-bore exit -> pipes (:1746-1868) ----
-template <bool FAST, bool ZEXT, bool NOWALL = false>
+// WORD: the uniforms are the ray's random words over 2^32 (uniforms_of) - the word-exact CDF draws (energy_draw_begin).
+template <bool FAST, bool ZEXT, bool NOWALL = false, bool WORD = false>
 __device__ __forceinline__ void phase_a_bore(const HotA& H, const DevParams& P, const LdsTables& L, const Uniforms& U, RayState& st,
                                              bool& sampled, bool& reached, BoreRay& br, LaneMasks& M) {
   const bool cfg_test = FAST ? false : (H.test_active != 0);
@@ -635,37 +753,7 @@ __device__ __forceinline__ void phase_a_bore(const HotA& H, const DevParams& P, 
     const SinCosCoef K = sincos_coef();   // one set of scalar constants for the three evaluations
     sincos_turns<2>(u0, L.sincos, K, &s1, &c1);
     sincos_turns<1>(u1, L.sincos, K, &s2, &c2);
-    {
-      // lowerBound(fluxRadiusCDF, u2) (:437).  K = floor(u2 2^32) picks the guide bucket (sart_device.h: 2048 buckets, and 1024
-      // finer ones for u2 >= 31/32) whose two entries bracket the index.  The table sits in LDS as T' = floor(cdf 2^32) + 1 (half the
-      // bytes of the f64 table: the other half is image tile):  T' < K => cdf < u2;  T' > K + 1 => cdf > u2;  T' in {K, K + 1}:
-      // undecided, 2^-31 per entry looked at - the f64 table in device memory decides.  (The 1.0 pads read 0xFFFFFFFF.)
-      const uint32_t khi = U.u2_hi;
-      const uint32_t kb = khi >> 21, kt = (khi >> 17) - ((kRadiusGuideTopStart >> 17) - (uint32_t)(kRadiusGuide + 1));
-      const uint32_t k = khi >= kRadiusGuideTopStart ? kt : kb;
-      const int lo0 = (int)L.rguide[k];
-      const int hi0 = (int)L.rguide[k + 1];
-      // four consecutive candidates in ONE round trip to LDS: the table is sorted and rcdf[hi] >= u2, so entries at or beyond hi
-      // never count (the stage pads the table with four entries of 1.0)
-      const uint32_t c0 = L.rcdf_hi[lo0], c1 = L.rcdf_hi[lo0 + 1], c2 = L.rcdf_hi[lo0 + 2], c3 = L.rcdf_hi[lo0 + 3];
-      int lo = lo0 + (int)(c0 < khi) + (int)(c1 < khi) + (int)(c2 < khi) + (int)(c3 < khi);
-      // undecided: an entry in {K, K + 1}, i.e. the smallest of the four differences (unsigned: entries below K wrap to huge) < 2
-      bool tie = min(min(c0 - khi, c1 - khi), min(c2 - khi, c3 - khi)) < 2u;
-      if ((c3 < khi) & (hi0 > lo0 + 4)) {
-        asm volatile("; rare: radius bucket wider than four entries");
-        int hi = hi0;
-        while (lo < hi) {   // first entry that is not certainly below u2
-          const int mid = (lo + hi) >> 1;
-          if (L.rcdf_hi[mid] < khi) lo = mid + 1; else hi = mid;
-        }
-        tie = (L.rcdf_hi[lo] - khi) < 2u;   // that entry is undecided (everything behind it is >= it; the four in front were certain)
-      }
-      if (tie) {
-        asm volatile("; rare: a tie in the upper 32 bits of the radius draw");
-        lo = lower_bound_bracket(as_global(L.rcdf_f64), lo0, hi0, u2);
-      }
-      st.r_idx = lo;
-    }
+    st.r_idx = radius_draw<WORD>(L, U.u2_hi, u2);
     const double r = (0.0015 + (double)st.r_idx * 0.0005) * H.sun_radius;
     const double ox = c1 * s2 * r, oy = s1 * s2 * r, oz = c2 * r - H.sun_distance;
     // getRandomPointOnDisk (:412-422)
@@ -819,7 +907,9 @@ __device__ __forceinline__ bool phase_a_telescope(const HotA& H, const DevParams
     const double xs = fma(H.spider_z, tsx, X0), ys = fma(H.spider_z, tsy, Y0);
     const double c_sp = xs * frsq(fma(xs, xs, ys * ys));
     // (bitwise: the second test is needed by every lane the first one does not block - no divergent region around it)
-    const bool spoke_a = spoke_measure(H.spoke_n, c_ent) >= H.spoke_cos_thr, spoke_b = spoke_measure(H.spoke_n, c_sp) >= H.spoke_cos_thr;
+    double meas_a, meas_b;
+    spoke_measure_pair(H.spoke_n, c_ent, c_sp, meas_a, meas_b);
+    const bool spoke_a = meas_a >= H.spoke_cos_thr, spoke_b = meas_b >= H.spoke_cos_thr;
     const bool spoke = spoke_a | spoke_b;
     bool blocked = inner | ring | spoke;
     const bool xmm = H.telescope_kind == SART_TK_XMM;   // wave-uniform
@@ -895,13 +985,13 @@ __device__ __forceinline__ bool phase_a_telescope(const HotA& H, const DevParams
 }
 
 // Both halves back to back (histogram and record kernels).
-template <bool FAST, int ROT, bool ZEXT, bool NOWALL = false>
+template <bool FAST, int ROT, bool ZEXT, bool NOWALL = false, bool WORD = false>
 __device__ __forceinline__ bool phase_a_core(const HotA& H, const DevParams& P, const LdsTables& L, const Uniforms& U, RayState& st,
                                              bool& sampled, bool& reached, double& radial_out, LaneMasks& M) {
   static_assert(!ZEXT || (FAST && ROT == 0), "the z-extent form needs the magnet-frame slopes in phase B");
   static_assert(!NOWALL || ZEXT, "the constant-path form is a specialisation of the vacuum, unrotated one");
   BoreRay br;
-  phase_a_bore<FAST, ZEXT, NOWALL>(H, P, L, U, st, sampled, reached, br, M);
+  phase_a_bore<FAST, ZEXT, NOWALL, WORD>(H, P, L, U, st, sampled, reached, br, M);
   return phase_a_telescope<FAST, ROT>(H, P, tel_rot_of(P), L, br, st, radial_out, M);
 }
 
@@ -927,11 +1017,12 @@ __device__ __forceinline__ Uniforms uniforms_of(uint32_t seed_lo, uint32_t seed_
   U.u3 = u52(u3_hi, 0u);
   return U;
 }
-template <bool FAST, int ROT, bool ZEXT, bool NOWALL = false>
+// (WORD = false: the record kernel, which keeps the general draws for both sources of its uniforms)
+template <bool FAST, int ROT, bool ZEXT, bool NOWALL = false, bool WORD = true>
 __device__ __forceinline__ bool phase_a(const HotA& H, const DevParams& P, const LdsTables& L, uint32_t seed_lo,
                                         uint32_t seed_hi, uint64_t ray_id, uint32_t u3_hi, RayState& st, bool& sampled,
                                         bool& reached, double& radial, LaneMasks& M) {
-  return phase_a_core<FAST, ROT, ZEXT, NOWALL>(H, P, L, uniforms_of(seed_lo, seed_hi, ray_id, u3_hi), st, sampled, reached, radial, M);
+  return phase_a_core<FAST, ROT, ZEXT, NOWALL, WORD>(H, P, L, uniforms_of(seed_lo, seed_hi, ray_id, u3_hi), st, sampled, reached, radial, M);
 }
 
 // z of pointExitCB in the rotated telescope frame (z0 of :2051) from the ray as phase B knows it: the point of the ray whose z
@@ -991,6 +1082,9 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
 #define SART_B_STAMP(k, dep)
 #endif
   SART_B_STAMP(0, st.X0);
+  // the accumulating kernels draw with the ray's own random word (st.u5_hi: u5 = u5_hi / 2^32); the record kernel may have been
+  // handed its uniforms from outside and keeps the general draw
+  constexpr bool WORD = !RECORDS;
   // the energy draw runs beside the mirror arithmetic (its gathers are issued early, consumed late)
   const bool draw_energy = NODRAW ? false : __builtin_amdgcn_readfirstlane(e_idx_in) < 0;   // wave-uniform: false for the X-ray test source
   EnergyDraw ed = {};
@@ -998,9 +1092,9 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
   // working-set experiments (wrong results by design): 0x04000000 guide rows folded onto 16, 0x02000000 CDF rows folded onto 16,
   // 0x01000000 reflectivity / energy rows folded onto 32
   const uint32_t dbg = (uint32_t)__builtin_amdgcn_readfirstlane((int)A.flags);
-  if (draw_energy) energy_draw_begin(HB, (dbg & 0x02000000u) ? (st.r_idx & 15) : st.r_idx, st.u5, ed, (dbg & 0x04000000u) ? (st.r_idx & 15) : st.r_idx);
+  if (draw_energy) energy_draw_begin<WORD>(HB, (dbg & 0x02000000u) ? (st.r_idx & 15) : st.r_idx, st.u5, st.u5_hi, ed, (dbg & 0x04000000u) ? (st.r_idx & 15) : st.r_idx);
 #else
-  if (draw_energy) energy_draw_begin(HB, st.r_idx, st.u5, ed);
+  if (draw_energy) energy_draw_begin<WORD>(HB, st.r_idx, st.u5, st.u5_hi, ed);
 #endif
   const ShellDev& sh = L.shells[st.shell];
   // P / A may live in LDS: branch conditions are made wave-uniform (scalar branches) explicitly.
@@ -1081,24 +1175,26 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
   if (use_refl) {
     const int na2 = HB.refl_n_angles - 2;
     const double amin = P.refl_angle_min, inv_da = P.refl_inv_dangle, da = P.refl_dangle;
-    auto angle_cell = [&](double sina, double sin2a, double& xu_out) {
-      const double alpha = asin_small(sina, sin2a) * 57.29577951308232;   // getMirrorAngle (:782-795), degrees
+    double asin_a1, asin_a2;
+    asin_small_pair(sin_a1, sin2_a1, sin_a2, sin2_a2, asin_a1, asin_a2);   // getMirrorAngle (:782-795) of both mirrors
+    auto angle_cell = [&](double asin_a, double& xu_out) {
+      const double alpha = asin_a * 57.29577951308232;   // degrees
       const double t = (alpha - amin) * inv_da;
       int i = (int)t;                 // = floor(t) for t >= 0; negative or NaN t ends in cell 0 through the clamp
       i = max(min(i, na2), 0);
       xu_out = (alpha - fma((double)i, da, amin)) * inv_da;
       return i;
     };
-    ia1 = angle_cell(sin_a1, sin2_a1, xu1);
-    ia2 = angle_cell(sin_a2, sin2_a2, xu2);
+    ia1 = angle_cell(asin_a1, xu1);
+    ia2 = angle_cell(asin_a2, xu2);
   }
 
   // ---- energy index; the energy row and the two reflectivity pairs are requested the moment it is known and consumed
   // behind the detector-plane and window geometry ----
 #ifdef SART_DEBUG_KNOBS
-  const int e_idx = (dbg & 0x01000000u) ? ((draw_energy ? energy_draw_finish(HB, ed) : e_idx_in) & 31) : (draw_energy ? energy_draw_finish(HB, ed) : e_idx_in);
+  const int e_idx = (dbg & 0x01000000u) ? ((draw_energy ? energy_draw_finish<WORD>(HB, ed) : e_idx_in) & 31) : (draw_energy ? energy_draw_finish<WORD>(HB, ed) : e_idx_in);
 #else
-  const int e_idx = draw_energy ? energy_draw_finish(HB, ed) : e_idx_in;
+  const int e_idx = draw_energy ? energy_draw_finish<WORD>(HB, ed) : e_idx_in;
 #endif
   SART_B_STAMP(3, e_idx);
   // Accumulating kernels: only the lanes whose ray is still alive behind both mirrors (nickel, no-hit tests: `live` is settled
@@ -1289,7 +1385,7 @@ constexpr int kQueue = 128;   // ring capacity per wave: < 64 left over + <= 64 
 
 struct __align__(16) TablesLds {
   double sincos[2 * kSinCosEntries];
-  uint32_t rcdf_hi[kMaxRadii + 4];   // (floor(fluxRadiusCDF 2^52) >> 20) + 1, saturated; + four entries of 1.0 behind the table (four-wide candidate read)
+  uint32_t rcdf_hi[kMaxRadii + 4];   // floor(fluxRadiusCDF 2^52) >> 20 = floor(cdf 2^32), saturated; + four entries of 1.0 behind the table (four-wide candidate read)
   ShellDev shells[kMaxShells];
   uint16_t rguide[kRadiusGuideEntries + 6];
   uint8_t lut[kShellLutMax];
@@ -1329,7 +1425,7 @@ __device__ __forceinline__ void stage_tables(TablesLds& S, const DevParams& P, c
   for (int i = threadIdx.x; i < 2 * kSinCosEntries; i += BLOCK) S.sincos[i] = as_global(T.sincos_tab)[i];
   for (int i = threadIdx.x; i < P.n_radii + 4; i += BLOCK) {   // (cdf_hi32_kernel's definition, sart_tables.hip)
     const double c = (i < P.n_radii) ? as_global(T.flux_radius_cdf)[i] : 1.0;
-    const unsigned long long t = (__double2ull_rd(c * 4503599627370496.0) >> 20) + 1ull;   // the product is exact: cdf <= 1
+    const unsigned long long t = __double2ull_rd(c * 4503599627370496.0) >> 20;   // floor(cdf 2^32); the product is exact: cdf <= 1
     S.rcdf_hi[i] = t > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)t;
   }
   for (int i = threadIdx.x; i < kRadiusGuideEntries; i += BLOCK) S.rguide[i] = as_global(T.radius_guide)[i];
@@ -1579,6 +1675,7 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
       st.path_cb = PATHC ? H.length_b : Q.w[wave].path[slot];   // PATHC: z extent of the path = lengthB for every ray
       const uint2 cell = Q.w[wave].cell[slot];
       st.u5 = u52(cell.y, 0u);   // the same bits phase A would have carried as a double
+      st.u5_hi = cell.y;
       if (!ROT) {
         st.zcb = -(H.dz3 - H.dz1);
       } else {
@@ -2080,6 +2177,7 @@ __global__ __launch_bounds__(BLOCK) void shell_histogram_kernel(HotA H, const De
       st.tsx = Q.w[wave].tsx[slot]; st.tsy = Q.w[wave].tsy[slot];
       st.path_cb = Q.w[wave].path[slot];
       st.u5 = Q.w[wave].u5[slot];
+      st.u5_hi = upper32_of_uniform(st.u5);   // u5 = word / 2^32 (uniforms_of): the word back, exactly
       if (!ROT) {
         st.zcb = -(H.dz3 - H.dz1);
       } else {
@@ -2730,7 +2828,7 @@ __global__ __launch_bounds__(BLOCK) void trace_angular_scan_kernel(HotA H, const
     reload_hot(Hl);
     BoreRay br;
     LaneMasks M;
-    phase_a_bore<FAST, false>(Hl, Pb, L, uniforms_of(A.seed_lo, A.seed_hi, id_base + (uint64_t)rel, u3_hi), st, sampled, reached, br, M);
+    phase_a_bore<FAST, false, false, true>(Hl, Pb, L, uniforms_of(A.seed_lo, A.seed_hi, id_base + (uint64_t)rel, u3_hi), st, sampled, reached, br, M);
     stash_m = ballot64(valid) & M.reached;
     n_reached += (uint32_t)__popcll(stash_m);
     st_x1 = br.x1; st_y1 = br.y1; st_x3 = br.x3; st_y3 = br.y3;
@@ -2742,7 +2840,7 @@ __global__ __launch_bounds__(BLOCK) void trace_angular_scan_kernel(HotA H, const
       // (lanes whose ray is dead draw from a valid row with a valid uniform: the result is not used)
       HotB HB;
       reload_kernarg(HB, offsetof(AScanKernArgs, HB));
-      st_eidx = sample_energy_index(HB, st.r_idx, st.u5);
+      st_eidx = sample_energy_index<true>(HB, st.r_idx, st.u5, st.u5_hi);
     }
     ka = stash_m ? 0 : n_angles;   // (a wave none of whose rays reached the telescope has no angles to walk)
     __builtin_amdgcn_s_setprio(0);
@@ -3028,7 +3126,7 @@ __global__ __launch_bounds__(BLOCK) void ascan_images_kernel(HotA H, const DevBl
     reload_hot(Hl);
     BoreRay br;
     LaneMasks M;
-    phase_a_bore<FAST, false>(Hl, Pb, L, uniforms_of(A.seed_lo, A.seed_hi, id_base + (uint64_t)rel, u3_hi), st, sampled, reached, br, M);
+    phase_a_bore<FAST, false, false, true>(Hl, Pb, L, uniforms_of(A.seed_lo, A.seed_hi, id_base + (uint64_t)rel, u3_hi), st, sampled, reached, br, M);
     stash_m = ballot64(valid) & M.reached;
     n_reached += (uint32_t)__popcll(stash_m);
     st_x1 = br.x1; st_y1 = br.y1; st_x3 = br.x3; st_y3 = br.y3;
@@ -3040,7 +3138,7 @@ __global__ __launch_bounds__(BLOCK) void ascan_images_kernel(HotA H, const DevBl
       // (lanes whose ray is dead draw from a valid row with a valid uniform: the result is not used)
       HotB HB;
       reload_kernarg(HB, offsetof(AScanKernArgs, HB));
-      st_eidx = sample_energy_index(HB, st.r_idx, st.u5);
+      st_eidx = sample_energy_index<true>(HB, st.r_idx, st.u5, st.u5_hi);
     }
     ka = stash_m ? 0 : n_angles;   // (a wave none of whose rays reached the telescope has no angles to walk)
     __builtin_amdgcn_s_setprio(0);
@@ -3933,7 +4031,7 @@ __global__ __launch_bounds__(kRecBlock) void trace_records_kernel(HotA H, const 
       alive = phase_a_core<false, -1, false>(H, P, L, U, st, sampled, reached, radial, masks);
     } else {
       const uint32_t u3_hi = word_of(stream_block(ray_id >> 2, A.seed_lo, A.seed_hi), (uint32_t)ray_id & 3u);
-      alive = phase_a<false, -1, false>(H, P, L, A.seed_lo, A.seed_hi, ray_id, u3_hi, st, sampled, reached, radial, masks);
+      alive = phase_a<false, -1, false, false, false>(H, P, L, A.seed_lo, A.seed_hi, ray_id, u3_hi, st, sampled, reached, radial, masks);
     }
     int e_idx = -1;
     if (sampled) {
@@ -4070,6 +4168,16 @@ __global__ void math_eval_kernel(int fn, const double* __restrict__ in, double* 
     case 12: r = exp_neg(x); break;
     case 13: r = cos_any(x, tab, K); break;
     case 14: r = cos_any_vvs(x, tab, GasCos::make()); break;
+    // the paired forms (tests/test_gpu_horner_pairs.py): element i with its neighbour i ^ 1 as partner (n even), as the first
+    // member (odd cases) or the second (even cases) of the pair - both must give the single form's bits for element i
+    case 15: { const double y = in[min(i ^ 1, n - 1)]; double o; asin_small_pair(x, x * x, y, y * y, r, o); break; }
+    case 16: { const double y = in[min(i ^ 1, n - 1)]; double o; asin_small_pair(y, y * y, x, x * x, o, r); break; }
+    case 17: { double o; spoke_measure_pair(16, x, in[min(i ^ 1, n - 1)], r, o); break; }
+    case 18: { double o; spoke_measure_pair(16, in[min(i ^ 1, n - 1)], x, o, r); break; }
+    case 19: { double o; spoke_measure_pair(6, x, in[min(i ^ 1, n - 1)], r, o); break; }
+    case 20: { double o; spoke_measure_pair(6, in[min(i ^ 1, n - 1)], x, o, r); break; }
+    case 21: r = spoke_measure(16, x); break;
+    case 22: r = spoke_measure(6, x); break;
     default: break;
   }
   out[i] = r;
@@ -4077,7 +4185,7 @@ __global__ void math_eval_kernel(int fn, const double* __restrict__ in, double* 
 extern "C" __attribute__((visibility("default"))) int sart_internal_math_eval(int fn, const double* in_host, double* out_host, int n,
                                                                                const double* sincos_table_host) {
   double *d_in = nullptr, *d_out = nullptr, *d_tab = nullptr;
-  if (n < 1 || hipMalloc(&d_in, (size_t)n * 8) != hipSuccess || hipMalloc(&d_out, (size_t)n * 8) != hipSuccess ||
+  if (n < 1 || (fn >= 15 && fn <= 20 && (n & 1)) || hipMalloc(&d_in, (size_t)n * 8) != hipSuccess || hipMalloc(&d_out, (size_t)n * 8) != hipSuccess ||
       hipMalloc(&d_tab, 2 * kSinCosEntries * 8) != hipSuccess)
     return -1;
   (void)hipMemcpy(d_in, in_host, (size_t)n * 8, hipMemcpyHostToDevice);
@@ -4086,6 +4194,92 @@ extern "C" __attribute__((visibility("default"))) int sart_internal_math_eval(in
   const hipError_t e = hipMemcpy(out_host, d_out, (size_t)n * 8, hipMemcpyDeviceToHost);
   (void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(d_tab);
   return e == hipSuccess ? 0 : -2;
+}
+
+// ---- the two CDF draws under test (tests/test_gpu_word_draw.py), not part of the C-ABI: the index of (row, word) from the
+// word-exact form and from the general form, on a small table handed in from the host.  kind 0: energy draw, cdf = [n_rows][n_cols]
+// (padded, turned into cdf_hi32 and given its guide here); kind 1: radius draw, cdf = [n_cols] staged into LDS by stage_tables.
+void launch_cdf_hi32(const double* cdf_dev, uint32_t* out_dev, size_t n, hipStream_t stream);
+void launch_build_guides(const double* ecdf_dev, int n_rows, int n_energies, uint16_t* eguide_dev, const double* rcdf_dev, int n_radii,
+                         uint16_t* rguide_dev, uint32_t* status_dev, hipStream_t stream);
+__global__ __launch_bounds__(256) void word_draw_energy_kernel(HotB HB, const int32_t* __restrict__ rows, const uint32_t* __restrict__ words, int n,
+                                                               int32_t* __restrict__ out_word, int32_t* __restrict__ out_general) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t z = words[i];
+  const double u = u52(z, 0u);
+  out_word[i] = sample_energy_index<true>(HB, rows[i], u, z);
+  out_general[i] = sample_energy_index<false>(HB, rows[i], u);
+}
+__global__ __launch_bounds__(256) void word_draw_radius_kernel(const double* __restrict__ rcdf, const uint16_t* __restrict__ rguide,
+                                                               const double* __restrict__ sincos_tab, int n_radii,
+                                                               const uint32_t* __restrict__ words, int n, int32_t* __restrict__ out_word,
+                                                               int32_t* __restrict__ out_general) {
+  __shared__ TablesLds S;
+  DevParams P = {};
+  P.n_radii = n_radii;       // (no shells, no look-up table: stage_tables copies none)
+  DevTables T = {};
+  T.sincos_tab = sincos_tab;
+  T.flux_radius_cdf = rcdf;
+  T.radius_guide = rguide;
+  stage_tables<256>(S, P, T);
+  const LdsTables L{S.sincos, S.rcdf_hi, rcdf, S.rguide, S.shells, S.lut};
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t z = words[i];
+  out_word[i] = radius_draw<true>(L, z, u52(z, 0u));
+  out_general[i] = radius_draw<false>(L, z, u52(z, 0u));
+}
+extern "C" __attribute__((visibility("default"))) int sart_internal_word_draw(int kind, const double* cdf_host, int n_rows, int n_cols,
+                                                                               const int32_t* rows_host, const uint32_t* words_host, int n,
+                                                                               int32_t* out_word_host, int32_t* out_general_host) {
+  if (n < 1 || n_rows < 1 || n_cols < 1 || (kind != 0 && kind != 1) || (kind == 1 && (n_rows != 1 || n_cols > kMaxRadii)) || n_cols > 65535)
+    return -1;
+  if (kind == 0)
+    for (int i = 0; i < n; ++i)
+      if (rows_host[i] < 0 || rows_host[i] >= n_rows) return -1;
+  const int stride = kind == 0 ? n_cols + kEnergyCdfPad : n_cols;
+  std::vector<double> cdf((size_t)n_rows * stride, 1.0);
+  for (int r = 0; r < n_rows; ++r)
+    for (int k = 0; k < n_cols; ++k) cdf[(size_t)r * stride + k] = cdf_host[(size_t)r * n_cols + k];
+  const size_t n_guide = kind == 0 ? (size_t)n_rows * kEnergyGuideEntries : (size_t)kRadiusGuideEntries;
+  double *d_cdf = nullptr, *d_tab = nullptr;
+  uint32_t *d_hi = nullptr, *d_words = nullptr, *d_status = nullptr;
+  uint16_t* d_guide = nullptr;
+  int32_t *d_rows = nullptr, *d_ow = nullptr, *d_og = nullptr;
+  int rc = -2;
+  if (hipMalloc(&d_cdf, cdf.size() * 8) == hipSuccess && hipMalloc(&d_hi, cdf.size() * 4) == hipSuccess &&
+      hipMalloc(&d_guide, n_guide * 2) == hipSuccess && hipMalloc(&d_words, (size_t)n * 4) == hipSuccess &&
+      hipMalloc(&d_rows, (size_t)n * 4) == hipSuccess && hipMalloc(&d_ow, (size_t)n * 4) == hipSuccess &&
+      hipMalloc(&d_og, (size_t)n * 4) == hipSuccess && hipMalloc(&d_status, 8) == hipSuccess &&
+      hipMalloc(&d_tab, 2 * kSinCosEntries * 8) == hipSuccess) {
+    (void)hipMemcpy(d_cdf, cdf.data(), cdf.size() * 8, hipMemcpyHostToDevice);
+    (void)hipMemcpy(d_words, words_host, (size_t)n * 4, hipMemcpyHostToDevice);
+    (void)hipMemset(d_rows, 0, (size_t)n * 4);
+    (void)hipMemset(d_tab, 0, 2 * kSinCosEntries * 8);
+    if (kind == 0) {
+      (void)hipMemcpy(d_rows, rows_host, (size_t)n * 4, hipMemcpyHostToDevice);
+      launch_cdf_hi32(d_cdf, d_hi, cdf.size(), nullptr);
+      launch_build_guides(d_cdf, n_rows, n_cols, d_guide, nullptr, 0, nullptr, d_status, nullptr);
+      HotB HB = {};
+      HB.diff_flux_cdfs = d_cdf;
+      HB.cdf_hi32 = d_hi;
+      HB.energy_guide = d_guide;
+      HB.n_energies = n_cols;
+      HB.cdf_stride = stride;
+      hipLaunchKernelGGL(word_draw_energy_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, HB, d_rows, d_words, n, d_ow, d_og);
+    } else {
+      launch_build_guides(nullptr, 0, 0, nullptr, d_cdf, n_cols, d_guide, d_status, nullptr);
+      hipLaunchKernelGGL(word_draw_radius_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, d_cdf, d_guide, d_tab, n_cols, d_words, n, d_ow,
+                         d_og);
+    }
+    const hipError_t e1 = hipMemcpy(out_word_host, d_ow, (size_t)n * 4, hipMemcpyDeviceToHost);
+    const hipError_t e2 = hipMemcpy(out_general_host, d_og, (size_t)n * 4, hipMemcpyDeviceToHost);
+    rc = (e1 == hipSuccess && e2 == hipSuccess && hipGetLastError() == hipSuccess) ? 0 : -2;
+  }
+  (void)hipFree(d_cdf); (void)hipFree(d_hi); (void)hipFree(d_guide); (void)hipFree(d_words); (void)hipFree(d_rows);
+  (void)hipFree(d_ow); (void)hipFree(d_og); (void)hipFree(d_status); (void)hipFree(d_tab);
+  return rc;
 }
 
 // ---- launch wrappers (called from sart_api.hip) ----

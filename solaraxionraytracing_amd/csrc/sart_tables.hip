@@ -161,4 +161,15 @@ void launch_build_solar_tables(const double* em_dev, const double* radii_dev, co
                      n_energies, eguide_dev);
 }
 
+// The two guide tables alone, of CDFs that are already in device memory (the word-draw test entry, sart_kernels.hip); either
+// table may be left out (null).  status_dev: two words, as above.
+void launch_build_guides(const double* ecdf_dev, int n_rows, int n_energies, uint16_t* eguide_dev, const double* rcdf_dev, int n_radii,
+                         uint16_t* rguide_dev, uint32_t* status_dev, hipStream_t stream) {
+  (void)hipMemsetAsync(status_dev, 0, 2 * sizeof(uint32_t), stream);
+  if (rguide_dev) hipLaunchKernelGGL(radius_guide_kernel, dim3(1), dim3(256), 0, stream, rcdf_dev, n_radii, rguide_dev, status_dev);
+  if (eguide_dev)
+    hipLaunchKernelGGL(energy_guide_kernel, dim3((kEnergyGuideEntries + 255) / 256, n_rows), dim3(256), 0, stream, ecdf_dev, n_rows, n_energies,
+                       eguide_dev);
+}
+
 }  // namespace sart

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Instruction histogram of a trace kernel from the compiler's own listing (no GPU needed):
 
-  python tools/isa_histogram.py [--variant 5] [--fixed] [--json profiles/r03_isa_histogram.json] [--pmc profiles/<..>_pmc_summary.json]
+  python tools/isa_histogram.py [--variant 5] [--fixed] [--salu] [--json profiles/r03_isa_histogram.json] [--pmc profiles/<..>_pmc_summary.json]
 
 Compiles csrc/sart_kernels.hip with -save-temps into csrc/build/asm/ (same flags as the Makefile), cuts the chosen
 instantiation of trace_histogram_kernel out of the gfx950 assembly and counts its instructions per pipeline stage and class.
@@ -177,6 +177,68 @@ def histogram(lines):
 
 VALU_CLASSES = ("f64", "int", "cmp", "select", "mov", "cvt", "lane", "other")
 
+# Classes of the scalar instructions of the hot path (--salu): a wave issues one instruction of any kind per four cycles, so
+# with four waves per SIMD each of these takes an issue slot that a vector instruction could have had.
+SALU_CLASSES = ("literal_mov", "s_nop", "mask", "branch", "s_load", "s_setprio", "s_waitcnt", "other")
+MASK = re.compile(r"s_(and|or|xor|andn2|orn2|nand|nor|xnor|not|mov|cselect|bcnt1_i32|ff1_i32|wqm)_b64|s_(and|or|xor|andn2|orn2)_saveexec_b64|s_cmp_(eq|lg)_u64")
+SREG = re.compile(r"\bs(\d+)\b|\bs\[(\d+):(\d+)\]")
+
+
+def salu_class(mn: str, text: str) -> str:
+    if mn == "s_nop":
+        return "s_nop"
+    if mn.startswith("s_waitcnt"):
+        return "s_waitcnt"
+    if mn == "s_setprio":
+        return "s_setprio"
+    if mn.startswith(("s_load_", "s_buffer_load_")):
+        return "s_load"
+    if mn.startswith(("s_cbranch", "s_branch")):
+        return "branch"
+    if mn == "s_mov_b32" and re.search(r",\s*(0x[0-9a-fA-F]+|-?\d+(\.\d+)?)\s*(;.*)?$", text):
+        return "literal_mov"
+    if MASK.match(mn) or "exec" in text or "vcc" in text:
+        return "mask"
+    return "other"
+
+
+def sregs(operands: str) -> set:
+    out = set()
+    for m in SREG.finditer(operands):
+        if m.group(1) is not None:
+            out.add(int(m.group(1)))
+        else:
+            out.update(range(int(m.group(2)), int(m.group(3)) + 1))
+    return out
+
+
+def salu_breakdown(hot_lines):
+    """hot_lines: (stage, class, text) of the hot path in program order -> {stage: {class: n, "s_nop_by_neighbours": {"prev -> next": n},
+    "nop_between_literal_mov_and_reader": n}}.  An s_nop counts as `between a literal move and its reader` when the instruction in
+    front of it is an s_mov_b32 of a literal and the instruction behind it names the register that move wrote."""
+    out = collections.OrderedDict()
+    scalar = lambda c: c in ("salu", "s_waitcnt")
+    for i, (st, cls, text) in enumerate(hot_lines):
+        if not scalar(cls):
+            continue
+        mn = text.split()[0]
+        d = out.setdefault(st, {**{c: 0 for c in SALU_CLASSES}, "s_nop_by_neighbours": collections.Counter(), "nop_between_literal_mov_and_reader": 0})
+        c = salu_class(mn, text)
+        d[c] += 1
+        if c == "s_nop":
+            prev = hot_lines[i - 1][2] if i > 0 else ""
+            nxt = hot_lines[i + 1][2] if i + 1 < len(hot_lines) else ""
+            pm, nm = (prev.split() or ["-"])[0], (nxt.split() or ["-"])[0]
+            if salu_class(pm, prev) == "literal_mov":
+                pm = "s_mov_b32(literal)"
+                dst = sregs(prev.split(",")[0])
+                if dst & sregs(nxt.split(None, 1)[1] if " " in nxt else ""):
+                    d["nop_between_literal_mov_and_reader"] += 1
+            d["s_nop_by_neighbours"]["%s -> %s" % (pm, nm)] += 1
+    for d in out.values():
+        d["s_nop_by_neighbours"] = dict(d["s_nop_by_neighbours"].most_common())
+    return out
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -188,6 +250,7 @@ def main():
     ap.add_argument("--pmc", default=None, help="profiles/<tag>_<workload>_pmc_summary.json of the same build: measured totals beside the model")
     ap.add_argument("--passes-b", type=float, default=None, help="phase-B passes per 64 launched rays (default: from --pmc results or 0.3295)")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--salu", action="store_true", help="per-stage breakdown of the hot path's scalar instructions (also part of --json)")
     ap.add_argument("--dump", default=None, help="comma-separated classes: print the hot-path instructions of these classes (e.g. mov,select,cvt,lane)")
     args = ap.parse_args()
     asm = args.asm or build_asm()
@@ -204,6 +267,16 @@ def main():
                                 "vmem": d["hot"]["vmem"], "vmem_atomic": d["hot"]["vmem_atomic"], "s_waitcnt": d["hot"]["s_waitcnt"],
                                 "rare_valu": rare,
                                 "top_non_arithmetic": [[k, v] for k, v in d["mnemonics"].most_common() if classify(k) in ("cmp", "select", "mov", "cvt", "lane", "other")][:14]}
+    salu = salu_breakdown(histogram.hot_lines)
+    for st, d in salu.items():
+        report["stages"][st]["salu_by_kind"] = d
+    if args.salu:
+        print("%-9s " % "stage" + " ".join("%11s" % c for c in SALU_CLASSES) + " | nop between literal s_mov and its reader")
+        for st, d in salu.items():
+            print("%-9s " % st + " ".join("%11d" % d[c] for c in SALU_CLASSES) + " | %d" % d["nop_between_literal_mov_and_reader"])
+        for st, d in salu.items():
+            for k, v in d["s_nop_by_neighbours"].items():
+                print("  s_nop %-8s %3d  %s" % (st, v, k))
     if args.dump:
         want = set(args.dump.split(","))
         for st, cls, text in histogram.hot_lines:
