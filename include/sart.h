@@ -378,11 +378,48 @@ int sart_trace_records_passed(sart_context* ctx, const sart_trace_params_t* para
 int sart_trace_records_passed_device(sart_context* ctx, const sart_trace_params_t* params, sart_axion_t* ax_buf_device,
                                      uint64_t capacity, uint64_t* counts_device);
 /*
+ * The passed rays as selected columns, structure-of-arrays.  What the consumers of the passed records read is five or six of
+ * their 26 eight-byte words (generateResultPlots :2263-2289: x, y, r, weights, energiesAx, shellNumber); this call hands over
+ * those words alone.  Bit w < 26 of `column_mask` selects word w of the 208-byte record (SART_COL_*, in the order of
+ * sart_axion_t): word 0 = passed | passedTillWindow << 8 | hitNickel << 16, word 16 = kinds | kindsWindow << 8, word 22 =
+ * shellNumber as int64, every other word a double.  Bit 26 (SART_COL_RAY_ID) is no word of the record: the ray's global id,
+ * params->ray_id_offset + i, as uint64 - with it a caller can trace one ray again through sart_trace_records.
+ * Layout: the j-th selected column, in ascending bit order, occupies the 8-byte slots [j * capacity, (j + 1) * capacity) of
+ * `columns`; slot j * capacity + k holds that word of the k-th passed ray in ray-id order, byte for byte what
+ * sart_trace_records_passed writes for that ray.  sart_columns_len(mask, capacity) = popcount(mask) * capacity = the slots of
+ * the buffer (0 for a mask that is 0 or has a bit >= SART_COL_COUNT set, or if the product does not fit).
+ * `capacity` and the counts are those of sart_trace_records_passed: counts->n_passed is whole whatever the capacity, and no
+ * slot at or behind min(n_passed, capacity) of any column is written.  SART_ERR_INVALID_ARGUMENT, with the context as it was:
+ * mask 0, a bit >= 27, a NULL pointer (`columns` may be NULL with capacity 0), a buffer size that overflows.
+ * The rays are traced in chunks of 2^20; the selected words and a flag word per ray are staged column by column in device
+ * scratch, compacted with the integer scan of the record path (the order does not depend on the launch geometry) and, in the
+ * host form, copied out one column at a time while the next chunk is traced.  The host form does not pre-fault `columns`:
+ * pages the caller has not touched yet are mapped by the copies themselves (INTEGRATION.md 4b has both rates).
+ */
+enum {
+  SART_COL_FLAGS = 0, SART_COL_POINTDATA_X = 1, SART_COL_POINTDATA_Y = 2, SART_COL_POINTDATA_X_BEFORE = 3,
+  SART_COL_POINTDATA_Y_BEFORE = 4, SART_COL_POINTDATA_R = 5, SART_COL_WEIGHTS = 6, SART_COL_WEIGHTS_ALL = 7,
+  SART_COL_TRANSMISSION_MAGNET = 8, SART_COL_YAW_ANGLES = 9, SART_COL_PIXVALS_X = 10, SART_COL_PIXVALS_Y = 11,
+  SART_COL_RADII = 12, SART_COL_ENERGIES_AX = 13, SART_COL_ENERGIES_AX_ALL = 14, SART_COL_ENERGIES_AX_WINDOW = 15,
+  SART_COL_KINDS = 16, SART_COL_TRANS_PROB_WINDOW = 17, SART_COL_TRANS_PROB_ARGON = 18, SART_COL_TRANS_PROB_DETECTOR = 19,
+  SART_COL_TRANS_PROB_MAGNET = 20, SART_COL_DEVIATION_DET = 21, SART_COL_SHELL_NUMBER = 22, SART_COL_ENERGIES_PRE = 23,
+  SART_COL_EMRATES_PRE = 24, SART_COL_REFLECT = 25, SART_COL_RAY_ID = 26, SART_COL_COUNT = 27
+};
+size_t sart_columns_len(uint32_t column_mask, uint64_t capacity);
+int sart_trace_columns_passed(sart_context* ctx, const sart_trace_params_t* params, uint32_t column_mask, void* columns,
+                              uint64_t capacity, sart_record_counts_t* counts);
+/* Same with DEVICE memory for the columns and for the counts; enqueues on the stream.  params->accumulate != 0: the rays are
+ * appended behind the counts_device[1] already in every column and the counts grow; 0: the counts start from zero. */
+int sart_trace_columns_passed_device(sart_context* ctx, const sart_trace_params_t* params, uint32_t column_mask,
+                                     void* columns_device, uint64_t capacity, uint64_t* counts_device);
+/*
  * Device scratch of the record entries.  sart_trace_records and sart_trace_records_passed[_device] trace into buffers the
  * context owns: one of min(n_rays, 2^20) records (208 B each: 218 MB at full size), a second one as soon as a call needs more
  * than one chunk, and - host form of the passed-only call above one chunk - a third for the compacted records (436 - 654 MB in
- * all).  The buffers only grow (a call never frees: hipFree would synchronise the device) and stay until sart_destroy - or
- * until this call, which waits for the context's streams and frees them; the next record call allocates again.  The
+ * all).  sart_trace_columns_passed[_device] keeps its own: the staged words of one chunk (8 B per selected word and ray + 4 B
+ * per ray: 54 MB for six columns at full size) and, host form, one or two compacted half-buffers of the same shape (ray id
+ * included).  The buffers only grow (a call never frees: hipFree would synchronise the device) and stay until sart_destroy - or
+ * until this call, which waits for the context's streams and frees them; the next record or column call allocates again.  The
  * histogram / scan entries do not use them.
  */
 int sart_release_scratch(sart_context* ctx);

@@ -7,6 +7,7 @@
         [--massScanMin M0 --massScanMax M1 --numMassScanPoints K]     (not in the reference: see below)
         [--energyScanMin E0 --energyScanMax E1 --numEnergyScanPoints K]  (not in the reference: see below)
         [--shellBreakdown]                                               (not in the reference: see below)
+        [--events PATH.npz [--eventColumns a,b,c]]                       (not in the reference: see below)
 
 Same switches, same two modes (full run = calculateFluxFractions, :2755-2776; angular scan, :2778-2815).  What differs:
 `--rays` replaces the compile-time constant NumberOfPointsSun (:251, default 1e6), plots are never made (the numbers
@@ -21,7 +22,11 @@ detection efficiency per energy and, for a parallel beam, the effective area (th
 llnl_xray_telescope_cast_effective_area_parallel_light_DTU_thesis.csv).  It cannot be combined with the other scans.
 --shellBreakdown (full-run mode only) also breaks the result down by mirror shell (Axion.shellNumber, :218; the data of
 generateResultPlots' dfDet "Shell" column and energies_by_shell plot, :2351-2376) and writes `shell_breakdown_{year}.csv` and
-`energies_by_shell_{year}.csv` beside the image CSV."""
+`energies_by_shell_{year}.csv` beside the image CSV.
+--events PATH.npz (full-run mode only) also writes the passed rays themselves, as columns in ray order (the `axionsPass` that
+generateResultPlots plots from, :2253-2289): one array per name of --eventColumns (default pointdataX, pointdataY, pointdataR,
+energiesAx, weights, shellNumber, ray_id; any field of the Axion record, `flags`, `kinds_packed`, `ray_id`) and the four counts
+n_rays, n_passed, n_passed_till_window, n_hit_nickel.  The rays are those of the image: same seed, same ids."""
 from __future__ import annotations
 
 import argparse
@@ -35,6 +40,9 @@ from .raytracer import (RayTracer, angle_image_names, containment_radii, initFul
                         performEnergyScan, write_image_csv, write_shell_csvs)
 
 WINDOW_YEAR = {_lib.DK_INGRID2017: "2017", _lib.DK_INGRID2018: "2018", _lib.DK_INGRIDIAXO: "IAXO"}   # WindowYearKind, :1468-1484
+
+
+EVENT_COLUMNS = ("pointdataX", "pointdataY", "pointdataR", "energiesAx", "weights", "shellNumber", "ray_id")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -62,6 +70,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--numEnergyScanPoints", type=int, default=32)
     ap.add_argument("--shellBreakdown", action="store_true",
                     help="extension (full-run mode): the result per mirror shell, shell_breakdown_{year}.csv and energies_by_shell_{year}.csv")
+    ap.add_argument("--events", default="", metavar="PATH.npz",
+                    help="extension (full-run mode): the passed rays as columns, in ray order, and the four counts, as a numpy .npz")
+    ap.add_argument("--eventColumns", default=",".join(EVENT_COLUMNS), help="comma-separated columns of --events (default: %(default)s)")
     ap.add_argument("--config", default="", help="path of a config.toml")
     ap.add_argument("--configPath", default="", help="directory that holds config.toml")
     ap.add_argument("--rays", type=float, default=1e6, help="NumberOfPointsSun (raytracer.nim:251)")
@@ -77,7 +88,14 @@ def energy_scan_requested(args) -> bool:
 
 def check_scan_args(ap: argparse.ArgumentParser, args) -> None:
     """The energy scan is a mode of its own: exits 2 (argparse's usage error) when it is combined with another scan or asks for
-    no valid energies.  --shellBreakdown belongs to the full-run mode: exits 2 beside any scan."""
+    no valid energies.  --shellBreakdown and --events belong to the full-run mode: exit 2 beside any scan."""
+    if getattr(args, "events", "") and (energy_scan_requested(args) or args.massScanMax > args.massScanMin
+                                        or args.angularScanMin != args.angularScanMax):
+        ap.error("--events belongs to the full run: it cannot be combined with a mass, angular or energy scan")
+    if getattr(args, "events", ""):
+        unknown = [c for c in event_columns(args) if c not in _lib.COLUMNS]
+        if unknown or not event_columns(args):
+            ap.error("--eventColumns: unknown column(s) %s; known: %s" % (", ".join(unknown) or "(none given)", ", ".join(_lib.COLUMNS)))
     if getattr(args, "shellBreakdown", False) and (energy_scan_requested(args) or args.massScanMax > args.massScanMin
                                                    or args.angularScanMin != args.angularScanMax):
         ap.error("--shellBreakdown belongs to the full run: it cannot be combined with a mass, angular or energy scan")
@@ -87,6 +105,10 @@ def check_scan_args(ap: argparse.ArgumentParser, args) -> None:
         ap.error("--energyScanMin / --energyScanMax cannot be combined with a mass scan or an angular scan")
     if not (0.0 < args.energyScanMin < args.energyScanMax) or args.numEnergyScanPoints < 1:
         ap.error("the energy scan needs 0 < --energyScanMin < --energyScanMax (keV) and --numEnergyScanPoints >= 1")
+
+
+def event_columns(args) -> list:
+    return [c.strip() for c in args.eventColumns.split(",") if c.strip()]
 
 
 def setup_from_args(args):
@@ -160,6 +182,10 @@ def main(argv=None) -> int:
             if args.shellBreakdown:
                 for path in write_shell_csvs(args.outpath, year, shells, full.energies, s["N_RAYS"]):
                     print("wrote", path)
+            if args.events:
+                cols, counts = rt.trace_columns(n, event_columns(args), seed=args.seed, flags=flags)
+                np.savez(args.events, **cols, **counts)
+                print("wrote", args.events, "(%d passed rays, columns %s)" % (counts["n_passed"], ", ".join(cols)))
         else:
             res = performAngularScan(rt, args.angularScanMin, args.angularScanMax, args.numAngularScanPoints, n, seed=args.seed, flags=flags,
                                      fused=args.fusedAngularScan, errors=args.fusedAngularScan, images=args.angularImages)

@@ -163,6 +163,28 @@ AXION_DTYPE = _np.dtype({
     "itemsize": 208,
 })
 
+# Columns of sart_trace_columns_passed: name -> bit of the column mask (SART_COL_*).  The 8-byte fields of the record by their
+# word, the two packed byte groups (word 0: passed | passedTillWindow << 8 | hitNickel << 16, word 16: kinds | kindsWindow << 8)
+# and the ray's global id, which is no word of the record.
+COLUMNS = {n: AXION_DTYPE.fields[n][1] // 8 for n in AXION_DTYPE.names if AXION_DTYPE.fields[n][0].itemsize == 8}
+COLUMNS.update(flags=0, kinds_packed=16, ray_id=26)
+COLUMN_COUNT = 27
+
+
+def column_dtype(name: str):
+    """How the 8-byte slots of column ``name`` are read."""
+    return _np.dtype("i8" if name == "shellNumber" else "u8" if name in ("flags", "kinds_packed", "ray_id") else "f8")
+
+
+def column_mask(columns) -> int:
+    """Mask of the named columns; the buffer holds them in ascending bit order (``sorted(set(columns), key=COLUMNS.get)``)."""
+    mask = 0
+    for n in columns:
+        if n not in COLUMNS:
+            raise KeyError("unknown column %r (one of %s)" % (n, ", ".join(COLUMNS)))
+        mask |= 1 << COLUMNS[n]
+    return mask
+
 
 class RecordCounts(C.Structure):
     """sart_record_counts_t"""
@@ -247,6 +269,9 @@ SART_SYMBOLS = {
     "sart_trace_records_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p]),
     "sart_trace_records_passed": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p, C.c_uint64, _P(RecordCounts)]),
     "sart_trace_records_passed_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "sart_columns_len": (C.c_size_t, [C.c_uint32, C.c_uint64]),
+    "sart_trace_columns_passed": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_uint32, C.c_void_p, C.c_uint64, _P(RecordCounts)]),
+    "sart_trace_columns_passed_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
     "sart_release_scratch": (C.c_int, [C.c_void_p]),
     "sart_trace_histogram_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p]),
     "sart_trace_histogram": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _P(Summary)]),

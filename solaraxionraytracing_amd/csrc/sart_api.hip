@@ -58,6 +58,11 @@ int records_block();
 int compact_chunk_max();
 void launch_compact_records(const sart_axion_t* rec, uint32_t n, sart_axion_t* out, unsigned long long capacity, uint32_t* block_counts,
                             unsigned long long* block_first, unsigned long long* counts, hipStream_t stream);
+void launch_stage_columns(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, uint64_t* stage, uint32_t* flags,
+                          uint32_t mask, int n_blocks, hipStream_t stream);
+void launch_compact_columns(const uint64_t* stage, const uint32_t* flags, uint32_t n, uint32_t mask, unsigned long long ray_id0, uint64_t* out,
+                            unsigned long long capacity, uint32_t* block_counts, unsigned long long* block_first,
+                            unsigned long long* counts, hipStream_t stream);
 int histogram_blocks_per_cu(int variant);
 void launch_build_solar_tables(const double* em_dev, const double* radii_dev, const double* energies_dev, int n_radii, int n_energies,
                                double* cdf_dev, double* row_sum_dev, double* rcdf_dev, uint16_t* rguide_dev, uint16_t* eguide_dev,
@@ -234,6 +239,10 @@ struct sart_context {
   DevBuf<uint32_t> d_cmp_counts;
   DevBuf<unsigned long long> d_cmp_first, d_cmp_totals;
   unsigned long long* h_cmp_totals = nullptr;
+  // passed rays as columns: the staged words [K][chunk] and flag words [chunk] of one chunk, two compacted half-buffers [K][chunk]
+  // (host form only); the scan scratch and the counts are the record path's
+  DevBuf<uint64_t> d_col_stage, d_col_cmp[2];
+  DevBuf<uint32_t> d_col_flags;
   hipStream_t copy_stream = nullptr;   // D2H of the record chunks, beside the kernels on `stream`
   hipEvent_t rec_traced[2] = {nullptr, nullptr}, rec_copied[2] = {nullptr, nullptr};
   bool derived_dirty = true;
@@ -1662,6 +1671,132 @@ int sart_trace_records_passed(sart_context* c, const sart_trace_params_t* p, sar
   return 0;
 }
 
+// ---- passed rays as selected columns ---------------------------------------------------------------------------------------------
+// The consumers of the passed records read five or six of their 26 words (generateResultPlots raytracer.nim:2263-2289).  Same
+// chunks, scan and counts as the passed-records path, but the stage kernel writes only the selected words, structure-of-arrays
+// (sart_kernels.hip: columns_stage / count / scatter), and only those cross PCIe.
+namespace {
+constexpr uint32_t kColumnMaskAll = (uint32_t(1) << SART_COL_COUNT) - 1u;
+constexpr uint32_t kColumnMaskStaged = (uint32_t(1) << SART_COL_RAY_ID) - 1u;   // the words of the record: the ray id is computed
+int popcount32(uint32_t v) { return __builtin_popcount(v); }
+bool columns_args_ok(uint32_t mask, const void* columns, uint64_t capacity) {
+  if (mask == 0 || (mask & ~kColumnMaskAll) || (!columns && capacity)) return false;
+  return capacity <= (~uint64_t(0) / 8) / static_cast<uint64_t>(popcount32(mask));   // the buffer's bytes fit 64 bits
+}
+// one chunk: q->n_rays rays staged, counted and scattered to out_dev[K][capacity] behind counts_dev[1]
+int columns_chunk(sart_context* c, const sart_trace_params_t* q, uint32_t mask, uint64_t* out_dev, uint64_t capacity, unsigned long long* counts_dev) {
+  if (int rc = refresh_derived(c)) return rc;
+  if (int rc = sync_blob(c)) return rc;
+  TraceArgs a;
+  if (int rc = make_args(c, q, a)) return rc;
+  if (c->blocks_per_cu_rec == 0) c->blocks_per_cu_rec = 4;
+  {
+    TimedLaunch tl(c);
+    launch_stage_columns(c->hot, c->hotb, c->d_blob.p, a, c->d_col_stage.p, c->d_col_flags.p, mask,
+                         grid_for(a.n_rays, c->n_cu, c->blocks_per_cu_rec, records_block()), c->stream);
+  }
+  launch_compact_columns(c->d_col_stage.p, c->d_col_flags.p, static_cast<uint32_t>(q->n_rays), mask, q->ray_id_offset, out_dev, capacity,
+                         c->d_cmp_counts.p, c->d_cmp_first.p, counts_dev, c->stream);
+  SART_HIP(hipGetLastError());
+  return 0;
+}
+int columns_scratch(sart_context* c, uint32_t mask, uint64_t chunk) {
+  if (int rc = c->d_col_stage.reserve(std::max<uint64_t>(1, popcount32(mask & kColumnMaskStaged) * chunk))) return rc;
+  if (int rc = c->d_col_flags.reserve(chunk)) return rc;
+  if (int rc = c->d_cmp_counts.resize(1024)) return rc;
+  if (int rc = c->d_cmp_first.resize(1024)) return rc;
+  return 0;
+}
+}  // namespace
+
+size_t sart_columns_len(uint32_t mask, uint64_t capacity) {
+  if (mask == 0 || (mask & ~kColumnMaskAll)) return 0;
+  const uint64_t k = static_cast<uint64_t>(popcount32(mask));
+  return capacity <= ~uint64_t(0) / k ? static_cast<size_t>(k * capacity) : 0;
+}
+
+int sart_trace_columns_passed_device(sart_context* c, const sart_trace_params_t* p, uint32_t mask, void* out_dev, uint64_t capacity,
+                                     uint64_t* counts_dev) {
+  if (!c || !p || !counts_dev || !columns_args_ok(mask, out_dev, capacity)) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument or invalid column mask / capacity");
+  SART_HIP(hipSetDevice(c->device));
+  if (!p->accumulate) SART_HIP(hipMemsetAsync(counts_dev, 0, 4 * sizeof(uint64_t), c->stream));
+  if (p->n_rays == 0) return 0;
+  const uint64_t chunk = compact_chunk_of(c);
+  if (int rc = columns_scratch(c, mask, std::min<uint64_t>(chunk, p->n_rays))) return rc;
+  sart_trace_params_t q = *p;
+  for (uint64_t done = 0; done < p->n_rays; done += chunk) {
+    q.n_rays = std::min(chunk, p->n_rays - done);
+    q.ray_id_offset = p->ray_id_offset + done;
+    if (int rc = columns_chunk(c, &q, mask, static_cast<uint64_t*>(out_dev), capacity, reinterpret_cast<unsigned long long*>(counts_dev))) return rc;
+  }
+  return 0;
+}
+
+int sart_trace_columns_passed(sart_context* c, const sart_trace_params_t* p, uint32_t mask, void* out, uint64_t capacity,
+                              sart_record_counts_t* counts) {
+  if (!c || !p || !counts || !columns_args_ok(mask, out, capacity)) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument or invalid column mask / capacity");
+  std::memset(counts, 0, sizeof *counts);
+  if (p->n_rays == 0) return 0;
+  SART_HIP(hipSetDevice(c->device));
+  const uint64_t n = p->n_rays, chunk = compact_chunk_of(c), n_chunks = (n + chunk - 1) / chunk, pitch = std::min(chunk, n);
+  const uint64_t n_cols = static_cast<uint64_t>(popcount32(mask));
+  if (int rc = columns_scratch(c, mask, pitch)) return rc;
+  for (int k = 0; k < (n_chunks > 1 ? 2 : 1); ++k)   // the compacted half-buffers [n_cols][pitch]
+    if (int rc = c->d_col_cmp[k].reserve(n_cols * pitch)) return rc;
+  if (int rc = c->d_cmp_totals.resize(8)) return rc;
+  if (!c->h_cmp_totals) SART_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_cmp_totals), 8 * sizeof(unsigned long long), hipHostMallocDefault));
+  if (!c->copy_stream) SART_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+  for (int k = 0; k < 2; ++k) {
+    if (!c->rec_traced[k]) SART_HIP(hipEventCreateWithFlags(&c->rec_traced[k], hipEventDisableTiming));
+    if (!c->rec_copied[k]) SART_HIP(hipEventCreateWithFlags(&c->rec_copied[k], hipEventDisableTiming));
+  }
+  uint64_t* const cols = static_cast<uint64_t*>(out);
+  sart_trace_params_t q = *p;
+  int rc = 0;
+  hipError_t he = hipSuccess;   // as in sart_trace_records: no early return while work on the caller's buffer is queued
+  const char* what = "";
+  auto step = [&](hipError_t e, const char* name) {
+    if (e != hipSuccess && he == hipSuccess) { he = e; what = name; }
+    return e == hipSuccess;
+  };
+  uint64_t written = 0;
+  for (uint64_t k = 0; k <= n_chunks && rc == 0 && he == hipSuccess; ++k) {
+    if (k < n_chunks) {   // stage + compact chunk k into half-buffer k & 1 once the copies of chunk k - 2 have left it
+      const int b = static_cast<int>(k & 1);
+      if (k >= 2 && !step(hipStreamWaitEvent(c->stream, c->rec_copied[b], 0), "hipStreamWaitEvent(stream)")) break;
+      q.n_rays = std::min(chunk, n - k * chunk);
+      q.ray_id_offset = p->ray_id_offset + k * chunk;
+      unsigned long long* totals = c->d_cmp_totals.p + 4 * b;
+      if (!step(hipMemsetAsync(totals, 0, 4 * sizeof(unsigned long long), c->stream), "hipMemsetAsync(counts)")) break;
+      rc = (c->knobs.records_fail_chunk > 0 && k + 1 == static_cast<uint64_t>(c->knobs.records_fail_chunk))
+               ? fail(SART_ERR_INTERNAL, "sart_trace_columns_passed: failure injected by SART_RECORDS_FAIL_CHUNK (test hook)")
+               : columns_chunk(c, &q, mask, c->d_col_cmp[b].p, pitch, totals);
+      if (rc) break;
+      if (!step(hipMemcpyAsync(c->h_cmp_totals + 4 * b, totals, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(counts)")) break;
+      if (!step(hipEventRecord(c->rec_traced[b], c->stream), "hipEventRecord(traced)")) break;
+    }
+    if (k > 0) {          // the columns of chunk k - 1 cross PCIe while chunk k is traced: one copy per column
+      const int b = static_cast<int>((k - 1) & 1);
+      if (!step(hipEventSynchronize(c->rec_traced[b]), "hipEventSynchronize(traced)")) break;
+      const unsigned long long* t = c->h_cmp_totals + 4 * b;
+      counts->n_rays += t[0]; counts->n_passed += t[1]; counts->n_passed_till_window += t[2]; counts->n_hit_nickel += t[3];
+      const uint64_t cnt = std::min<uint64_t>(t[1], capacity - written);
+      bool ok = true;
+      for (uint64_t j = 0; j < n_cols && cnt && ok; ++j)
+        ok = step(hipMemcpyAsync(cols + j * capacity + written, c->d_col_cmp[b].p + j * pitch, cnt * 8, hipMemcpyDeviceToHost, c->copy_stream),
+                  "hipMemcpyAsync(column)");
+      if (!ok) break;
+      written += cnt;
+      if (!step(hipEventRecord(c->rec_copied[b], c->copy_stream), "hipEventRecord(copied)")) break;
+    }
+  }
+  const hipError_t e1 = hipStreamSynchronize(c->copy_stream), e2 = hipStreamSynchronize(c->stream);
+  if (rc) return rc;
+  if (he != hipSuccess) return fail(SART_ERR_NO_DEVICE, std::string("sart_trace_columns_passed: ") + what + ": " + hipGetErrorString(he));
+  if (e1 != hipSuccess || e2 != hipSuccess) return fail(SART_ERR_NO_DEVICE, std::string("sart_trace_columns_passed: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+  return 0;
+}
+
 int sart_release_scratch(sart_context* c) {
   if (!c) return fail(SART_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SART_HIP(hipSetDevice(c->device));
@@ -1670,6 +1805,9 @@ int sart_release_scratch(sart_context* c) {
   c->d_rec.release();
   c->d_rec2.release();
   c->d_cmp.release();
+  c->d_col_stage.release();
+  c->d_col_flags.release();
+  for (auto& b : c->d_col_cmp) b.release();
   return 0;
 }
 

@@ -4126,6 +4126,111 @@ __global__ __launch_bounds__(kCompactBlock) void records_scatter_kernel(const sa
   }
 }
 
+// ---- passed rays as selected columns (include/sart.h: sart_trace_columns_passed) ---------------------------------------------
+// The same rays, but only the words the caller selects (bit w of `mask` = word w of the record), structure-of-arrays.  Three
+// steps per chunk of n rays: columns_stage_kernel traces the rays as trace_records_kernel does and writes, per ray, its flag
+// word as u32 and each selected word into stage[slot][n] (slot = the number of selected words below it; coalesced 8-byte
+// stores); columns_count_kernel counts the flags per block (records_scan_kernel then turns the counts into offsets, as for the
+// records); columns_scatter_kernel moves the words of the passed rays to out[slot][capacity].
+constexpr uint32_t kColumnWords = sizeof(sart_axion_t) / 8;   // 26; bit 26 of a mask = the ray id, which is computed, not staged
+__global__ __launch_bounds__(kRecBlock) void columns_stage_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
+                                                                   uint64_t* __restrict__ stage, uint32_t* __restrict__ flags,
+                                                                   HotB HB, uint32_t mask) {
+  __shared__ TablesLds S;
+  __shared__ DevBlob B;
+  {
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(blob);
+    uint64_t* dst = reinterpret_cast<uint64_t*>(&B);
+    for (int i = threadIdx.x; i < (int)(sizeof(DevBlob) / 8); i += kRecBlock) dst[i] = src[i];
+    __syncthreads();
+  }
+  const DevParams& P = B.P;
+  stage_tables<kRecBlock>(S, P, B.T);
+  const LdsTables L{S.sincos, S.rcdf_hi, B.T.flux_radius_cdf, S.rguide, S.shells, S.lut};
+
+  const uint64_t stride = (uint64_t)gridDim.x * kRecBlock;
+  for (uint64_t i = (uint64_t)blockIdx.x * kRecBlock + threadIdx.x; i < A.n_rays; i += stride) {
+    sart_axion_t rec = {};
+    RayState st;
+    bool sampled, reached;
+    double radial;
+    LaneMasks masks;
+    const uint64_t ray_id = A.ray_id_offset + i;
+    const uint32_t u3_hi = word_of(stream_block(ray_id >> 2, A.seed_lo, A.seed_hi), (uint32_t)ray_id & 3u);
+    const bool alive = phase_a<false, -1, false, false, false>(H, P, L, A.seed_lo, A.seed_hi, ray_id, u3_hi, st, sampled, reached, radial, masks);
+    int e_idx = -1;
+    if (sampled) {
+      e_idx = H.test_active ? P.n_energies : sample_energy_index(HB, st.r_idx, st.u5);
+      rec.emratesPre = 1.0;
+      rec.energiesPre = load_energy_row(HB, e_idx).energy;
+    }
+    if (ballot64(alive)) {
+      RayOut ro;
+      if (!sampled) { st.u5 = 0.0; st.r_idx = 0; }
+      phase_b<true, false, -1, false>(P, L, HB, A, st, e_idx >= 0 ? e_idx : 0, alive, ro, &rec);
+    }
+    // the words of store_record, each behind a wave-uniform test of its mask bit (w is a literal in every call: the record is
+    // never indexed at run time and stays in registers); the slot is a scalar popcount
+    auto bits = [](double v) { return (uint64_t)__double_as_longlong(v); };
+    auto put = [&](uint32_t w, uint64_t v) {
+      if ((mask >> w) & 1u) stage[(uint64_t)__popc(mask & ((1u << w) - 1u)) * A.n_rays + i] = v;
+    };
+    const uint64_t w0 = (uint64_t)rec.passed | ((uint64_t)rec.passedTillWindow << 8) | ((uint64_t)rec.hitNickel << 16);
+    flags[i] = (uint32_t)w0;
+    put(0, w0);
+    put(1, bits(rec.pointdataX)); put(2, bits(rec.pointdataY)); put(3, bits(rec.pointdataXBefore)); put(4, bits(rec.pointdataYBefore));
+    put(5, bits(rec.pointdataR)); put(6, bits(rec.weights)); put(7, bits(rec.weightsAll)); put(8, bits(rec.transmissionMagnet));
+    put(9, bits(rec.yawAngles)); put(10, bits(rec.pixvalsX)); put(11, bits(rec.pixvalsY)); put(12, bits(rec.radii));
+    put(13, bits(rec.energiesAx)); put(14, bits(rec.energiesAxAll)); put(15, bits(rec.energiesAxWindow));
+    put(16, (uint64_t)rec.kinds | ((uint64_t)rec.kindsWindow << 8));
+    put(17, bits(rec.transProbWindow)); put(18, bits(rec.transProbArgon)); put(19, bits(rec.transProbDetector));
+    put(20, bits(rec.transProbMagnet)); put(21, bits(rec.deviationDet)); put(22, (uint64_t)rec.shellNumber);
+    put(23, bits(rec.energiesPre)); put(24, bits(rec.emratesPre)); put(25, bits(rec.reflect));
+  }
+}
+// records_count_kernel on the staged flag words
+__global__ __launch_bounds__(kCompactBlock) void columns_count_kernel(const uint32_t* __restrict__ flags, uint32_t n,
+                                                                       uint32_t* __restrict__ block_counts,
+                                                                       unsigned long long* __restrict__ counts) {
+  __shared__ uint32_t part[kCompactBlock / 64][3];
+  const uint32_t i = blockIdx.x * kCompactBlock + threadIdx.x;
+  const uint32_t f = i < n ? flags[i] : 0u;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t np = (uint32_t)__popcll(ballot64((f & 0xFFu) != 0u)), nw = (uint32_t)__popcll(ballot64((f & 0xFF00u) != 0u)),
+                 nn = (uint32_t)__popcll(ballot64((f & 0xFF0000u) != 0u));
+  if (lane == 0) { part[wave][0] = np; part[wave][1] = nw; part[wave][2] = nn; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t a = 0, b = 0, c = 0;
+    for (int w = 0; w < kCompactBlock / 64; ++w) { a += part[w][0]; b += part[w][1]; c += part[w][2]; }
+    block_counts[blockIdx.x] = a;
+    if (b) atomicAdd(&counts[2], (unsigned long long)b);
+    if (c) atomicAdd(&counts[3], (unsigned long long)c);
+  }
+}
+// Passed ray i of the chunk goes to index d = block_first + (passed rays before it in its block) of every column, if d is below
+// the capacity: column j of the output = out[j * capacity ..], the staged ones first, in mask order, then the ray id (bit 26).
+__global__ __launch_bounds__(kCompactBlock) void columns_scatter_kernel(const uint64_t* __restrict__ stage, const uint32_t* __restrict__ flags,
+                                                                         uint32_t n, const unsigned long long* __restrict__ block_first,
+                                                                         uint64_t* __restrict__ out, unsigned long long capacity,
+                                                                         uint32_t mask, unsigned long long ray_id0) {
+  __shared__ uint32_t wave_count[kCompactBlock / 64];
+  const uint32_t i = blockIdx.x * kCompactBlock + threadIdx.x;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const bool passed = i < n && (flags[i] & 0xFFu) != 0u;
+  const uint64_t m = ballot64(passed);
+  const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+  if (lane == 0) wave_count[wave] = (uint32_t)__popcll(m);
+  __syncthreads();
+  uint32_t before = 0;
+  for (int w = 0; w < wave; ++w) before += wave_count[w];
+  const unsigned long long d = block_first[blockIdx.x] + before + prefix;
+  if (!passed || d >= capacity) return;
+  const uint32_t n_staged = (uint32_t)__popc(mask & ((1u << kColumnWords) - 1u));
+  for (uint32_t j = 0; j < n_staged; ++j) out[(unsigned long long)j * capacity + d] = stage[(uint64_t)j * n + i];
+  if ((mask >> kColumnWords) & 1u) out[(unsigned long long)n_staged * capacity + d] = ray_id0 + i;
+}
+
 // The offsets the kernels assume for their own arguments when they re-read them from the kernel-argument segment
 // (reload_hot / reload_zones / reload_kernarg).  Not part of the C-ABI: tests/test_host_and_abi.py compares them with the
 // argument offsets in the code object's metadata, so that a compiler that lays arguments out differently fails a CPU test
@@ -4528,6 +4633,21 @@ void launch_compact_records(const sart_axion_t* rec, uint32_t n, sart_axion_t* o
 void launch_trace_records(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, sart_axion_t* out, int n_blocks,
                           hipStream_t stream, const double* uniforms_dev) {
   hipLaunchKernelGGL(trace_records_kernel, dim3(n_blocks), dim3(kRecBlock), 0, stream, H, blob, A, out, HB, uniforms_dev);
+}
+// stage: [popcount(mask & 0x3FFFFFF)][A.n_rays] words, flags: [A.n_rays]
+void launch_stage_columns(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, uint64_t* stage, uint32_t* flags,
+                          uint32_t mask, int n_blocks, hipStream_t stream) {
+  hipLaunchKernelGGL(columns_stage_kernel, dim3(n_blocks), dim3(kRecBlock), 0, stream, H, blob, A, stage, flags, HB, mask);
+}
+// scratch and counts as in launch_compact_records; out: [popcount(mask)][capacity] words
+void launch_compact_columns(const uint64_t* stage, const uint32_t* flags, uint32_t n, uint32_t mask, unsigned long long ray_id0, uint64_t* out,
+                            unsigned long long capacity, uint32_t* block_counts, unsigned long long* block_first,
+                            unsigned long long* counts, hipStream_t stream) {
+  const uint32_t n_blocks = (n + kCompactBlock - 1) / kCompactBlock;
+  hipLaunchKernelGGL(columns_count_kernel, dim3(n_blocks), dim3(kCompactBlock), 0, stream, flags, n, block_counts, counts);
+  hipLaunchKernelGGL(records_scan_kernel, dim3(1), dim3(kCompactMaxBlocks), 0, stream, block_counts, n_blocks, block_first, counts, n);
+  hipLaunchKernelGGL(columns_scatter_kernel, dim3(n_blocks), dim3(kCompactBlock), 0, stream, stage, flags, n, block_first, out, capacity, mask,
+                     ray_id0);
 }
 
 }  // namespace sart

@@ -135,6 +135,30 @@ def initFullSetup(experiment: int = _lib.ES_BABYIAXO, detector: int = _lib.DK_IN
     return FullRaytraceSetup(setup, np.ascontiguousarray(energies), rcdf, ecdf, refl, det, flags, meta=meta, device_emission=dev_em)
 
 
+def columns_from_records(records: np.ndarray, columns, ray_ids=None) -> dict:
+    """The columns of RayTracer.trace_columns out of an AXION_DTYPE array (the records of the passed rays, in ray order):
+    {name: 1-D array}, dtypes as there.  ``flags`` = passed | passedTillWindow << 8 | hitNickel << 16 and ``kinds_packed`` =
+    kinds | kindsWindow << 8, as the library packs words 0 and 16 of the record; ``ray_id`` is no part of a record and comes
+    from ``ray_ids`` (the global ids of these records)."""
+    records = np.asarray(records)
+    assert records.dtype == AXION_DTYPE
+    u8 = lambda name: records[name].astype(np.uint64)
+    cols = {}
+    for c in sorted(set(columns), key=_lib.COLUMNS.__getitem__):
+        if c == "flags":
+            cols[c] = u8("passed") | (u8("passedTillWindow") << np.uint64(8)) | (u8("hitNickel") << np.uint64(16))
+        elif c == "kinds_packed":
+            cols[c] = u8("kinds") | (u8("kindsWindow") << np.uint64(8))
+        elif c == "ray_id":
+            if ray_ids is None:
+                raise ValueError("the ray_id column is not in the records: pass ray_ids")
+            cols[c] = np.ascontiguousarray(ray_ids, dtype=np.uint64)
+            assert cols[c].shape == records.shape
+        else:
+            cols[c] = np.ascontiguousarray(records[c])
+    return cols
+
+
 class RayTracer:
     """One libsart context on one GPU holding the captures of ``traceAxionWrapper``
     (raytracer.nim:2223-2232)."""
@@ -142,6 +166,7 @@ class RayTracer:
     def __init__(self, full: FullRaytraceSetup, device: int = 0):
         self.lib = _lib.load_sart()
         self.full = full
+        self.device = int(device)
         h = C.c_void_p()
         _lib.check(self.lib.sart_create(device, C.byref(h)))
         self.handle = h
@@ -328,6 +353,58 @@ class RayTracer:
     def trace_records_passed_device(self, params: TraceParams, out_ptr: int, capacity: int, counts_ptr: int):
         """sart_trace_records_passed_device: device pointers (records, four uint64 counts); enqueues on the stream."""
         _lib.check(self.lib.sart_trace_records_passed_device(self.handle, C.byref(params), C.c_void_p(out_ptr), int(capacity), C.c_void_p(counts_ptr)))
+
+    # -- the passed rays as selected columns (include/sart.h: sart_trace_columns_passed) --------
+    DEFAULT_COLUMNS = ("pointdataX", "pointdataY", "pointdataR", "energiesAx", "weights", "shellNumber")
+
+    def trace_columns(self, n: int, columns=DEFAULT_COLUMNS, seed: int = 299792458, ray_id_offset: int = 0, flags: int | None = None,
+                      capacity: int | None = None, out: np.ndarray | None = None):
+        """The passed rays of traceAxionWrapper(n, ...) as the named columns (_lib.COLUMNS), in ray order: ({name: 1-D array},
+        counts as traceAxionWrapperPassed returns them).  Each array holds min(n_passed, capacity) entries and is a view of one
+        [K][capacity] buffer of 8-byte slots (``out``: a C-contiguous uint64 array of the caller's with at least that many
+        elements; ``capacity`` defaults to n, which is always enough): float64, except shellNumber (int64) and flags /
+        kinds_packed / ray_id (uint64).  Only these words cross PCIe."""
+        names = sorted(set(columns), key=_lib.COLUMNS.__getitem__)
+        mask = _lib.column_mask(names)
+        n_cols = bin(mask).count("1")      # (two names of one word, as "flags" and nothing else today, would share a column)
+        capacity = int(n if capacity is None else capacity)
+        if out is None:
+            out = np.empty(n_cols * capacity, dtype=np.uint64)
+        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.size >= n_cols * capacity
+        p = self.trace_params(n, seed, ray_id_offset, flags)
+        cnt = _lib.RecordCounts()
+        _lib.check(self.lib.sart_trace_columns_passed(self.handle, C.byref(p), mask, out.ctypes.data_as(C.c_void_p) if out.size else None,
+                                                      capacity, C.byref(cnt)))
+        counts = {k: int(getattr(cnt, k)) for k, _ in _lib.RecordCounts._fields_}
+        m = min(counts["n_passed"], capacity)
+        flat = out.reshape(-1)
+        slot = {bit: j for j, bit in enumerate(sorted({_lib.COLUMNS[c] for c in names}))}
+        return {c: flat[slot[_lib.COLUMNS[c]] * capacity:][:m].view(_lib.column_dtype(c)) for c in names}, counts
+
+    def trace_columns_device(self, params: TraceParams, columns, capacity: int, out=None, counts=None):
+        """sart_trace_columns_passed_device on torch tensors of the context's device: ({name: 1-D tensor of ``capacity`` slots},
+        counts tensor of four int64).  The tensors are views of ``out``, one [K, capacity] int64 buffer (made here unless
+        given): float64 for the doubles, int64 for shellNumber, flags, kinds_packed and ray_id.  Only enqueues on the context's
+        stream: slots at and behind counts[1] keep what ``out`` held.  ``params.accumulate`` appends behind counts[1]."""
+        import torch
+        names = sorted(set(columns), key=_lib.COLUMNS.__getitem__)
+        mask = _lib.column_mask(names)
+        bits = sorted({_lib.COLUMNS[c] for c in names})
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty((len(bits), int(capacity)), dtype=torch.int64, device=dev)
+        if counts is None:
+            counts = torch.zeros(4, dtype=torch.int64, device=dev)
+        assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() >= len(bits) * int(capacity) and out.device == dev
+        assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() >= 4 and counts.device == dev
+        _lib.check(self.lib.sart_trace_columns_passed_device(self.handle, C.byref(params), mask, C.c_void_p(out.data_ptr()) if out.numel() else None,
+                                                             int(capacity), C.c_void_p(counts.data_ptr())))
+        rows = out.reshape(-1)[:len(bits) * int(capacity)].view(len(bits), int(capacity))
+        cols = {}
+        for c in names:
+            row = rows[bits.index(_lib.COLUMNS[c])]
+            cols[c] = row.view(torch.float64) if _lib.column_dtype(c) == np.float64 else row
+        return cols, counts
 
     def trace_records_uniforms(self, uniforms: np.ndarray, flags: int | None = None) -> np.ndarray:
         """Test entry (sart_internal_trace_records_uniforms, not part of include/sart.h): the records of the rays whose six
