@@ -737,7 +737,7 @@ __device__ __forceinline__ int radius_draw(const LdsTables& L, uint32_t u2_hi, d
 // WORD: the uniforms are the ray's random words over 2^32 (uniforms_of) - the word-exact CDF draws (energy_draw_begin).
 template <bool FAST, bool ZEXT, bool NOWALL = false, bool WORD = false>
 __device__ __forceinline__ void phase_a_bore(const HotA& H, const DevParams& P, const LdsTables& L, const Uniforms& U, RayState& st,
-                                             bool& sampled, bool& reached, BoreRay& br, LaneMasks& M) {
+                                             bool& sampled, bool& reached, BoreRay& br, LaneMasks& M, const SinCosCoef* held = nullptr) {
   const bool cfg_test = FAST ? false : (H.test_active != 0);
   const double u0 = U.u0, u1 = U.u1, u2 = U.u2, u3 = U.u3, u4 = U.u4;
   st.u5 = U.u5;
@@ -750,7 +750,8 @@ __device__ __forceinline__ void phase_a_bore(const HotA& H, const DevParams& P, 
   if (!cfg_test) {
     // getRandomPointFromSolarModel (:425-442): theta1 = 360 u0 deg, theta2 = 180 u1 deg (uniform in theta)
     double s1, c1, s2, c2;
-    const SinCosCoef K = sincos_coef();   // one set of scalar constants for the three evaluations
+    // one set of constants for the three evaluations: scalar, written here, or the caller's copy in vector registers (`held`)
+    const SinCosCoef K = held ? *held : sincos_coef();
     sincos_turns<2>(u0, L.sincos, K, &s1, &c1);
     sincos_turns<1>(u1, L.sincos, K, &s2, &c2);
     st.r_idx = radius_draw<WORD>(L, U.u2_hi, u2);
@@ -987,11 +988,11 @@ __device__ __forceinline__ bool phase_a_telescope(const HotA& H, const DevParams
 // Both halves back to back (histogram and record kernels).
 template <bool FAST, int ROT, bool ZEXT, bool NOWALL = false, bool WORD = false>
 __device__ __forceinline__ bool phase_a_core(const HotA& H, const DevParams& P, const LdsTables& L, const Uniforms& U, RayState& st,
-                                             bool& sampled, bool& reached, double& radial_out, LaneMasks& M) {
+                                             bool& sampled, bool& reached, double& radial_out, LaneMasks& M, const SinCosCoef* held = nullptr) {
   static_assert(!ZEXT || (FAST && ROT == 0), "the z-extent form needs the magnet-frame slopes in phase B");
   static_assert(!NOWALL || ZEXT, "the constant-path form is a specialisation of the vacuum, unrotated one");
   BoreRay br;
-  phase_a_bore<FAST, ZEXT, NOWALL, WORD>(H, P, L, U, st, sampled, reached, br, M);
+  phase_a_bore<FAST, ZEXT, NOWALL, WORD>(H, P, L, U, st, sampled, reached, br, M, held);
   return phase_a_telescope<FAST, ROT>(H, P, tel_rot_of(P), L, br, st, radial_out, M);
 }
 
@@ -1021,8 +1022,8 @@ __device__ __forceinline__ Uniforms uniforms_of(uint32_t seed_lo, uint32_t seed_
 template <bool FAST, int ROT, bool ZEXT, bool NOWALL = false, bool WORD = true>
 __device__ __forceinline__ bool phase_a(const HotA& H, const DevParams& P, const LdsTables& L, uint32_t seed_lo,
                                         uint32_t seed_hi, uint64_t ray_id, uint32_t u3_hi, RayState& st, bool& sampled,
-                                        bool& reached, double& radial, LaneMasks& M) {
-  return phase_a_core<FAST, ROT, ZEXT, NOWALL, WORD>(H, P, L, uniforms_of(seed_lo, seed_hi, ray_id, u3_hi), st, sampled, reached, radial, M);
+                                        bool& reached, double& radial, LaneMasks& M, const SinCosCoef* held = nullptr) {
+  return phase_a_core<FAST, ROT, ZEXT, NOWALL, WORD>(H, P, L, uniforms_of(seed_lo, seed_hi, ray_id, u3_hi), st, sampled, reached, radial, M, held);
 }
 
 // z of pointExitCB in the rotated telescope frame (z0 of :2051) from the ray as phase B knows it: the point of the ray whose z
@@ -1064,6 +1065,16 @@ struct RayOut {
 // experiment builds)
 #ifndef SART_GATHER_LIVE
 #define SART_GATHER_LIVE 1
+#endif
+// 1: ... and everything behind the gathers - detector plane, chip and strip geometry, weights, out.* - runs for those lanes only
+// (0: only the three gathers are predicated; experiment builds).  The record kernel and the energy scan keep the flat form.
+#ifndef SART_B_LIVE_REGION
+#define SART_B_LIVE_REGION 1
+#endif
+// 1: trace_histogram_kernel holds phase A's sine / cosine coefficients in vector registers where it has them to spare (0: every
+// pass writes them into scalar registers; experiment builds)
+#ifndef SART_A_SINCOS_VGPR
+#define SART_A_SINCOS_VGPR 1
 #endif
 struct EScanGeo {
   double cos_ya, path_cb, distance_pipe_m, xu1, xu2;
@@ -1198,13 +1209,29 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
 #endif
   SART_B_STAMP(3, e_idx);
   // Accumulating kernels: only the lanes whose ray is still alive behind both mirrors (nickel, no-hit tests: `live` is settled
-  // here; lanes beyond the pass' valid rays included) request them - the others would fetch three cache lines for values that
-  // live_m discards below.  Their row reads as zero and their reflectivities as (1, 1).  ONE predicated region; every ballot of
-  // this function stays outside it (a ballot in there would see the live lanes only).  Record mode gathers for every lane.
+  // here; lanes beyond the pass' valid rays included) go on - `live_m` discards whatever the others would compute, so they are
+  // switched off from here to the end of the function (REGION: ONE predicated region, skipped by a wave without a live lane).
+  // What leaves the region per lane (the r_* values and out.* below) is left UNSPECIFIED for the dead lanes instead of
+  // defaulted - a default is a v_mov per register at the join.  The compares and ballots behind out.m_till / out.m_passed stay
+  // behind the region, on those values, and keep their `live_m &`: a mask written inside it would be a per-lane value at the
+  // join (the compiler turns a predicate that crosses it into v_cndmask + v_cmp per ballot).  Record mode and the energy scan run
+  // flat, for every lane, with every default.
+  constexpr bool REGION = SART_B_LIVE_REGION && SART_GATHER_LIVE && !RECORDS && !ESCAN;
+  const bool gather = (RECORDS || !SART_GATHER_LIVE) ? true : __builtin_amdgcn_inverse_ballot_w64(live_m);
+  // (wave-uniform: the gas stage's conversion probability is multiplied in last, a zero takes the ray out of out.m_till)
+  const bool r_prob_deferred = REGION && !SCAN && stage_gas != 0 && !(flags & SART_CF_IGNORE_CONV_PROB);
+  // (deliberately without initialisers: an initial value is what the dead lanes would carry across the join.  Every lane reads
+  // them behind the region - through the empty asm there, so that nothing is derived from "unwritten" - and live_m or
+  // out.m_passed masks whatever a dead lane holds.)
+  double r_pdx, r_pdy, r_rdet2, r_w_till, r_weight, r_reflect, r_prob;
+  GasRay r_gas;
+  out.e_idx = e_idx;
+  // (the body keeps the function's indentation: it is the function's tail, called under `gather` or unconditionally)
+  auto behind_the_mirrors = [&]() __attribute__((always_inline)) {
+  if constexpr (REGION) asm volatile("; hot: phase B behind the mirrors, live lanes only");
   EnergyDev en = {};
   d2 g1 = {1.0, 1.0}, g2 = {1.0, 1.0};
-  const bool gather = (RECORDS || !SART_GATHER_LIVE) ? true : __builtin_amdgcn_inverse_ballot_w64(live_m);
-  if (!ESCAN && gather) {
+  if (!ESCAN && (REGION || gather)) {
     asm volatile("; hot: gathers of the live lanes");
     en = load_energy_row(HB, e_idx);
     if (use_refl) {
@@ -1254,7 +1281,8 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
   const double rdet2 = fma(pdx, pdx, pdy * pdy);
   const bool off_window = rdet2 > P.radius_window_sq, off_x = fabs(pdx) > P.chip_cx, off_y = fabs(pdy) > P.chip_cy;
   const bool on_chip = !((!(flags & SART_CF_IGNORE_DET_WINDOW)) & off_window) & !(off_x | off_y);
-  const uint64_t on_chip_m = ~(((flags & SART_CF_IGNORE_DET_WINDOW) ? 0ull : ballot64(off_window)) | ballot64(off_x) | ballot64(off_y));
+  const uint64_t on_chip_m = REGION ? 0ull : ~(((flags & SART_CF_IGNORE_DET_WINDOW) ? 0ull : ballot64(off_window)) | ballot64(off_x) | ballot64(off_y));
+  if constexpr (REGION) { r_pdx = pdx; r_pdy = pdy; r_rdet2 = rdet2; }
   const double yt = fabs(fma(pdy, P.theta_c, -pdx * P.theta_s));
   bool in_strip = false;
   for (int i = 0; i < n_half_strips; ++i) in_strip = in_strip | ((yt > P.strip_lo[i]) & (yt < P.strip_hi[i]));
@@ -1312,10 +1340,11 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
 
   const bool has_weight = weight != 0.0;
   const bool till_window = live & has_weight;
-  out.m_till = live_m & ballot64(has_weight);   // (a deferred conversion probability of exactly zero is taken out below)
+  if constexpr (REGION) r_w_till = weight;
+  else out.m_till = live_m & ballot64(has_weight);   // (a deferred conversion probability of exactly zero is taken out below)
   if (RECORDS && till_window) rec->passedTillWindow = 1;
   live = live & on_chip;
-  live_m &= on_chip_m;
+  if constexpr (!REGION) live_m &= on_chip_m;
 
   const double trans_window = (n_half_strips > 0) ? (in_strip ? en.t_strongback : en.t_window) : 0.0;
   const uint8_t kind_w = in_strip ? SART_MK_SI : SART_MK_SI3N4;
@@ -1327,19 +1356,28 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
   if (!SCAN && prob_deferred) {
     const double prob = gas_conversion_prob(P.gas_dm2_abs, out.gas, P.gas_term1, L.sincos, GasCos::make());
     weight *= prob;
-    out.m_till &= ballot64(prob != 0.0);
+    if constexpr (REGION) r_prob = prob;
+    else out.m_till &= ballot64(prob != 0.0);
   }
 
   SART_B_STAMP(5, weight);
   const bool final_weight = weight != 0.0;
-  out.m_passed = live_m & ballot64(final_weight);
-  out.passed = RECORDS ? (live & final_weight) : __builtin_amdgcn_inverse_ballot_w64(out.m_passed);
-  out.reflect = reflectv;
-  out.e_idx = e_idx;
-  out.rdet = fsqrt_pos(rdet2 + 1e-300);       // + 1e-300: exact no-op unless the ray hits the chip centre to the last bit
-  out.px = -pdx + P.chip_cx;                                          // :2203-2204
-  out.py = pdy + P.chip_cy;
-  out.weight = weight;
+  if constexpr (!REGION) {
+    out.m_passed = live_m & ballot64(final_weight);
+    out.passed = RECORDS ? (live & final_weight) : __builtin_amdgcn_inverse_ballot_w64(out.m_passed);
+  }
+  if constexpr (REGION) {
+    r_reflect = reflectv; r_weight = weight;
+    if constexpr (SCAN) r_gas = out.gas;
+  } else {
+    out.reflect = reflectv;
+    out.rdet = fsqrt_pos(rdet2 + 1e-300);     // + 1e-300: exact no-op unless the ray hits the chip centre to the last bit
+    out.weight = weight;
+  }
+  if constexpr (!REGION) {
+    out.px = -pdx + P.chip_cx;                                        // :2203-2204
+    out.py = pdy + P.chip_cy;
+  }
   if (RECORDS && live) {
     if (n_half_strips > 0) {
       rec->transProbWindow = trans_window;
@@ -1358,6 +1396,31 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
     rec->weights = weight;
     rec->weightsAll = weight;
     rec->passed = (weight != 0.0) ? 1 : 0;
+  }
+  };   // behind_the_mirrors
+  if constexpr (REGION) {
+    // (a copy of the flags that the region does not share: a test of `flags` made on both sides of the join is merged into a
+    // per-lane value across it)
+    uint32_t flags_j = flags;
+    asm volatile("" : "+s"(flags_j));
+    if (gather) behind_the_mirrors();
+    // (opaque: the compiler otherwise sinks the compares below into the region and carries their predicates across the join)
+    asm volatile("" : "+v"(r_pdx), "+v"(r_pdy), "+v"(r_rdet2), "+v"(r_w_till), "+v"(r_weight));
+    // the region's predicates and their masks, with every lane switched on again, as the flat form takes them: the dead
+    // lanes' bits are unspecified and fall to live_m (still the rays alive behind the mirrors)
+    out.m_till = live_m & ballot64(r_w_till != 0.0);
+    if (r_prob_deferred) out.m_till &= ballot64(r_prob != 0.0);
+    const uint64_t off_m = ((flags_j & SART_CF_IGNORE_DET_WINDOW) ? 0ull : ballot64(r_rdet2 > P.radius_window_sq)) | ballot64(fabs(r_pdx) > P.chip_cx) |
+                           ballot64(fabs(r_pdy) > P.chip_cy);
+    out.m_passed = live_m & ~off_m & ballot64(r_weight != 0.0);
+    out.reflect = r_reflect; out.weight = r_weight;
+    out.rdet = fsqrt_pos(r_rdet2 + 1e-300);   // (consumed by the passed rays only: the compiler sinks it into their region)
+    if constexpr (SCAN) out.gas = r_gas;
+    out.passed = __builtin_amdgcn_inverse_ballot_w64(out.m_passed);
+    out.px = -r_pdx + P.chip_cx;                                      // :2203-2204
+    out.py = r_pdy + P.chip_cy;
+  } else {
+    behind_the_mirrors();
   }
 }
 
@@ -1620,6 +1683,15 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
   };
 
+  // The seven sine / cosine coefficients of phase A (sincos_coef()'s values) in vector registers for the whole kernel, where the
+  // instantiation has them to spare - vacuum stage, specialised: 107 / 108 of 128 VGPRs without them, the gas and generic ones
+  // stand at 114 - 123: 14 s_mov_b32 less per phase-A pass, and the scalar registers they occupied across the three
+  // evaluations no longer push kernel-argument pointers into spill lanes (variant 5: 23 -> 12 scalar spills).  The empty asm
+  // keeps the compiler from folding the values back into literals.
+  constexpr bool HOLD_SINCOS = SART_A_SINCOS_VGPR && FAST && GAS == 0 && !SCAN;
+  SinCosCoef Ksc = {-0.5992645293207921, 2.5501640398773455, -5.16771278004997, 3.141592653589793, -1.3352627688545895, 4.0587121264167685,
+                    -4.934802200544679};
+  if constexpr (HOLD_SINCOS) asm volatile("" : "+v"(Ksc.s3), "+v"(Ksc.s2), "+v"(Ksc.s1), "+v"(Ksc.s0), "+v"(Ksc.d3), "+v"(Ksc.d2), "+v"(Ksc.d1));
   // stage A1 for the ray with id id_base + rel (valid lanes only count); u3_hi = its word of the shared stream
   auto run_phase_a = [&](uint32_t rel, bool valid, uint32_t u3_hi) {
     SART_STAGE_MARK("A1");
@@ -1631,7 +1703,8 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
     reload_hot(Hl);
     constexpr bool ZEXT = FAST && !ROT && GAS >= 0;
     LaneMasks M;
-    (void)phase_a<FAST, ROT ? 1 : 0, ZEXT, PATHC>(Hl, Pb, L, A.seed_lo, A.seed_hi, id_base + (uint64_t)rel, u3_hi, st, sampled, reached, radial, M);
+    (void)phase_a<FAST, ROT ? 1 : 0, ZEXT, PATHC>(Hl, Pb, L, A.seed_lo, A.seed_hi, id_base + (uint64_t)rel, u3_hi, st, sampled, reached, radial, M,
+                                                  HOLD_SINCOS ? &Ksc : nullptr);
     const uint64_t valid_m = ballot64(valid);
     n_reached += (uint32_t)__popcll(valid_m & M.reached);
     const uint64_t selected = valid_m & M.ok;

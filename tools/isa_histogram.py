@@ -240,6 +240,52 @@ def salu_breakdown(hot_lines):
     return out
 
 
+# Kinds of the hot path's LDS reads (--lds), told apart by their addressing: the rings are read with the 64-element stride
+# forms or beyond the tables (offset >= 32 KiB); the tables behind the parameter block (shell table, sine / cosine table, CDF
+# guides) with a per-lane base register and an offset of 4 KiB or more; a read at a small immediate offset is a field of the
+# DevBlob / TraceArgs copies at the head of LDS (one address for the whole wave: a broadcast) when its base register is one that
+# serves several such fields in the stage, and a per-lane table access (base register = entry address) otherwise.
+LDS_KINDS = ("ring", "table", "parameter", "per_lane_small_offset", "write_or_atomic")
+
+
+def lds_breakdown(hot_lines):
+    """-> {stage: {kind: n, "parameter_reads": [text, ...]}} of the hot path's ds_* instructions."""
+    per_stage = collections.OrderedDict()
+    for st, cls, text in hot_lines:
+        if cls == "lds":
+            per_stage.setdefault(st, []).append(text)
+    out = collections.OrderedDict()
+    for st, texts in per_stage.items():
+        parsed = []
+        for t in texts:
+            mn = t.split()[0]
+            ops = [o.strip() for o in t.split(None, 1)[1].split(",")] if " " in t else []
+            unit = 8 if "b64" in mn else 4
+            unit *= 64 if "st64" in mn else 1
+            offs = [int(m.group(2)) * (unit if m.group(1) != "offset" else 1) for m in re.finditer(r"(offset[01]?):(\d+)", t)] or [0]
+            is_read = mn.startswith("ds_read") or mn.startswith("ds_load")
+            base = ops[1] if is_read and len(ops) > 1 else (ops[0] if ops else "")
+            parsed.append((mn, base.split()[0] if base else "", max(offs), is_read, t))
+        small = collections.Counter(b for mn, b, off, rd, t in parsed if rd and "st64" not in mn and off < 4096)
+        d = {k: 0 for k in LDS_KINDS}
+        d["parameter_reads"] = []
+        for mn, base, off, rd, t in parsed:
+            if not rd:
+                kind = "write_or_atomic"
+            elif "st64" in mn or off >= 32768:
+                kind = "ring"
+            elif off >= 4096:
+                kind = "table"
+            elif small[base] >= 3:
+                kind = "parameter"
+                d["parameter_reads"].append(t)
+            else:
+                kind = "per_lane_small_offset"
+            d[kind] += 1
+        out[st] = d
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--variant", type=int, default=5, help="0 vacuum, 1 generic, 2 generic rotated, 3 gas, 4 rotated, 5 vacuum + constant path (headline)")
@@ -251,6 +297,7 @@ def main():
     ap.add_argument("--passes-b", type=float, default=None, help="phase-B passes per 64 launched rays (default: from --pmc results or 0.3295)")
     ap.add_argument("--json", default=None)
     ap.add_argument("--salu", action="store_true", help="per-stage breakdown of the hot path's scalar instructions (also part of --json)")
+    ap.add_argument("--lds", action="store_true", help="per-stage breakdown of the hot path's LDS instructions: ring, table, parameter broadcast (also part of --json)")
     ap.add_argument("--dump", default=None, help="comma-separated classes: print the hot-path instructions of these classes (e.g. mov,select,cvt,lane)")
     args = ap.parse_args()
     asm = args.asm or build_asm()
@@ -277,6 +324,15 @@ def main():
         for st, d in salu.items():
             for k, v in d["s_nop_by_neighbours"].items():
                 print("  s_nop %-8s %3d  %s" % (st, v, k))
+    lds = lds_breakdown(histogram.hot_lines)
+    for st, d in lds.items():
+        report["stages"][st]["lds_by_kind"] = d
+    if args.lds:
+        print("%-9s " % "stage" + " ".join("%22s" % c for c in LDS_KINDS))
+        for st, d in lds.items():
+            print("%-9s " % st + " ".join("%22d" % d[c] for c in LDS_KINDS))
+        for t in lds.get("B", {}).get("parameter_reads", []):
+            print("  B parameter read  %s" % t)
     if args.dump:
         want = set(args.dump.split(","))
         for st, cls, text in histogram.hot_lines:
