@@ -759,6 +759,80 @@ int sart_trace_histogram_shells(sart_context* ctx, const sart_trace_params_t* pa
 int sart_finalize_shells_device(sart_context* ctx, const sart_trace_params_t* params, const void* shells_fixed_device,
                                 double* out_f64_device);
 
+/* ---- emission-channel breakdown of the histogram trace -------------------------- */
+/*
+ * The solar emission table is a sum of terms (include/sart_emission.h: SART_EM_*; readOpacityFile.nim:849) that scale with
+ * different couplings.  A ray drawn at (radius index r, energy index e) stands for the probability mass of that cell of the TOTAL
+ * table (raytracer.nim:2670-2705, draws :425-471); the share of its weight that belongs to channel t is rates_t[r][e] / total[r][e].
+ * These entry points are sart_trace_histogram_device plus, per channel t < T <= SART_MAX_CHANNELS, the flux, its sum of squares, the
+ * energy spectrum and the focal-plane image of c_t = w f_t - from ONE trace, with common random numbers across the channels.
+ *
+ * Channels of a context (they belong to its solar tables: sart_set_solar_tables* and sart_emission_to_solar_tables* drop them):
+ *   sart_set_source_channels[_device]   channel_rates [T][n_radii][n_energies] (row-major: the layout of sart_emission_table's
+ *                       components_out) and total_rates [n_radii][n_energies], HOST or DEVICE pointers.  Blocking, copies: the caller
+ *                       keeps its memory.  Both forms run the same device kernel (identical bits), which writes the library's table
+ *                         frac[(r n_energies + e) stride + t] = rates_t[r][e] / total[r][e]     (IEEE f64 division; 0 where total == 0:
+ *                                                                                               such a cell has no CDF mass)
+ *                       stride = T rounded up to 1, 2, 4 or 8, padding 0: a ray's fractions are one aligned run of <= 64 bytes.  A
+ *                       fraction in (1, 1 + 2^-49] is stored as 1 (two summation orders of <= 8 non-negative addends differ by less).
+ *                       SART_ERR_INVALID_ARGUMENT, naming the first offending cell, context unchanged: T outside [1, 8], a NULL
+ *                       pointer, a negative or non-finite rate, a fraction above 1 + 2^-49 (a component that is not part of the
+ *                       total), n_radii / n_energies other than those of the context's solar tables.  SART_ERR_NOT_READY before
+ *                       solar tables are set.
+ *   sart_get_source_channels            host copy of the fractions as [T][n_radii][n_energies] and T (either may be NULL)
+ *   sart_clear_source_channels
+ *
+ * Tracing:
+ *   accumulator_device  exactly what sart_trace_histogram_device accumulates for the same params (image, scalars, spectra, flux-only
+ *                       launches): the contract of the per-shell entry - bit for bit in SART_ACCUM_FIXED64 against the generic kernel
+ *                       variants, ~1e-12 with equal counters against the solar-source specialisations, up to the summation order in f64
+ *   channels_device     a flat array of sart_channel_block_len(T, n_energies, spectra, nx, ny) 8-byte slots (f64, or raw int64 in
+ *                       FIXED64; ranks reduce it as it is):
+ *                         1. T rows of SART_CHAN_ROW slots: SART_CHAN_SUM_WEIGHTS, _SUM_WEIGHTS_SQ, _N_CONTRIBUTING (passed rays with
+ *                            f_t > 0), _SUM_WEIGHTS_OUTSIDE (rays that miss the image; every ray of a flux-only launch), and in raw
+ *                            FIXED64 the high limbs _SUM_WEIGHTS_HI, _SUM_WEIGHTS_SQ_HI, _SUM_WEIGHTS_OUTSIDE_HI: value = (hi 2^40 + lo)
+ *                            quantum; slot 6 is reserved (0)
+ *                         2. with params->spectra: energy_weights[T][n_energies + 1], in the bins of the accumulator's energy spectrum
+ *                         3. with image_nx > 0: T images [ny][nx], in the accumulator's image binning
+ * Per passed ray and channel, c_t = w f_t is ONE f64 product; in FIXED64 it is rounded to the accumulator's weight quantum (c_t^2
+ * to the quantum of the squared weights).  The same c_t goes to the row, the ray's energy bin and its pixel (or _OUTSIDE); channels
+ * with c_t == 0 issue no atomics.  Hence, in FIXED64 and exactly as integers, per channel: pixels + outside = energy bins =
+ * SUM_WEIGHTS (checked by sart_finalize_channels_device).  ACROSS channels the sums are not exact: sum_t c_t rounds T times where
+ * the global sum rounds once, so |sum_t SUM_WEIGHTS_t - SUM_WEIGHTS| <= N_PASSED (T + 1) / 2 quanta when sum_t f_t = 1.
+ * Quanta: the accumulator's, frozen in the same way; params->accumulate applies to both buffers.
+ * SART_ERR_INVALID_ARGUMENT, context unchanged: the X-ray test source is active (no solar sampling), a NULL pointer, an invalid image
+ * or spectra specification.  SART_ERR_NOT_READY without channels.
+ * Cost: the generic histogram variants plus, per passed ray, one gather of <= 64 bytes from the fraction table (n_radii n_energies
+ * stride doubles: 189 MB at 1968 x 1500 x 8, Infinity-Cache resident) and per channel three LDS atomics and up to two global atomics
+ * (DESIGN.md 3.2d).
+ */
+#define SART_MAX_CHANNELS 8
+enum { SART_CHAN_SUM_WEIGHTS = 0, SART_CHAN_SUM_WEIGHTS_SQ = 1, SART_CHAN_N_CONTRIBUTING = 2, SART_CHAN_SUM_WEIGHTS_OUTSIDE = 3,
+       SART_CHAN_SUM_WEIGHTS_HI = 4, SART_CHAN_SUM_WEIGHTS_SQ_HI = 5, SART_CHAN_RESERVED = 6, SART_CHAN_SUM_WEIGHTS_OUTSIDE_HI = 7,
+       SART_CHAN_ROW = 8 };
+/* HOST pointers. */
+int sart_set_source_channels(sart_context* ctx, const double* channel_rates, const double* total_rates, int32_t n_channels,
+                             int32_t n_radii, int32_t n_energies);
+/* DEVICE pointers (e.g. components_dev / em_rates_dev of sart_emission_table_device). */
+int sart_set_source_channels_device(sart_context* ctx, const double* channel_rates_device, const double* total_rates_device,
+                                    int32_t n_channels, int32_t n_radii, int32_t n_energies);
+int sart_get_source_channels(sart_context* ctx, double* fractions_out, int32_t* n_channels_out);
+int sart_clear_source_channels(sart_context* ctx);
+/* 8-byte slots of a channel block: T SART_CHAN_ROW + (spectra ? T (n_energies + 1) : 0) + T nx ny. */
+size_t sart_channel_block_len(int32_t n_channels, int32_t n_energies, int32_t spectra, int32_t nx, int32_t ny);
+/* DEVICE memory; asynchronous on the context's stream. */
+int sart_trace_histogram_channels_device(sart_context* ctx, const sart_trace_params_t* params, double* accumulator_device,
+                                         double* channels_device);
+/* Blocking form with HOST outputs (each may be NULL), finalized in FIXED64 mode.  Starts from zero: params->accumulate is not read. */
+int sart_trace_histogram_channels(sart_context* ctx, const sart_trace_params_t* params, double* image_out_host, sart_summary_t* summary_out,
+                                  double* spectra_out_host, double* channels_out_host);
+/* Raw FIXED64 block -> doubles with the context's frozen quanta (device pointers; in place allowed); asynchronous.  Checks, surfacing as
+ * SART_ERR_ACCUMULATOR from the next sart_synchronize: a slot negative or >= 2^62; per channel, pixels + outside and (with spectra)
+ * the energy bins must equal SUM_WEIGHTS exactly.  No resolution check: a faint channel (weights averaging few quanta) is no error -
+ * every c_t is exact to half a quantum of the TOTAL weight, SUM_WEIGHTS_SQ to N_CONTRIBUTING / 2 quanta of the squared weights. */
+int sart_finalize_channels_device(sart_context* ctx, const sart_trace_params_t* params, const void* channels_fixed_device,
+                                  double* out_f64_device);
+
 /* ---- multi-GPU ---------------------------------------------------------- */
 /*
  * Sum the fused accumulators of n contexts (one per GPU of this process) into the one of contexts[root]:

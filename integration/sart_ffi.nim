@@ -182,6 +182,24 @@ proc sart_trace_histogram_shells*(ctx: ptr SartContext, p: ptr SartTraceParams, 
                                   spectraOutHost: ptr cdouble, shellsOutHost: ptr cdouble): cint {.importc, header: sartH.}
 proc sart_finalize_shells_device*(ctx: ptr SartContext, p: ptr SartTraceParams, shellsFixedDevice: pointer,
                                   outF64Device: ptr cdouble): cint {.importc, header: sartH.}
+## emission-channel breakdown of the histogram trace: per channel t < T <= 8 of the context's fraction table (rates_t / total per
+## (radius, energy) cell) the flux, its sum of squares, the energy spectrum and the image of w f_t, from the one trace.  The block:
+## T rows of 8 slots (sum c, sum c^2, N_CONTRIBUTING, sum c outside the image, their FIXED64 high limbs in slots 4, 5, 7), with spectra
+## [T][nEnergies + 1] energy weights, with an image T images [ny][nx]
+const SartMaxChannels* = 8
+proc sart_set_source_channels*(ctx: ptr SartContext, channelRates: ptr cdouble, totalRates: ptr cdouble, nChannels, nRadii,
+                               nEnergies: int32): cint {.importc, header: sartH.}
+proc sart_set_source_channels_device*(ctx: ptr SartContext, channelRatesDevice: ptr cdouble, totalRatesDevice: ptr cdouble, nChannels,
+                                      nRadii, nEnergies: int32): cint {.importc, header: sartH.}
+proc sart_get_source_channels*(ctx: ptr SartContext, fractionsOut: ptr cdouble, nChannelsOut: ptr int32): cint {.importc, header: sartH.}
+proc sart_clear_source_channels*(ctx: ptr SartContext): cint {.importc, header: sartH.}
+proc sart_channel_block_len*(nChannels, nEnergies, spectra, nx, ny: int32): csize_t {.importc, header: sartH.}
+proc sart_trace_histogram_channels_device*(ctx: ptr SartContext, p: ptr SartTraceParams, accumulatorDevice: ptr cdouble,
+                                           channelsDevice: ptr cdouble): cint {.importc, header: sartH.}
+proc sart_trace_histogram_channels*(ctx: ptr SartContext, p: ptr SartTraceParams, imageOutHost: ptr cdouble, summaryOut: ptr SartSummary,
+                                    spectraOutHost: ptr cdouble, channelsOutHost: ptr cdouble): cint {.importc, header: sartH.}
+proc sart_finalize_channels_device*(ctx: ptr SartContext, p: ptr SartTraceParams, channelsFixedDevice: pointer,
+                                    outF64Device: ptr cdouble): cint {.importc, header: sartH.}
 proc sart_reduce_across_devices*(contexts: ptr ptr SartContext, accumulatorsDevice: ptr ptr cdouble, n: int32, nDoubles: csize_t,
                                  root: int32): cint {.importc, header: sartH.}
 proc sart_enable_kernel_timing*(ctx: ptr SartContext, enable: cint): cint {.importc, header: sartH.}

@@ -7,6 +7,7 @@
         [--massScanMin M0 --massScanMax M1 --numMassScanPoints K]     (not in the reference: see below)
         [--energyScanMin E0 --energyScanMax E1 --numEnergyScanPoints K]  (not in the reference: see below)
         [--shellBreakdown]                                               (not in the reference: see below)
+        [--emissionChannels {terms,couplings}]                           (not in the reference: see below)
         [--events PATH.npz [--eventColumns a,b,c]]                       (not in the reference: see below)
 
 Same switches, same two modes (full run = calculateFluxFractions, :2755-2776; angular scan, :2778-2815).  What differs:
@@ -23,6 +24,11 @@ llnl_xray_telescope_cast_effective_area_parallel_light_DTU_thesis.csv).  It cann
 --shellBreakdown (full-run mode only) also breaks the result down by mirror shell (Axion.shellNumber, :218; the data of
 generateResultPlots' dfDet "Shell" column and energies_by_shell plot, :2351-2376) and writes `shell_breakdown_{year}.csv` and
 `energies_by_shell_{year}.csv` beside the image CSV.
+--emissionChannels terms|couplings (full-run mode only) also breaks the result down by the process that emitted the axion: the eight
+terms of the solar emission table (readOpacityFile.nim:849) or their sums per coupling (g_ae, g_agamma, g_anuclei), from the one trace.
+The run's emission table becomes the all-terms AGSS09 table made on the GPU (the only one whose components are known: it cannot be
+combined with --xrayTest or a solar-model CSV, nor with --shellBreakdown: one breakdown per run).  Writes `flux_by_channel_{year}.csv`, `energies_by_channel_{year}.csv` and one
+`axion_image_{year}_{name}.csv` per channel.
 --events PATH.npz (full-run mode only) also writes the passed rays themselves, as columns in ray order (the `axionsPass` that
 generateResultPlots plots from, :2253-2289): one array per name of --eventColumns (default pointdataX, pointdataY, pointdataR,
 energiesAx, weights, shellNumber, ray_id; any field of the Axion record, `flags`, `kinds_packed`, `ray_id`) and the four counts
@@ -37,7 +43,7 @@ import numpy as np
 
 from . import _lib, config as cfgmod
 from .raytracer import (RayTracer, angle_image_names, containment_radii, initFullSetup, performAngularScan, performAxionMassScan,
-                        performEnergyScan, write_image_csv, write_shell_csvs)
+                        performEnergyScan, write_channel_csvs, write_image_csv, write_shell_csvs)
 
 WINDOW_YEAR = {_lib.DK_INGRID2017: "2017", _lib.DK_INGRID2018: "2018", _lib.DK_INGRIDIAXO: "IAXO"}   # WindowYearKind, :1468-1484
 
@@ -70,6 +76,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--numEnergyScanPoints", type=int, default=32)
     ap.add_argument("--shellBreakdown", action="store_true",
                     help="extension (full-run mode): the result per mirror shell, shell_breakdown_{year}.csv and energies_by_shell_{year}.csv")
+    ap.add_argument("--emissionChannels", choices=("terms", "couplings"), default=None,
+                    help="extension (full-run mode): the result per emission process (terms) or per coupling (couplings) from the one "
+                         "trace; switches the emission table to the all-terms AGSS09 table made on the GPU")
     ap.add_argument("--events", default="", metavar="PATH.npz",
                     help="extension (full-run mode): the passed rays as columns, in ray order, and the four counts, as a numpy .npz")
     ap.add_argument("--eventColumns", default=",".join(EVENT_COLUMNS), help="comma-separated columns of --events (default: %(default)s)")
@@ -99,12 +108,32 @@ def check_scan_args(ap: argparse.ArgumentParser, args) -> None:
     if getattr(args, "shellBreakdown", False) and (energy_scan_requested(args) or args.massScanMax > args.massScanMin
                                                    or args.angularScanMin != args.angularScanMax):
         ap.error("--shellBreakdown belongs to the full run: it cannot be combined with a mass, angular or energy scan")
+    if getattr(args, "emissionChannels", None):
+        if energy_scan_requested(args) or args.massScanMax > args.massScanMin or args.angularScanMin != args.angularScanMax:
+            ap.error("--emissionChannels belongs to the full run: it cannot be combined with a mass, angular or energy scan")
+        if args.xrayTest:
+            ap.error("--emissionChannels needs the solar source: it cannot be combined with --xrayTest")
+        if getattr(args, "shellBreakdown", False):
+            ap.error("--emissionChannels cannot be combined with --shellBreakdown (one breakdown per run)")
     if not energy_scan_requested(args):
         return
     if args.massScanMax > args.massScanMin or args.angularScanMin != args.angularScanMax:
         ap.error("--energyScanMin / --energyScanMax cannot be combined with a mass scan or an angular scan")
     if not (0.0 < args.energyScanMin < args.energyScanMax) or args.numEnergyScanPoints < 1:
         ap.error("the energy scan needs 0 < --energyScanMin < --energyScanMax (keV) and --numEnergyScanPoints >= 1")
+
+
+def config_path_of(args) -> str:
+    return args.config or (os.path.join(args.configPath, "config.toml") if args.configPath else "")
+
+
+def check_channels_config(ap: argparse.ArgumentParser, args) -> None:
+    """--emissionChannels beside a config whose solar-model CSV exists: exit 2 before anything is built (a CSV has no components)."""
+    path = config_path_of(args)
+    if getattr(args, "emissionChannels", None) and path:
+        csv = cfgmod.solar_model_csv_of(path)
+        if csv:
+            ap.error("--emissionChannels cannot be combined with a solar-model CSV (%s): its components are not known" % csv)
 
 
 def event_columns(args) -> list:
@@ -114,10 +143,11 @@ def event_columns(args) -> list:
 def setup_from_args(args):
     flags = cfgmod.flags_from_cli(args.ignoreDetWindow, args.ignoreGasAbs, args.ignoreConvProb, args.ignoreReflection,
                                   args.xrayTest, args.detectorInstall, args.magnet)
-    path = args.config or (os.path.join(args.configPath, "config.toml") if args.configPath else "")
+    path = config_path_of(args)
+    over = {"emission": "agss09"} if getattr(args, "emissionChannels", None) else {}
     if path:
-        return cfgmod.init_full_setup_from_config(path, flags), flags
-    return initFullSetup(flags=flags), flags
+        return cfgmod.init_full_setup_from_config(path, flags, **over), flags
+    return initFullSetup(flags=flags, **over), flags
 
 
 def write_result(path, img, s, spec, chip_max):
@@ -138,9 +168,17 @@ def main(argv=None) -> int:
     ap = build_parser()
     args = ap.parse_args(argv)
     check_scan_args(ap, args)
+    check_channels_config(ap, args)
     full, flags = setup_from_args(args)
     if energy_scan_requested(args) and not full.setup.test_active:
         ap.error("the energy scan needs the X-ray test source: --xrayTest, or [TestXraySource] active in the config")
+    if args.emissionChannels:
+        if full.setup.test_active:
+            ap.error("--emissionChannels needs the solar source: the config's X-ray test source is active")
+        if full.meta.get("emission") != "E0-agss09-all-terms-gpu":
+            ap.error("--emissionChannels cannot be combined with a solar-model CSV (%s): its components are not known"
+                     % full.meta.get("emission"))
+        print("--emissionChannels: the emission table of this run is the all-terms AGSS09 table made on the GPU")
     n = int(args.rays)
     os.makedirs(args.outpath, exist_ok=True)
     print("Flags:", [name for name, bit in (("cfIgnoreDetWindow", _lib.CF_IGNORE_DET_WINDOW), ("cfIgnoreGasAbs", _lib.CF_IGNORE_GAS_ABS),
@@ -176,11 +214,18 @@ def main(argv=None) -> int:
             year = WINDOW_YEAR.get(full.setup.detector_kind, "IAXO")
             if args.shellBreakdown:
                 img, s, spec, shells = rt.trace_shells(n, seed=args.seed, flags=flags)
+            elif args.emissionChannels:
+                rt.set_emission_channels(args.emissionChannels)
+                img, s, spec, chans = rt.trace_channels(n, seed=args.seed, flags=flags)
             else:
                 img, s, spec = rt.trace_spectra(n, seed=args.seed, flags=flags)
             write_result(os.path.join(args.outpath, "axion_image_%s.csv" % year), img, s, spec, full.setup.chip_x_max)
             if args.shellBreakdown:
                 for path in write_shell_csvs(args.outpath, year, shells, full.energies, s["N_RAYS"]):
+                    print("wrote", path)
+            if args.emissionChannels:
+                r1w, r2w = containment_radii(spec)[2:]
+                for path in write_channel_csvs(args.outpath, year, chans, full.energies, full.setup.chip_x_max, r1w, r2w):
                     print("wrote", path)
             if args.events:
                 cols, counts = rt.trace_columns(n, event_columns(args), seed=args.seed, flags=flags)

@@ -59,6 +59,13 @@ FIXED_LIMB_BITS = 40
 SHELL_ROW = 8
 SHELL = dict(N_SELECTED=0, N_HIT_NICKEL=1, N_PASSED_TILL_WINDOW=2, N_PASSED=3, SUM_WEIGHTS=4, SUM_WEIGHTS_SQ=5)
 SHELL_HI = dict(SUM_WEIGHTS=6, SUM_WEIGHTS_SQ=7)
+# emission-channel breakdown (include/sart.h: SART_CHAN_*): T rows of CHAN_ROW slots, then (spectra) energy_weights[T][n_energies + 1],
+# then (image) T images [ny][nx]
+MAX_CHANNELS = 8
+CHAN_ROW = 8
+CHAN = dict(SUM_WEIGHTS=0, SUM_WEIGHTS_SQ=1, N_CONTRIBUTING=2, SUM_WEIGHTS_OUTSIDE=3)
+CHAN_HI = dict(SUM_WEIGHTS=4, SUM_WEIGHTS_SQ=5, SUM_WEIGHTS_OUTSIDE=7)
+CHAN_RESERVED = 6
 
 
 def energy_scan_len(n_energies: int) -> int:
@@ -84,6 +91,32 @@ def split_shells(block, n_shells: int, n_energies: int, spectra: bool) -> dict:
         ne1 = int(n_energies) + 1
         tail = block[n_shells * SHELL_ROW:].reshape(2, n_shells, ne1)
         out["energy_counts"], out["energy_weights"] = tail[0].copy(), tail[1].copy()
+    return out
+
+
+def channel_block_len(n_channels: int, n_energies: int, spectra: bool, nx: int, ny: int) -> int:
+    """sart_channel_block_len: 8-byte slots of an emission-channel block."""
+    t, n_energies = max(int(n_channels), 0), max(int(n_energies), 0)
+    n_img = int(nx) * int(ny) if nx > 0 and ny > 0 else 0
+    return t * CHAN_ROW + (t * (n_energies + 1) if spectra else 0) + t * n_img
+
+
+def split_channels(block, n_channels: int, n_energies: int, spectra: bool, nx: int, ny: int) -> dict:
+    """Dict of per-channel arrays (keys of CHAN) from a finalized channel block; with ``spectra`` also ``energy_weights``
+    [T][n_energies + 1], with an image ``images`` [T][ny][nx]."""
+    import numpy as np
+    block = np.asarray(block, dtype=np.float64)
+    t = int(n_channels)
+    assert block.size == channel_block_len(t, n_energies, spectra, nx, ny)
+    rows = block[:t * CHAN_ROW].reshape(t, CHAN_ROW)
+    out = {k: rows[:, i].copy() for k, i in CHAN.items()}
+    o = t * CHAN_ROW
+    if spectra:
+        ne1 = int(n_energies) + 1
+        out["energy_weights"] = block[o:o + t * ne1].reshape(t, ne1).copy()
+        o += t * ne1
+    if nx > 0 and ny > 0:
+        out["images"] = block[o:].reshape(t, int(ny), int(nx)).copy()
     return out
 
 
@@ -298,6 +331,14 @@ SART_SYMBOLS = {
     "sart_trace_histogram_shells_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p, C.c_void_p]),
     "sart_trace_histogram_shells": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _P(Summary), _dp, _dp]),
     "sart_finalize_shells_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p, C.c_void_p]),
+    "sart_set_source_channels": (C.c_int, [C.c_void_p, _dp, _dp, _i, _i, _i]),
+    "sart_set_source_channels_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _i, _i, _i]),
+    "sart_get_source_channels": (C.c_int, [C.c_void_p, _dp, _P(C.c_int32)]),
+    "sart_clear_source_channels": (C.c_int, [C.c_void_p]),
+    "sart_channel_block_len": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "sart_trace_histogram_channels_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p, C.c_void_p]),
+    "sart_trace_histogram_channels": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _P(Summary), _dp, _dp]),
+    "sart_finalize_channels_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p, C.c_void_p]),
     "sart_reduce_across_devices": (C.c_int, [_P(C.c_void_p), _P(C.c_void_p), _i, C.c_size_t, _i]),
     "sart_enable_kernel_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "sart_get_kernel_timing": (C.c_int, [C.c_void_p, _dp, _P(C.c_int64)]),

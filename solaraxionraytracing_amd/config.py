@@ -105,6 +105,15 @@ def resolve_opcd_path(cfg: dict, base: str):
     return os.path.normpath(os.path.join(base, p))
 
 
+def solar_model_csv_of(config_path: str):
+    """The solar-model CSV a config.toml makes init_full_setup_from_config read (resourcePath / solarModelFile), or None where that
+    file does not exist and the emission table is made here."""
+    cfg = load_config(config_path)
+    rdir = resolve_resources(cfg, os.path.dirname(os.path.abspath(config_path)))["resourcePath"]
+    solar = os.path.join(rdir, cfg.get("Resources", {}).get("solarModelFile", "solar_model_dataframe.csv"))
+    return solar if os.path.exists(solar) else None
+
+
 def load_config(path: str) -> dict:
     import tomli
     with open(path, "rb") as f:

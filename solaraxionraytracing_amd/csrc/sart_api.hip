@@ -51,6 +51,13 @@ void launch_shell_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, 
                             int n_blocks, hipStream_t stream, bool rotated, bool fixed);
 void launch_finalize_shells(const void* in, double* out, int n_shells, int n_energies1, int spectra, double q_w, double q_w2,
                             void* check_dev, hipStream_t stream);
+int channel_histogram_blocks_per_cu(bool rotated);
+void launch_channel_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, double* acc, const ChannelArgs& CH,
+                              int n_blocks, hipStream_t stream, bool rotated, bool fixed);
+void launch_finalize_channels(const void* in, double* out, int n_channels, int n_energies1, int spectra, size_t n_img, double q_w,
+                              double q_w2, void* check_dev, hipStream_t stream);
+void launch_channel_fractions(const double* rates_dev, const double* total_dev, double* frac_dev, int n_channels, int stride,
+                              size_t n_cells, unsigned long long* first_bad_dev, hipStream_t stream);
 int histogram_block_of(int variant);
 void launch_trace_records(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, sart_axion_t* out, int n_blocks,
                           hipStream_t stream, const double* uniforms_dev);
@@ -293,6 +300,12 @@ struct sart_context {
   // per-shell breakdown: per-workgroup shell tables; scratch accumulator / block of the blocking form and their f64 images
   DevBuf<double> d_shell_partials, d_sacc, d_sacc_fin, d_sblock, d_sblock_fin;
   int blocks_per_cu_shells[2] = {0, 0};
+  // emission-channel breakdown: the fraction table [n_radii][n_energies][chan_stride] of the current solar tables (dropped with them),
+  // per-workgroup channel tables; scratch block of the blocking form and its f64 image (the accumulator's scratch is the shells')
+  bool have_channels = false;
+  int n_channels = 0, chan_stride = 0;
+  DevBuf<double> d_chan_frac, d_chan_partials, d_cblock, d_cblock_fin;
+  int blocks_per_cu_channels[2] = {0, 0};
 
   // timing
   bool timing = false;
@@ -1261,6 +1274,7 @@ int sart_set_solar_tables(sart_context* c, const double* rcdf, const double* ecd
   c->n_radii = nR;
   c->n_energies = nE;
   c->have_solar = true;
+  c->have_channels = false;   // they belonged to the old table
   c->derived_dirty = true;
   return 0;
 }
@@ -1286,6 +1300,7 @@ int sart_set_solar_tables_device(sart_context* c, const double* em_rates_dev, co
   if (int rc = c->d_eguide.resize(static_cast<size_t>(nR) * kEnergyGuideEntries)) return rc;
   if (int rc = c->d_ecdf_hi32.resize(static_cast<size_t>(nR) * (static_cast<size_t>(nE) + kEnergyCdfPad))) return rc;
   c->have_solar = false;                       // until the new tables are known to be CDFs
+  c->have_channels = false;                    // they belonged to the old table
   launch_build_solar_tables(em_rates_dev, d_radii.p, d_energies.p, nR, nE, c->d_ecdf.p, d_row_sum.p, c->d_rcdf.p, c->d_rguide.p,
                             c->d_eguide.p, d_status.p, c->stream);
   launch_cdf_hi32(c->d_ecdf.p, c->d_ecdf_hi32.p, c->d_ecdf_hi32.n, c->stream);
@@ -1818,8 +1833,13 @@ size_t shell_block_len_of(const sart_context* c, const sart_trace_params_t* p) {
 }
 
 // sart_trace_histogram_device, and with `shells_dev` sart_trace_histogram_shells_device: the same host path (quanta, replicas, LDS
-// tile, partials) around trace_histogram_kernel or shell_histogram_kernel.
-int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_dev, double* shells_dev) {
+// tile, partials) around trace_histogram_kernel or shell_histogram_kernel; with `chan_dev` sart_trace_histogram_channels_device,
+// around channel_histogram_kernel.
+size_t channel_block_len_of(const sart_context* c, const sart_trace_params_t* p) {
+  return sart_channel_block_len(c->n_channels, c->n_energies, p->spectra, p->image_nx, p->image_ny);
+}
+
+int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_dev, double* shells_dev, double* chan_dev = nullptr) {
   SART_HIP(hipSetDevice(c->device));
   if (int rc = refresh_derived(c)) return rc;
   if (int rc = sync_blob(c)) return rc;
@@ -1835,6 +1855,7 @@ int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_
   }
   if (!p->accumulate) SART_HIP(hipMemsetAsync(acc_dev, 0, acc_len_of(c, p) * sizeof(double), c->stream));
   if (shells_dev && !p->accumulate) SART_HIP(hipMemsetAsync(shells_dev, 0, shell_block_len_of(c, p) * sizeof(double), c->stream));
+  if (chan_dev && !p->accumulate) SART_HIP(hipMemsetAsync(chan_dev, 0, channel_block_len_of(c, p) * sizeof(double), c->stream));
   if (a.n_rays == 0) return 0;
   if (a.n_rays > (1ull << 31)) {   // ray indices inside one launch are 32-bit (stage A0 ring): split
     sart_trace_params_t q = *p;
@@ -1843,7 +1864,7 @@ int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_
       const uint64_t n = std::min<uint64_t>(p->n_rays - done, 1ull << 31);
       q.n_rays = n;
       q.ray_id_offset = p->ray_id_offset + done;
-      if (int rc = histogram_launch(c, &q, acc_dev, shells_dev)) return rc;
+      if (int rc = histogram_launch(c, &q, acc_dev, shells_dev, chan_dev)) return rc;
       done += n;
     }
     return 0;
@@ -1939,6 +1960,12 @@ int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_
           a.tile_x0 = t.x0 + (t.n - n) / 2; a.tile_y0 = t.y0 + (t.n - n) / 2; a.tile_n = n;
           a.tile_base = free_s ? 0 : kTileRingCells;
         }
+        if (chan_dev) {   // the channel kernel keeps its channel table there: the same narrowing
+          const bool free_s = c->hot.n_zones == 0;
+          const int n = std::min(t.n, free_s ? kChanImageTileMax : kChanImageTileExtraMax);
+          a.tile_x0 = t.x0 + (t.n - n) / 2; a.tile_y0 = t.y0 + (t.n - n) / 2; a.tile_n = n;
+          a.tile_base = free_s ? 0 : kTileRingCells;
+        }
       }
     } else {
       a.replicas = acc_dev;
@@ -1971,6 +1998,40 @@ int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_
     {
       TimedLaunch tl(c);
       launch_shell_histogram(c->hot, c->hotb, c->d_blob.p, a, acc_dev, sh, n_blocks, c->stream, rotated, fixed);
+    }
+    SART_HIP(hipGetLastError());
+    return 0;
+  }
+  if (chan_dev) {
+    const bool rotated = c->params.rotated != 0;   // generic variants: hist_variant_of 1 / 2
+    if (c->blocks_per_cu_channels[rotated] == 0) {
+      c->blocks_per_cu_channels[rotated] = std::max(1, channel_histogram_blocks_per_cu(rotated));
+      if (c->knobs.hist_blocks_per_cu > 0) c->blocks_per_cu_channels[rotated] = c->knobs.hist_blocks_per_cu;
+    }
+    const int n_blocks = grid_for(a.n_rays, c->n_cu, c->blocks_per_cu_channels[rotated], 1024);
+    const size_t rows = std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4);
+    if (c->d_partials.n < static_cast<size_t>(n_blocks) * SART_ACC_COUNT) {
+      SART_HIP(hipStreamSynchronize(c->stream));
+      if (int rc = c->d_partials.resize(rows * SART_ACC_COUNT)) return rc;
+    }
+    if (c->d_chan_partials.n < static_cast<size_t>(n_blocks) * kMaxChannels * kChanPartialSlots) {
+      SART_HIP(hipStreamSynchronize(c->stream));
+      if (int rc = c->d_chan_partials.resize(rows * kMaxChannels * kChanPartialSlots)) return rc;
+    }
+    a.partials = c->d_partials.p;
+    ChannelArgs ch;
+    std::memset(&ch, 0, sizeof ch);
+    ch.block = chan_dev;
+    ch.partials = c->d_chan_partials.p;
+    ch.frac = c->d_chan_frac.p;
+    ch.n_channels = c->n_channels;
+    ch.stride = c->chan_stride;
+    ch.n_radii = c->n_radii;
+    ch.n_energies = c->n_energies;
+    ch.n_energies1 = c->n_energies + 1;
+    {
+      TimedLaunch tl(c);
+      launch_channel_histogram(c->hot, c->hotb, c->d_blob.p, a, acc_dev, ch, n_blocks, c->stream, rotated, fixed);
     }
     SART_HIP(hipGetLastError());
     return 0;
@@ -2063,6 +2124,166 @@ int sart_trace_histogram_shells(sart_context* c, const sart_trace_params_t* p, d
     SART_HIP(hipMemcpyAsync(spectra_out, src + nimg + SART_ACC_COUNT, (len - nimg - SART_ACC_COUNT) * sizeof(double),
                             hipMemcpyDeviceToHost, c->stream));
   if (shells_out) SART_HIP(hipMemcpyAsync(shells_out, ssrc, slen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  SART_HIP(hipStreamSynchronize(c->stream));
+  return status_take(c);
+}
+
+// ---- emission-channel breakdown (include/sart.h) --------------------------------------------
+namespace {
+
+// channel_fractions_kernel on device-resident rates: the one path of both set forms.  The new table replaces the context's only
+// when every cell passed.
+int set_channels_from_device(sart_context* c, const double* rates_dev, const double* total_dev, int32_t T, int32_t nR, int32_t nE) {
+  const int stride = T <= 1 ? 1 : T <= 2 ? 2 : T <= 4 ? 4 : 8;
+  const size_t n_cells = static_cast<size_t>(nR) * static_cast<size_t>(nE);
+  if (n_cells * static_cast<size_t>(stride) * sizeof(double) > 0xFFFFFFFFull)
+    return fail(SART_ERR_INVALID_ARGUMENT, "fraction table of 4 GB or more (the kernel's gather offsets are 32-bit)");
+  DevBuf<double> frac;
+  DevBuf<unsigned long long> bad;
+  if (int rc = frac.resize(n_cells * stride)) return rc;
+  if (int rc = bad.resize(1)) return rc;
+  launch_channel_fractions(rates_dev, total_dev, frac.p, T, stride, n_cells, bad.p, c->stream);
+  SART_HIP(hipGetLastError());
+  unsigned long long first = ~0ull;
+  SART_HIP(hipMemcpyAsync(&first, bad.p, sizeof first, hipMemcpyDeviceToHost, c->stream));
+  SART_HIP(hipStreamSynchronize(c->stream));
+  if (first != ~0ull) {
+    const unsigned code = static_cast<unsigned>(first & 3ull);
+    const unsigned long long cell = first >> 5, t = (first >> 2) & 7ull;
+    const std::string where = "radius index " + std::to_string(cell / static_cast<unsigned long long>(nE)) + ", energy index " +
+                              std::to_string(cell % static_cast<unsigned long long>(nE));
+    if (code == 3) return fail(SART_ERR_INVALID_ARGUMENT, "total_rates: negative or non-finite rate at " + where);
+    if (code == 1)
+      return fail(SART_ERR_INVALID_ARGUMENT, "channel_rates: negative or non-finite rate of channel " + std::to_string(t) + " at " + where);
+    return fail(SART_ERR_INVALID_ARGUMENT, "channel_rates: channel " + std::to_string(t) + " exceeds the total at " + where +
+                                               " (fraction above 1 + 2^-49: a component that is not part of the total?)");
+  }
+  std::swap(c->d_chan_frac.p, frac.p);   // (the stream is idle: nothing reads the old table, which `frac` frees)
+  std::swap(c->d_chan_frac.n, frac.n);
+  c->n_channels = T;
+  c->chan_stride = stride;
+  c->have_channels = true;
+  return 0;
+}
+
+int channels_args_check(sart_context* c, const double* rates, const double* total, int32_t T, int32_t nR, int32_t nE) {
+  if (!c || !rates || !total) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (T < 1 || T > SART_MAX_CHANNELS) return fail(SART_ERR_INVALID_ARGUMENT, "n_channels must be in [1, 8]");
+  if (!c->have_solar) return fail(SART_ERR_NOT_READY, "no solar tables");
+  if (nR != c->n_radii || nE != c->n_energies)
+    return fail(SART_ERR_INVALID_ARGUMENT, "n_radii / n_energies are not those of the context's solar tables (" +
+                                               std::to_string(c->n_radii) + " x " + std::to_string(c->n_energies) + ")");
+  return 0;
+}
+
+// params that a channel launch and its finalize accept (the context stays as it is otherwise)
+int channels_check(sart_context* c, const sart_trace_params_t* p) {
+  if (int rc = shells_check(c, p)) return rc;
+  if (c->setup.test_active) return fail(SART_ERR_INVALID_ARGUMENT, "the X-ray test source is active: no solar sampling, no emission channels");
+  if (!c->have_solar || !c->have_channels) return fail(SART_ERR_NOT_READY, "no source channels (sart_set_source_channels)");
+  return 0;
+}
+
+}  // namespace
+
+static_assert(SART_MAX_CHANNELS == kMaxChannels, "include/sart.h and sart_device.h");
+
+int sart_set_source_channels_device(sart_context* c, const double* rates_dev, const double* total_dev, int32_t T, int32_t nR, int32_t nE) {
+  if (int rc = channels_args_check(c, rates_dev, total_dev, T, nR, nE)) return rc;
+  SART_HIP(hipSetDevice(c->device));
+  SART_HIP(hipStreamSynchronize(c->stream));   // launches in flight read the table that is replaced
+  return set_channels_from_device(c, rates_dev, total_dev, T, nR, nE);
+}
+
+int sart_set_source_channels(sart_context* c, const double* rates, const double* total, int32_t T, int32_t nR, int32_t nE) {
+  if (int rc = channels_args_check(c, rates, total, T, nR, nE)) return rc;
+  SART_HIP(hipSetDevice(c->device));
+  SART_HIP(hipStreamSynchronize(c->stream));
+  const size_t n_cells = static_cast<size_t>(nR) * static_cast<size_t>(nE);
+  DevBuf<double> d_rates, d_total;
+  if (int rc = d_rates.upload(rates, n_cells * static_cast<size_t>(T))) return rc;
+  if (int rc = d_total.upload(total, n_cells)) return rc;
+  return set_channels_from_device(c, d_rates.p, d_total.p, T, nR, nE);   // (synchronises: the temporaries outlive the kernel)
+}
+
+int sart_get_source_channels(sart_context* c, double* fractions_out, int32_t* n_channels_out) {
+  if (!c) return fail(SART_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (!c->have_solar || !c->have_channels) return fail(SART_ERR_NOT_READY, "no source channels");
+  if (n_channels_out) *n_channels_out = c->n_channels;
+  if (!fractions_out) return 0;
+  SART_HIP(hipSetDevice(c->device));
+  SART_HIP(hipStreamSynchronize(c->stream));
+  const size_t n_cells = static_cast<size_t>(c->n_radii) * static_cast<size_t>(c->n_energies), stride = static_cast<size_t>(c->chan_stride);
+  std::vector<double> h(n_cells * stride);
+  SART_HIP(hipMemcpy(h.data(), c->d_chan_frac.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (int t = 0; t < c->n_channels; ++t)
+    for (size_t i = 0; i < n_cells; ++i) fractions_out[static_cast<size_t>(t) * n_cells + i] = h[i * stride + static_cast<size_t>(t)];
+  return 0;
+}
+
+int sart_clear_source_channels(sart_context* c) {
+  if (!c) return fail(SART_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  SART_HIP(hipSetDevice(c->device));
+  SART_HIP(hipStreamSynchronize(c->stream));
+  c->have_channels = false;
+  c->n_channels = c->chan_stride = 0;
+  c->d_chan_frac.release();
+  return 0;
+}
+
+size_t sart_channel_block_len(int32_t n_channels, int32_t n_energies, int32_t spectra, int32_t nx, int32_t ny) {
+  const size_t T = n_channels > 0 ? static_cast<size_t>(n_channels) : 0u;
+  const size_t n_img = (nx > 0 && ny > 0) ? static_cast<size_t>(nx) * static_cast<size_t>(ny) : 0u;
+  return T * static_cast<size_t>(SART_CHAN_ROW) + (spectra ? T * (static_cast<size_t>(n_energies > 0 ? n_energies : 0) + 1u) : 0u) + T * n_img;
+}
+
+int sart_trace_histogram_channels_device(sart_context* c, const sart_trace_params_t* p, double* acc_dev, double* chan_dev) {
+  if (!c || !p || !acc_dev || !chan_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (int rc = channels_check(c, p)) return rc;
+  return histogram_launch(c, p, acc_dev, nullptr, chan_dev);
+}
+
+int sart_finalize_channels_device(sart_context* c, const sart_trace_params_t* p, const void* raw_dev, double* out_dev) {
+  if (!c || !p || !raw_dev || !out_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (int rc = channels_check(c, p)) return rc;
+  if (!c->quanta_frozen) return fail(SART_ERR_NOT_READY, "no FIXED64 launch has fixed the quanta yet");
+  SART_HIP(hipSetDevice(c->device));
+  if (int rc = status_ensure(c)) return rc;
+  launch_finalize_channels(raw_dev, out_dev, c->n_channels, c->n_energies + 1, p->spectra ? 1 : 0,
+                           static_cast<size_t>(p->image_nx) * static_cast<size_t>(p->image_ny), std::ldexp(1.0, c->weight_exp),
+                           std::ldexp(1.0, c->weight_sq_exp), c->d_status.p, c->stream);
+  SART_HIP(hipGetLastError());
+  return status_enqueue_copy(c);
+}
+
+int sart_trace_histogram_channels(sart_context* c, const sart_trace_params_t* p, double* image_out, sart_summary_t* summary,
+                                  double* spectra_out, double* channels_out) {
+  if (!c || !p) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (int rc = channels_check(c, p)) return rc;
+  SART_HIP(hipSetDevice(c->device));
+  const size_t len = acc_len_of(c, p), clen = channel_block_len_of(c, p);
+  if (int rc = c->d_sacc.reserve(len)) return rc;
+  if (int rc = c->d_cblock.reserve(clen)) return rc;
+  sart_trace_params_t q = *p;
+  q.accumulate = 0;   // the blocking form has no accumulator the caller could add into
+  if (int rc = histogram_launch(c, &q, c->d_sacc.p, nullptr, c->d_cblock.p)) return rc;
+  const double* src = c->d_sacc.p;
+  const double* csrc = c->d_cblock.p;
+  if (c->accum_mode == SART_ACCUM_FIXED64) {
+    if (int rc = c->d_sacc_fin.reserve(len)) return rc;
+    if (int rc = c->d_cblock_fin.reserve(clen)) return rc;
+    if (int rc = sart_finalize_accumulator_device(c, p, c->d_sacc.p, c->d_sacc_fin.p)) return rc;
+    if (int rc = sart_finalize_channels_device(c, p, c->d_cblock.p, c->d_cblock_fin.p)) return rc;
+    src = c->d_sacc_fin.p;
+    csrc = c->d_cblock_fin.p;
+  }
+  const size_t nimg = static_cast<size_t>(p->image_nx) * p->image_ny;
+  if (image_out && nimg) SART_HIP(hipMemcpyAsync(image_out, src, nimg * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (summary) SART_HIP(hipMemcpyAsync(summary->v, src + nimg, SART_ACC_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (spectra_out && p->spectra)
+    SART_HIP(hipMemcpyAsync(spectra_out, src + nimg + SART_ACC_COUNT, (len - nimg - SART_ACC_COUNT) * sizeof(double),
+                            hipMemcpyDeviceToHost, c->stream));
+  if (channels_out) SART_HIP(hipMemcpyAsync(channels_out, csrc, clen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   SART_HIP(hipStreamSynchronize(c->stream));
   return status_take(c);
 }

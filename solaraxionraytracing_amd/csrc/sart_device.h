@@ -342,4 +342,29 @@ struct ShellArgs {
 };
 static_assert(sizeof(ShellArgs) == 32, "the kernel re-reads ShellArgs with scalar loads");
 
+// Emission-channel breakdown of the histogram trace (include/sart.h: sart_trace_histogram_channels_device).  channel_histogram_kernel
+// keeps, per workgroup and channel, three sums - of c = w f, of c^2, of c outside the image - spread over kChanLanes cells each (lane l
+// adds to cell l % kChanLanes: passed rays of one wave do not all meet in one LDS address) and one u32 counter spread likewise, in the last
+// kChanTableCells cells behind the tables (as the shell table: its image tile is at most kChanImageTileMax / kChanImageTileExtraMax
+// wide), and stores their sums once to partials[n_blocks][kMaxChannels][kChanPartialSlots]; fold_channels_kernel adds those to the
+// caller's block.  Per-channel energy bins and pixels take global atomics.
+constexpr int kMaxChannels = 8;
+constexpr int kChanLanes = 16;
+constexpr int kChanPartialSlots = 4;   // sum of c, sum of c^2, sum of c outside the image, N_CONTRIBUTING
+constexpr int kChanTableCells = kMaxChannels * 3 * kChanLanes + kMaxChannels * kChanLanes / 2;   // the sums and the u32 counters, in 8-byte cells
+constexpr int kChanImageTileMax = 51;        // 51 x 51 <= kTileRingCells + kRingExtraCells - kChanTableCells
+constexpr int kChanImageTileExtraMax = 25;   // 25 x 25 <= kRingExtraCells - kChanTableCells
+static_assert(kChanImageTileMax * kChanImageTileMax <= kTileRingCells + kRingExtraCells - kChanTableCells &&
+                  kChanImageTileExtraMax * kChanImageTileExtraMax <= kRingExtraCells - kChanTableCells,
+              "the channel kernel's image tile leaves the channel table alone");
+struct ChannelArgs {
+  double* block;          // the caller's block: rows of SART_CHAN_ROW slots, then (spectra) energy_weights[T][n_energies1], then T images
+  double* partials;       // [n_blocks][kMaxChannels][kChanPartialSlots] per-workgroup sums and counters (plain stores)
+  const double* frac;     // [n_radii][n_energies][stride]: the fractions of the ray drawn at (r, e), padded with 0
+  int32_t n_channels, stride;       // T in [1, kMaxChannels]; T rounded up to 1, 2, 4 or 8
+  int32_t n_radii, n_energies;      // the table's shape (the gather clamps its indices to it)
+  int32_t n_energies1, _pad;
+};
+static_assert(sizeof(ChannelArgs) == 48, "the kernel re-reads ChannelArgs with scalar loads");
+
 }  // namespace sart

@@ -2488,6 +2488,435 @@ __global__ __launch_bounds__(BLOCK) void shell_histogram_kernel(HotA H, const De
 }
 
 // ------------------------------------------------------------------------------------------------
+// emission-channel breakdown of the histogram trace (include/sart.h: sart_trace_histogram_channels_device)
+// ------------------------------------------------------------------------------------------------
+// shell_histogram_kernel's twin: trace_histogram_kernel's generic variants with the same accumulator - image, scalars, spectra -
+// plus, per channel t < T of the context's fraction table (ChannelArgs::frac, written by channel_fractions_kernel), the sums, the
+// energy spectrum and the image of c_t = w f_t, where f is the run of `stride` doubles at (r_idx n_energies + e_idx) stride: r_idx
+// travels through ring 1, e_idx comes out of phase B.  The run is ONE gather per passed ray (d2 loads of one aligned 64-byte line at
+// most), requested under the live-lane mask of the passed rays in front of the accumulator's own arithmetic and atomics so that it
+// flies behind them; the loop over t is wave-uniform (T from the kernel arguments) and unrolled, so f stays in registers.  Row sums
+// and N_CONTRIBUTING go to per-workgroup LDS cells (kChanLanes cells each), summed and stored once per workgroup and folded by
+// fold_channels_kernel; per-channel energy bins and pixels take global atomics like ascan_images_kernel's.  The table
+// lives in the last kChanTableCells cells behind the tables, so the LDS image tile is at most kChanImageTileMax wide (host).
+struct ChanKernArgs {
+  HotA H;
+  const DevBlob* blob;
+  TraceArgs A;
+  double* acc;
+  HotB HB;
+  ChannelArgs CH;
+};
+static_assert(offsetof(ChanKernArgs, A) == offsetof(HistKernArgs, A) && offsetof(ChanKernArgs, HB) == offsetof(HistKernArgs, HB) &&
+                  offsetof(ChanKernArgs, CH) == offsetof(HistKernArgs, SC),
+              "the channel kernel shares the argument offsets of the histogram kernel");
+
+template <int BLOCK, bool ROT, bool FIXED>
+__global__ __launch_bounds__(BLOCK) void channel_histogram_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
+                                                                  double* __restrict__ acc, HotB HBarg, ChannelArgs CHarg) {
+  using Sum = std::conditional_t<FIXED, long long, double>;   // per-lane sums: quanta (FIXED) or f64
+  struct LdsLayout {
+    TablesLds S;
+    double tile_extra[kRingExtraCells - kChanTableCells];    // cells kTileRingCells .. of the image tile
+    Sum chan_sum[kMaxChannels][3][kChanLanes];               // per channel: sum of c, sum of c^2, sum of c outside the image
+    uint32_t chan_cnt[kMaxChannels][kChanLanes];             // per channel: N_CONTRIBUTING
+    DevBlob B;
+    TraceArgs Ab;
+    QueueLds<BLOCK / 64> Q;
+  };
+  __shared__ LdsLayout lds;
+  TablesLds& S = lds.S;
+  QueueLds<BLOCK / 64>& Q = lds.Q;
+  static_assert((offsetof(LdsLayout, Q) % 512) == 0, "the rings are addressed with ds_*2st64 offsets");
+  static_assert((BLOCK / 64) * kQueue == kTileRingCells, "ring 0 of this workgroup is the first part of the tile space");
+  static_assert(sizeof(lds.chan_cnt) + sizeof(lds.chan_sum) == kChanTableCells * sizeof(double), "the channel table's cells");
+  // cell t of the LDS image tile: ring 0 (stage A0 off: ray + u3hi columns, 128 doubles per wave), then the cells behind the tables
+  auto tile_cell = [&](uint32_t t) -> double* {
+    return t < (uint32_t)kTileRingCells ? reinterpret_cast<double*>(&Q.w[t >> 7].ray[0]) + (t & 127u)
+                                        : &lds.tile_extra[t - (uint32_t)kTileRingCells];
+  };
+  DevBlob& B = lds.B;
+  TraceArgs& Ab = lds.Ab;
+  {
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(blob);
+    uint64_t* dst = reinterpret_cast<uint64_t*>(&B);
+    for (int i = threadIdx.x; i < (int)(sizeof(DevBlob) / 8); i += BLOCK) dst[i] = src[i];
+    if (threadIdx.x == 0) Ab = A;
+    __syncthreads();
+  }
+  const DevParams& Pb = B.P;
+  const DevTables& Tb = B.T;
+  {
+    uint64_t* q = reinterpret_cast<uint64_t*>(&Q);
+    for (int i = threadIdx.x; i < (int)(sizeof(Q) / 8); i += BLOCK) q[i] = 0ull;
+    for (int i = threadIdx.x; i < kRingExtraCells - kChanTableCells; i += BLOCK) lds.tile_extra[i] = 0.0;
+    for (int i = threadIdx.x; i < kMaxChannels * 3 * kChanLanes; i += BLOCK) (&lds.chan_sum[0][0][0])[i] = 0;
+    if (threadIdx.x < kMaxChannels * kChanLanes) (&lds.chan_cnt[0][0])[threadIdx.x] = 0u;
+  }
+  stage_tables<BLOCK>(S, Pb, Tb);   // (its barrier orders the zeroing above before the first use)
+  const LdsTables L{S.sincos, S.rcdf_hi, Tb.flux_radius_cdf, S.rguide, S.shells, S.lut};
+
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint64_t waves_total = (uint64_t)gridDim.x * (BLOCK / 64);
+  const uint64_t wave_global = (uint64_t)blockIdx.x * (BLOCK / 64) + wave;
+  const bool early_reject = H.n_zones > 0;   // wave-uniform; the host builds no zones for the X-ray test source
+  const uint64_t first_chunk = A.ray_id_offset >> 8;
+  uint64_t id_base = first_chunk << 8;
+  asm volatile("" : "+s"(id_base));
+  const uint32_t rel_begin = (uint32_t)(A.ray_id_offset & 255u);
+  const uint32_t rel_end = rel_begin + (uint32_t)A.n_rays;
+  const uint32_t n_chunks = (rel_end + 255u) >> 8;
+
+  uint32_t n_reached = 0, n_shell = 0, n_nickel = 0, n_till = 0, n_passed = 0;   // wave-uniform
+  uint32_t n_outside = 0;    // per lane: passed rays outside the image
+  Sum sum_w = 0, sum_w2 = 0, sum_x = 0, sum_y = 0, sum_r = 0;
+  long long sum_wo = 0;      // FIXED: weights of the passed rays outside the image
+  uint32_t h0 = 0, t0 = 0;   // ring 0 (A0 -> A1)
+  uint32_t h1 = 0, t1 = 0;   // ring 1 (A1 -> B)
+  auto ring_sync = [] {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
+  auto prefix_of = [](uint64_t mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+  };
+
+  // phase A as in trace_histogram_kernel's generic variants
+  auto run_phase_a = [&](uint32_t rel, bool valid, uint32_t u3_hi) {
+    SART_STAGE_MARK("A1");
+    __builtin_amdgcn_s_setprio(SART_PRIO_A1);
+    RayState st;
+    bool sampled = false, reached = false;
+    double radial;
+    HotA Hl;
+    reload_hot(Hl);
+    LaneMasks M;
+    (void)phase_a<false, ROT ? 1 : 0, false, false>(Hl, Pb, L, A.seed_lo, A.seed_hi, id_base + (uint64_t)rel, u3_hi, st, sampled, reached, radial, M);
+    const uint64_t valid_m = ballot64(valid);
+    n_reached += (uint32_t)__popcll(valid_m & M.reached);
+    const uint64_t selected = valid_m & M.ok;
+    n_shell += (uint32_t)__popcll(selected);
+    const uint64_t mask = selected & ~ballot64(radial < Pb.shell0_miss_radius);
+    const uint32_t cnt = (uint32_t)__popcll(mask);
+    if (__builtin_amdgcn_inverse_ballot_w64(mask)) {
+      const uint32_t slot = (t1 + prefix_of(mask)) % kQueue;
+      Q.w[wave].X0[slot] = st.X0; Q.w[wave].Y0[slot] = st.Y0;
+      Q.w[wave].tsx[slot] = st.tsx; Q.w[wave].tsy[slot] = st.tsy;
+      Q.w[wave].path[slot] = st.path_cb;
+      Q.w[wave].u5[slot] = st.u5;
+      Q.w[wave].idx[slot] = st.r_idx | (st.shell << 16);
+    }
+    t1 += cnt;
+    __builtin_amdgcn_s_setprio(0);
+  };
+
+  auto run_phase_b = [&](uint32_t n_valid) {
+    SART_STAGE_MARK("B");
+    __builtin_amdgcn_s_setprio(SART_PRIO_B);
+    RayState st;
+    const bool valid = (uint32_t)lane < n_valid;
+    const uint32_t slot = (h1 + (uint32_t)lane) % kQueue;
+    RayOut out;
+    {
+      st.X0 = Q.w[wave].X0[slot]; st.Y0 = Q.w[wave].Y0[slot];
+      st.tsx = Q.w[wave].tsx[slot]; st.tsy = Q.w[wave].tsy[slot];
+      st.path_cb = Q.w[wave].path[slot];
+      st.u5 = Q.w[wave].u5[slot];
+      st.u5_hi = upper32_of_uniform(st.u5);   // u5 = word / 2^32 (uniforms_of): the word back, exactly
+      if (!ROT) {
+        st.zcb = -(H.dz3 - H.dz1);
+      } else {
+        st.zcb = zcb_rotated(Pb.rx_s, -Pb.rx_c * Pb.ry_s, Pb.rx_c * Pb.ry_c, Pb.half_length_telescope, st.X0 + Pb.entrance_x,
+                             st.Y0 + Pb.entrance_y, st.tsx, st.tsy, H.dz3 - H.dz1);
+      }
+      const int packed = Q.w[wave].idx[slot];
+      st.r_idx = packed & 0xFFFF;
+      st.shell = packed >> 16;
+      const DevBlob& Bo = lds_opaque(B);
+      HotB HB;
+      reload_kernarg(HB, offsetof(ChanKernArgs, HB));
+      asm volatile("" :: "s"(HB.cdf_hi32), "s"(HB.energy_guide), "s"(HB.energy_tab), "s"(HB.refl), "s"(HB.refl_n_angles), "s"(HB.cdf_stride));
+      phase_b<false, false, -1, false>(Bo.P, L, HB, lds_opaque(Ab), st, H.test_active ? Pb.n_energies : -1, valid, out, nullptr);
+    }
+    h1 += n_valid;
+    __builtin_amdgcn_s_setprio(SART_PRIO_ACC);
+    n_nickel += (uint32_t)__popcll(out.m_nickel);
+    n_till += (uint32_t)__popcll(out.m_till);
+    n_passed += (uint32_t)__popcll(out.m_passed);
+    if (out.passed) {
+      SART_STAGE_MARK("ACC");
+      // this ray's fractions: requested first, used behind the accumulator's own work.  The indices are clamped to the table (host:
+      // its shape is the solar tables' and it is < 4 GB, so the byte offset is 32-bit).
+      ChannelArgs CHl;
+      reload_kernarg(CHl, offsetof(ChanKernArgs, CH));
+      asm volatile("" :: "s"(CHl.block), "s"(CHl.frac), "s"(CHl.n_channels), "s"(CHl.stride), "s"(CHl.n_radii), "s"(CHl.n_energies),
+                   "s"(CHl.n_energies1));
+      // (the first half of the run here, the second - strides of 8 only: the same 64-byte line, a cache hit by then - in front of the
+      // channel loop, where the first four channels' work covers it: all eight in flight across the accumulator's work spill registers)
+      double f[kMaxChannels];
+      const uint32_t f_off = ((uint32_t)min(max(st.r_idx, 0), CHl.n_radii - 1) * (uint32_t)CHl.n_energies +
+                              (uint32_t)min(max(out.e_idx, 0), CHl.n_energies - 1)) * ((uint32_t)CHl.stride * 8u);
+#pragma unroll
+      for (int k = 0; k < kMaxChannels; ++k) f[k] = 0.0;
+      if (CHl.stride == 1) {   // wave-uniform
+        f[0] = gload<double>(CHl.frac, f_off);
+      } else {
+#pragma unroll
+        for (int k = 0; k < kMaxChannels / 4; ++k)
+          if (2 * k < CHl.stride) {
+            const d2 v = gload<d2>(CHl.frac, f_off + 16u * (uint32_t)k);
+            f[2 * k] = v.x;
+            f[2 * k + 1] = v.y;
+          }
+      }
+      TraceArgs Al;
+      reload_kernarg(Al, offsetof(ChanKernArgs, A));
+      asm volatile("" :: "s"(Al.replicas), "s"(Al.replica_mask), "s"(Al.replica_stride), "s"(Al.image_nx), "s"(Al.image_ny),
+                   "s"(Al.image_x_min), "s"(Al.image_y_min), "s"(Al.image_inv_step_x), "s"(Al.image_inv_step_y), "s"(Al.spectra),
+                   "s"(Al.tile_x0), "s"(Al.tile_y0), "s"(Al.tile_n), "s"(Al.tile_base));
+      long long w_fx = 0;   // FIXED: this ray's weight in quanta (what the image, the sums and the spectra add)
+      if constexpr (FIXED) {
+        w_fx = to_fixed(out.weight, Al.fx_scale_w);
+        const long long w2_fx = to_fixed(out.weight * out.weight, Al.fx_scale_w2);
+        sum_w += w_fx;
+        sum_w2 += w2_fx;
+        sum_x += to_fixed(out.px, kFixedPositionScale);
+        sum_y += to_fixed(out.py, kFixedPositionScale);
+        sum_r += to_fixed(out.rdet, kFixedPositionScale);
+      } else {
+        sum_w += out.weight;
+        sum_w2 = fma(out.weight, out.weight, sum_w2);
+        sum_x += out.px;
+        sum_y += out.py;
+        sum_r += out.rdet;
+      }
+      // prepareHeatmap (:838-842), as trace_histogram_kernel bins it
+      const double fx = (out.px - Al.image_x_min) * Al.image_inv_step_x;
+      const double fy = (out.py - Al.image_y_min) * Al.image_inv_step_y;
+      const int nx = Al.image_nx, ny = Al.image_ny;
+      const uint64_t inside_m = ballot64(fx >= 0.0) & ballot64(fx < (double)nx) & ballot64(fy >= 0.0) & ballot64(fy < (double)ny);
+      const bool inside = __builtin_amdgcn_inverse_ballot_w64(inside_m);
+      n_outside += inside ? 0u : 1u;
+      if constexpr (FIXED) {
+        if (out.m_passed & ~inside_m) sum_wo += inside ? 0ll : w_fx;
+      }
+      double* const img = Al.replicas + (size_t)((uint32_t)wave_global & Al.replica_mask) * (size_t)Al.replica_stride;
+      uint32_t c_pix = 0u;   // the ray's pixel, for the channel images
+      if (inside) {
+        const uint32_t ix = (uint32_t)(int)fx, iy = (uint32_t)(int)fy;
+        c_pix = iy * (uint32_t)nx + ix;
+        const uint32_t tn = (uint32_t)Al.tile_n;
+        const uint32_t tx = ix - (uint32_t)Al.tile_x0, ty = iy - (uint32_t)Al.tile_y0;
+        if ((tx < tn) & (ty < tn)) {
+          const uint32_t t = ty * tn + tx + (uint32_t)Al.tile_base;   // < kTileRingCells + kRingExtraCells - kChanTableCells (host)
+          if constexpr (FIXED)
+            __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(tile_cell(t)), (unsigned long long)w_fx, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+          else
+            __hip_atomic_fetch_add(tile_cell(t), out.weight, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        } else {
+          const uint32_t pix = iy * (uint32_t)nx + ix;
+          typedef __attribute__((address_space(1))) char* gbytes;
+          if constexpr (FIXED) atomic_add_slot_i64((double*)((gbytes)img + pix * 8u), w_fx);
+          else unsafeAtomicAdd((double*)((gbytes)img + pix * 8u), out.weight);
+        }
+      }
+      if (Al.spectra) {   // wave-uniform: the spectra behind the scalars
+        double* rad = acc + (size_t)nx * (size_t)ny + SART_ACC_COUNT;
+        double* en = rad + 2 * (size_t)Al.n_radial_bins;
+        const size_t ne1 = (size_t)Pb.n_energies + 1;
+        const int rb = min((int)(out.rdet * Al.radial_inv_bin), Al.n_radial_bins - 1);
+        if constexpr (FIXED) {
+          atomic_add_slot_i64(&rad[rb], 1);
+          atomic_add_slot_i64(&rad[(size_t)Al.n_radial_bins + rb], w_fx);
+          atomic_add_slot_i64(&en[out.e_idx], 1);
+          atomic_add_slot_i64(&en[ne1 + out.e_idx], w_fx);
+          atomic_add_slot_i64(&en[2 * ne1 + out.e_idx], to_fixed(out.reflect, kFixedReflectScale));
+        } else {
+          unsafeAtomicAdd(&rad[rb], 1.0);
+          unsafeAtomicAdd(&rad[(size_t)Al.n_radial_bins + rb], out.weight);
+          unsafeAtomicAdd(&en[out.e_idx], 1.0);
+          unsafeAtomicAdd(&en[ne1 + out.e_idx], out.weight);
+          unsafeAtomicAdd(&en[2 * ne1 + out.e_idx], out.reflect);
+        }
+      }
+      // the channels: c_t = w f_t, ONE product; the same c_t to the row, the ray's energy bin and its pixel (or the row's OUTSIDE)
+      {
+        const uint32_t cl = (uint32_t)lane & (uint32_t)(kChanLanes - 1);
+        const size_t c_ne1 = (size_t)CHl.n_energies1, c_nimg = (size_t)nx * (size_t)ny;
+        double* const c_en = CHl.block + (size_t)CHl.n_channels * SART_CHAN_ROW;                  // energy_weights[t][e]
+        double* const c_img = c_en + (Al.spectra ? (size_t)CHl.n_channels * c_ne1 : (size_t)0);   // images [t][ny][nx]
+        if (CHl.stride == 8) {   // wave-uniform: the second half of the run
+#pragma unroll
+          for (int k = kMaxChannels / 4; k < kMaxChannels / 2; ++k) {
+            const d2 v = gload<d2>(CHl.frac, f_off + 16u * (uint32_t)k);
+            f[2 * k] = v.x;
+            f[2 * k + 1] = v.y;
+          }
+        }
+#pragma unroll
+        for (int t = 0; t < kMaxChannels; ++t) {
+          if (t >= CHl.n_channels) break;   // wave-uniform
+          const double ft = f[t];
+          if (ft > 0.0) __hip_atomic_fetch_add(&lds.chan_cnt[t][cl], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          const double c = out.weight * ft;
+          if (c != 0.0) {
+            if constexpr (FIXED) {
+              const long long c_fx = to_fixed(c, Al.fx_scale_w);
+              const long long c2_fx = to_fixed(c * c, Al.fx_scale_w2);
+              __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(&lds.chan_sum[t][0][cl]), (unsigned long long)c_fx,
+                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(&lds.chan_sum[t][1][cl]), (unsigned long long)c2_fx,
+                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              if (inside) atomic_add_slot_i64(c_img + (size_t)t * c_nimg + c_pix, c_fx);
+              else
+                __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(&lds.chan_sum[t][2][cl]), (unsigned long long)c_fx,
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              if (Al.spectra) atomic_add_slot_i64(c_en + (size_t)t * c_ne1 + (size_t)out.e_idx, c_fx);
+            } else {
+              __hip_atomic_fetch_add(&lds.chan_sum[t][0][cl], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              __hip_atomic_fetch_add(&lds.chan_sum[t][1][cl], c * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              if (inside) unsafeAtomicAdd(c_img + (size_t)t * c_nimg + c_pix, c);
+              else __hip_atomic_fetch_add(&lds.chan_sum[t][2][cl], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              if (Al.spectra) unsafeAtomicAdd(c_en + (size_t)t * c_ne1 + (size_t)out.e_idx, c);
+            }
+          }
+        }
+      }
+    }
+    __builtin_amdgcn_s_setprio(0);
+  };
+
+  // stage A0 as in the generic histogram variants (zone bounds re-read from the kernel arguments per pass)
+  uint32_t chunk = (uint32_t)wave_global;
+  const uint32_t lane4 = 4u * (uint32_t)lane;
+  uint32_t pass = 0;
+  U4 stream = U4{0u, 0u, 0u, 0u};
+  for (;;) {
+    const bool have_new = chunk < n_chunks;   // wave-uniform
+    SART_STAGE_MARK("LOOP");
+    if (have_new) {
+      SART_STAGE_MARK("A0");
+      if (pass == 0u) stream = stream_block(((first_chunk + (uint64_t)chunk) << 6) + (uint64_t)lane, A.seed_lo, A.seed_hi);
+      const uint32_t w = word_of(stream, pass);
+      const uint32_t rel = ((chunk << 8) + pass) + lane4;
+      if (early_reject) {
+        ZoneTable Z;
+        reload_zones(Z);
+        uint64_t dead_m = 0, reached_m = 0;
+#pragma unroll
+        for (int z = 0; z < kMaxZones; ++z) {
+          const uint64_t in = ballot64(w >= Z.lo[z]) & ballot64(w <= Z.hi[z]);
+          dead_m |= in;
+          reached_m |= ((Z.zone_reached >> z) & 1u) ? in : 0ull;
+        }
+        const uint32_t chunk_lo = chunk << 8;
+        uint64_t valid_m = ~0ull;
+        if ((chunk_lo < rel_begin) | (chunk_lo + 256u > rel_end)) valid_m = ballot64(rel >= rel_begin) & ballot64(rel < rel_end);
+        n_reached += (uint32_t)__popcll(valid_m & reached_m);
+        const uint64_t mask = valid_m & ~dead_m;
+        if (__builtin_amdgcn_inverse_ballot_w64(mask)) {
+          const uint32_t slot = (t0 + prefix_of(mask)) % kQueue;
+          Q.w[wave].ray[slot] = rel;
+          Q.w[wave].u3hi[slot] = w;
+        }
+        t0 += (uint32_t)__popcll(mask);
+      } else {
+        run_phase_a(rel, (rel >= rel_begin) & (rel < rel_end), w);
+      }
+      pass = (pass + 1u) & 3u;
+      if (pass == 0u) chunk += (uint32_t)waves_total;
+      ring_sync();
+    }
+    if (early_reject) {
+      const uint32_t n0 = t0 - h0;
+      if ((n0 >= 64u) | (!have_new & (n0 > 0u))) {
+        const uint32_t m = min(n0, 64u);
+        const bool v = (uint32_t)lane < m;
+        const uint32_t slot = (h0 + (uint32_t)lane) % kQueue;
+        const uint32_t rel = Q.w[wave].ray[slot];
+        const uint32_t w = Q.w[wave].u3hi[slot];
+        h0 += m;
+        run_phase_a(rel, v, w);
+        ring_sync();
+      }
+    }
+    const uint32_t n1 = t1 - h1;
+    const bool draining = !have_new & (t0 == h0);
+    if ((n1 >= 64u) | (draining & (n1 > 0u))) {
+      run_phase_b(min(n1, 64u));
+      ring_sync();
+    }
+    if (draining & (t1 == h1)) break;
+  }
+
+  SART_STAGE_MARK("EPILOGUE");
+  // flush of the LDS image tile: one global atomic per non-empty tile pixel and workgroup
+  if (A.tile_n > 0) {
+    __syncthreads();
+    const uint32_t tn = (uint32_t)A.tile_n, n_tile = tn * tn;
+    double* const img = A.replicas + (size_t)((uint32_t)wave_global & A.replica_mask) * (size_t)A.replica_stride;
+    for (uint32_t t = threadIdx.x; t < n_tile; t += BLOCK) {
+      const double v = *tile_cell(t + (uint32_t)A.tile_base);
+      if (__double_as_longlong(v) != 0ll) {
+        const uint32_t ty = t / tn, tx = t - ty * tn;
+        double* const px = &img[(size_t)((uint32_t)A.tile_y0 + ty) * (size_t)A.image_nx + ((uint32_t)A.tile_x0 + tx)];
+        if constexpr (FIXED) atomic_add_slot_i64(px, __double_as_longlong(v));
+        else unsafeAtomicAdd(px, v);
+      }
+    }
+  }
+  // scalars: as trace_histogram_kernel (wave reduction -> LDS staging in wave 0's first ring columns -> one store per workgroup)
+  __syncthreads();
+  Sum (*const red)[SART_ACC_COUNT] = reinterpret_cast<Sum (*)[SART_ACC_COUNT]>(&Q.w[0].X0[0]);
+  Sum sw, sw2, sxx, syy, srr;
+  if constexpr (FIXED) {
+    sw = wave_sum_i64(sum_w); sw2 = wave_sum_i64(sum_w2); sxx = wave_sum_i64(sum_x); syy = wave_sum_i64(sum_y); srr = wave_sum_i64(sum_r);
+  } else {
+    sw = wave_sum(sum_w); sw2 = wave_sum(sum_w2); sxx = wave_sum(sum_x); syy = wave_sum(sum_y); srr = wave_sum(sum_r);
+  }
+  const long long swo = FIXED ? wave_sum_i64(sum_wo) : 0ll;
+  const long long n_out = wave_sum_i64((long long)n_outside);
+  if (lane == 0) {
+    Sum* r = red[wave];
+    for (int k = 0; k < SART_ACC_COUNT; ++k) r[k] = 0;
+    r[SART_ACC_SUM_WEIGHTS] = sw;
+    r[SART_ACC_SUM_WEIGHTS_SQ] = sw2;
+    r[SART_ACC_SUM_X] = sxx;
+    r[SART_ACC_SUM_Y] = syy;
+    r[SART_ACC_SUM_R] = srr;
+    r[SART_ACC_N_PASSED] = (Sum)n_passed;
+    r[SART_ACC_N_PASSED_TILL_WINDOW] = (Sum)n_till;
+    r[SART_ACC_N_HIT_NICKEL] = (Sum)n_nickel;
+    r[SART_ACC_N_REACHED_TELESCOPE] = (Sum)n_reached;
+    r[SART_ACC_N_SHELL_SELECTED] = (Sum)n_shell;
+    r[SART_ACC_N_OUTSIDE_IMAGE] = (Sum)n_out;
+    if constexpr (FIXED) r[SART_ACC_SUM_WEIGHTS_OUTSIDE] = swo;
+  }
+  __syncthreads();
+  if (threadIdx.x < SART_ACC_COUNT) {
+    Sum t = 0;
+    for (int w = 0; w < BLOCK / 64; ++w) t += red[w][threadIdx.x];
+    reinterpret_cast<Sum*>(A.partials)[(size_t)blockIdx.x * SART_ACC_COUNT + threadIdx.x] = t;
+  }
+  // the channel table of this workgroup (every wave has left the loop: the barriers above)
+  if (threadIdx.x < kMaxChannels * kChanPartialSlots) {
+    const int t = threadIdx.x / kChanPartialSlots, j = threadIdx.x - t * kChanPartialSlots;
+    Sum v = 0;
+    if (j < 3) {
+      for (int l = 0; l < kChanLanes; ++l) v += lds.chan_sum[t][j][l];
+    } else {
+      uint32_t n = 0u;
+      for (int l = 0; l < kChanLanes; ++l) n += lds.chan_cnt[t][l];
+      v = (Sum)n;
+    }
+    reinterpret_cast<Sum*>(CHarg.partials)[(size_t)blockIdx.x * (kMaxChannels * kChanPartialSlots) + threadIdx.x] = v;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // fused energy scan (include/sart.h: sart_trace_energy_scan)
 // ------------------------------------------------------------------------------------------------
 // With the X-ray test source (sart_setup_t::test_active) the energy is a constant of the setup (energyAx = testSource.energy,
@@ -4050,6 +4479,142 @@ __global__ __launch_bounds__(256) void finalize_shells_kernel(const long long* i
   o[SART_SHELL_SUM_WEIGHTS_SQ] = sq_ok ? sw2 * F.q_w2 : __builtin_nan("");
 }
 
+// Channel block (include/sart.h: SART_CHAN_*) += the per-workgroup channel tables of one channel_histogram_kernel launch.  One
+// workgroup per channel, 64 threads = 4 slots x 16 groups of workgroups; group g sums the partials g, g + 16, ... in that order and
+// slot j's first thread adds the sixteen group sums in order: the summation tree is fixed for a given grid.  FIXED: integers, the three
+// sums in two limbs (hi 2^40 + lo, lo in [0, 2^40)) like fold_shells_kernel.
+template <bool FIXED>
+__global__ __launch_bounds__(64) void fold_channels_kernel(double* __restrict__ block_, const double* __restrict__ partials_, int n_blocks) {
+  using Sum = std::conditional_t<FIXED, long long, double>;
+  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
+  Sum* const row = reinterpret_cast<Sum*>(block_) + (size_t)blockIdx.x * SART_CHAN_ROW;
+  const Sum* const part = reinterpret_cast<const Sum*>(partials_);
+  __shared__ Sum red_lo[16][kChanPartialSlots], red_hi[16][kChanPartialSlots];
+  const int j = threadIdx.x & (kChanPartialSlots - 1), g = threadIdx.x / kChanPartialSlots;
+  Sum lo = 0, hi = 0;
+  for (int b = g; b < n_blocks; b += 16) {
+    const Sum p = part[((size_t)b * kMaxChannels + blockIdx.x) * kChanPartialSlots + j];
+    if constexpr (FIXED) { lo += p & kMask; hi += p >> kFixedLimbBits; } else lo += p;
+  }
+  red_lo[g][j] = lo;
+  red_hi[g][j] = hi;
+  __syncthreads();
+  if (g != 0) return;
+  lo = 0; hi = 0;
+  for (int i = 0; i < 16; ++i) { lo += red_lo[i][j]; hi += red_hi[i][j]; }
+  // partial slots 0 .. 2 are the sums SUM_WEIGHTS, SUM_WEIGHTS_SQ, SUM_WEIGHTS_OUTSIDE, 3 the counter N_CONTRIBUTING
+  if (j == 3) {
+    if constexpr (FIXED) row[SART_CHAN_N_CONTRIBUTING] += (hi << kFixedLimbBits) + lo; else row[SART_CHAN_N_CONTRIBUTING] += lo;
+  } else {
+    const int s = j == 0 ? SART_CHAN_SUM_WEIGHTS : j == 1 ? SART_CHAN_SUM_WEIGHTS_SQ : SART_CHAN_SUM_WEIGHTS_OUTSIDE;
+    const int sh = j == 0 ? SART_CHAN_SUM_WEIGHTS_HI : j == 1 ? SART_CHAN_SUM_WEIGHTS_SQ_HI : SART_CHAN_SUM_WEIGHTS_OUTSIDE_HI;
+    if constexpr (FIXED) {
+      lo += row[s];
+      row[s] = lo & kMask;
+      row[sh] += hi + (lo >> kFixedLimbBits);
+    } else {
+      row[s] += lo;
+    }
+  }
+}
+
+// Raw FIXED64 channel block -> doubles (sart_finalize_channels_device).  One workgroup per channel: its row, with spectra its energy
+// bins, with an image its pixels.  Each slot is read and written by the same thread (in place allowed).  Checks: every slot in
+// [0, 2^62); the exact conservation laws of the block itself - every contributing ray adds the same integer to SUM_WEIGHTS, to one
+// energy bin and to one pixel or SUM_WEIGHTS_OUTSIDE.  No resolution check: a faint channel's c_t are exact to half a quantum of the
+// total weight like every other, and its SUM_WEIGHTS_SQ is exact to N_CONTRIBUTING / 2 quanta of the squared weights.
+struct FinalizeChannelsArgs {
+  int32_t n_channels, n_energies1, spectra, _pad;
+  long long n_img;
+  double q_w, q_w2;
+};
+__global__ __launch_bounds__(256) void finalize_channels_kernel(const long long* in, double* out, FinalizeChannelsArgs F, FixedCheck* C) {
+  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
+  uint32_t* const status = &C->status;
+  const int t = blockIdx.x;
+  const long long* const row = in + (size_t)t * SART_CHAN_ROW;
+  long long v[SART_CHAN_ROW];
+  for (int j = 0; j < SART_CHAN_ROW; ++j) v[j] = row[j];   // (every thread: read before the block's first write)
+  __shared__ long long sums[4];   // energy bins lo, hi; pixels lo, hi
+  if (threadIdx.x < 4) sums[threadIdx.x] = 0;
+  __syncthreads();
+  const size_t ne = (size_t)F.n_energies1, T = (size_t)F.n_channels;
+  const size_t e0 = T * SART_CHAN_ROW + (size_t)t * ne;
+  const size_t p0 = T * SART_CHAN_ROW + (F.spectra ? T * ne : (size_t)0) + (size_t)t * (size_t)F.n_img;
+  long long acc4[4] = {0, 0, 0, 0};
+  if (F.spectra)
+    for (size_t e = threadIdx.x; e < ne; e += 256) {
+      const long long w = in[e0 + e];
+      fixed_status_check_slot(w, status);
+      acc4[0] += w & kMask;
+      acc4[1] += w >> kFixedLimbBits;
+      out[e0 + e] = (double)w * F.q_w;
+    }
+  for (size_t p = threadIdx.x; p < (size_t)F.n_img; p += 256) {
+    const long long w = in[p0 + p];
+    fixed_status_check_slot(w, status);
+    acc4[2] += w & kMask;
+    acc4[3] += w >> kFixedLimbBits;
+    out[p0 + p] = (double)w * F.q_w;
+  }
+  for (int k = 0; k < 4; ++k) {
+    const long long s = wave_sum_i64(acc4[k]);
+    if ((threadIdx.x & 63) == 0) atomicAdd(reinterpret_cast<unsigned long long*>(&sums[k]), (unsigned long long)s);
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  for (int j = 0; j < SART_CHAN_ROW; ++j) fixed_status_check_slot(v[j], status);
+  const double two40 = (double)(1ll << kFixedLimbBits);
+  const long long want_hi = v[SART_CHAN_SUM_WEIGHTS_HI] + (v[SART_CHAN_SUM_WEIGHTS] >> kFixedLimbBits);
+  const long long want_lo = v[SART_CHAN_SUM_WEIGHTS] & kMask;
+  if (F.spectra) {
+    const long long hi = sums[1] + (sums[0] >> kFixedLimbBits), lo = sums[0] & kMask;
+    if (hi != want_hi || lo != want_lo) atomicOr(status, kFixedStatusNotConserved);
+  }
+  {
+    const long long l = sums[2] + v[SART_CHAN_SUM_WEIGHTS_OUTSIDE];
+    const long long hi = sums[3] + v[SART_CHAN_SUM_WEIGHTS_OUTSIDE_HI] + (l >> kFixedLimbBits), lo = l & kMask;
+    if (hi != want_hi || lo != want_lo) atomicOr(status, kFixedStatusNotConserved);
+  }
+  double* const o = out + (size_t)t * SART_CHAN_ROW;
+  for (int j = 0; j < SART_CHAN_ROW; ++j) o[j] = 0.0;
+  o[SART_CHAN_SUM_WEIGHTS] = ((double)v[SART_CHAN_SUM_WEIGHTS_HI] * two40 + (double)v[SART_CHAN_SUM_WEIGHTS]) * F.q_w;
+  o[SART_CHAN_SUM_WEIGHTS_SQ] = ((double)v[SART_CHAN_SUM_WEIGHTS_SQ_HI] * two40 + (double)v[SART_CHAN_SUM_WEIGHTS_SQ]) * F.q_w2;
+  o[SART_CHAN_N_CONTRIBUTING] = (double)v[SART_CHAN_N_CONTRIBUTING];
+  o[SART_CHAN_SUM_WEIGHTS_OUTSIDE] = ((double)v[SART_CHAN_SUM_WEIGHTS_OUTSIDE_HI] * two40 + (double)v[SART_CHAN_SUM_WEIGHTS_OUTSIDE]) * F.q_w;
+}
+
+// The fraction table of sart_set_source_channels[_device]: frac[cell stride + t] = rates[t][cell] / total[cell] (IEEE division; 0
+// where total == 0), t >= T padded with 0, a fraction in (1, 1 + 2^-49] stored as 1.  One thread per cell (r, e).  *first_bad (set to
+// ~0 by the host) = min over the offending entries of (cell 8 + t) 4 + code: 1 a negative or non-finite rate, 2 a fraction above
+// 1 + 2^-49, 3 a negative or non-finite total (t = 0).
+__global__ __launch_bounds__(256) void channel_fractions_kernel(const double* __restrict__ rates, const double* __restrict__ total,
+                                                               double* __restrict__ frac, int n_channels, int stride, long long n_cells,
+                                                               unsigned long long* first_bad) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_cells) return;
+  const double tot = total[i];
+  unsigned long long bad = ~0ull;
+  if (!(tot >= 0.0) || !(tot <= 1.7976931348623157e308)) bad = ((unsigned long long)i * 8ull) * 4ull + 3ull;
+  constexpr double kOneUp = 1.0 + 0x1p-49;
+  for (int t = 0; t < stride; ++t) {
+    double f = 0.0;
+    if (t < n_channels) {
+      const double r = rates[(size_t)t * (size_t)n_cells + (size_t)i];
+      const unsigned long long key = ((unsigned long long)i * 8ull + (unsigned long long)t) * 4ull;
+      if (!(r >= 0.0) || !(r <= 1.7976931348623157e308)) {
+        bad = min(bad, key + 1ull);
+      } else if (tot > 0.0) {
+        f = r / tot;
+        if (f > kOneUp) bad = min(bad, key + 2ull);
+        f = fmin(f, 1.0);
+      }
+    }
+    frac[(size_t)i * (size_t)stride + (size_t)t] = f;
+  }
+  if (bad != ~0ull) atomicMin(first_bad, bad);
+}
+
 // Literal drop-in for traceAxionWrapper: one Axion record per ray, in ray order (no compaction).
 constexpr int kRecBlock = 256;
 // `uniforms` != nullptr (sart_internal_trace_records_uniforms, a test entry): ray i takes its six uniforms from
@@ -4650,6 +5215,53 @@ void launch_finalize_shells(const void* in, double* out, int n_shells, int n_ene
   FinalizeShellsArgs F{n_shells, n_energies1, spectra, 0, q_w, q_w2};
   hipLaunchKernelGGL(finalize_shells_kernel, dim3(n_shells), dim3(256), 0, stream, reinterpret_cast<const long long*>(in), out, F,
                      static_cast<FixedCheck*>(check_dev));
+}
+
+// The emission-channel histogram launch (generic variants: `rotated` = hist_variant_of 2): the kernel, then the folds of
+// launch_trace_histogram (scalars, replicas) and the fold of the channel table into the caller's block.
+int channel_histogram_blocks_per_cu(bool rotated) {
+  int n = 0;
+  const hipError_t e = rotated ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, channel_histogram_kernel<1024, true, false>, 1024, 0)
+                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, channel_histogram_kernel<1024, false, false>, 1024, 0);
+  return (e == hipSuccess && n > 0) ? n : 1;
+}
+void launch_channel_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, double* acc, const ChannelArgs& CH,
+                              int n_blocks, hipStream_t stream, bool rotated, bool fixed) {
+  switch ((rotated ? 2 : 0) + (fixed ? 1 : 0)) {
+    case 0: hipLaunchKernelGGL((channel_histogram_kernel<1024, false, false>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, CH); break;
+    case 1: hipLaunchKernelGGL((channel_histogram_kernel<1024, false, true>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, CH); break;
+    case 2: hipLaunchKernelGGL((channel_histogram_kernel<1024, true, false>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, CH); break;
+    default: hipLaunchKernelGGL((channel_histogram_kernel<1024, true, true>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, CH); break;
+  }
+  const int n_img = A.image_nx * A.image_ny;
+  if (fixed) {
+    long long* const acc_i = reinterpret_cast<long long*>(acc);
+    hipLaunchKernelGGL(fold_scalars_fixed_kernel, dim3(1), dim3(256), 0, stream, acc_i + n_img,
+                       reinterpret_cast<const long long*>(A.partials), n_blocks, (long long)A.n_rays);
+    if (A.replica_mask != 0u)
+      hipLaunchKernelGGL(fold_replicas_kernel<long long>, dim3((n_img + 255) / 256), dim3(256), 0, stream, acc_i,
+                         reinterpret_cast<long long*>(A.replicas), n_img, (int)A.replica_mask + 1, A.replica_stride);
+    hipLaunchKernelGGL(fold_channels_kernel<true>, dim3(CH.n_channels), dim3(64), 0, stream, CH.block, CH.partials, n_blocks);
+    return;
+  }
+  hipLaunchKernelGGL(fold_scalars_kernel, dim3(1), dim3(256), 0, stream, acc + n_img, A.partials, n_blocks, (double)A.n_rays);
+  if (A.replica_mask != 0u)
+    hipLaunchKernelGGL(fold_replicas_kernel<double>, dim3((n_img + 255) / 256), dim3(256), 0, stream, acc, A.replicas, n_img,
+                       (int)A.replica_mask + 1, A.replica_stride);
+  hipLaunchKernelGGL(fold_channels_kernel<false>, dim3(CH.n_channels), dim3(64), 0, stream, CH.block, CH.partials, n_blocks);
+}
+void launch_finalize_channels(const void* in, double* out, int n_channels, int n_energies1, int spectra, size_t n_img, double q_w,
+                              double q_w2, void* check_dev, hipStream_t stream) {
+  FinalizeChannelsArgs F{n_channels, n_energies1, spectra, 0, (long long)n_img, q_w, q_w2};
+  hipLaunchKernelGGL(finalize_channels_kernel, dim3(n_channels), dim3(256), 0, stream, reinterpret_cast<const long long*>(in), out, F,
+                     static_cast<FixedCheck*>(check_dev));
+}
+// first_bad_dev: one 8-byte word, set to ~0 here
+void launch_channel_fractions(const double* rates_dev, const double* total_dev, double* frac_dev, int n_channels, int stride,
+                              size_t n_cells, unsigned long long* first_bad_dev, hipStream_t stream) {
+  (void)hipMemsetAsync(first_bad_dev, 0xFF, sizeof(unsigned long long), stream);
+  hipLaunchKernelGGL(channel_fractions_kernel, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, stream, rates_dev, total_dev,
+                     frac_dev, n_channels, stride, (long long)n_cells, first_bad_dev);
 }
 
 size_t fixed_check_bytes() { return sizeof(FixedCheck); }

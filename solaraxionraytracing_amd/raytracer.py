@@ -295,6 +295,7 @@ class RayTracer:
                                                          _lib.as_dp(energies), radii.size, energies.size))
         self.full.energies = energies
         self._n_radii_set = radii.size
+        self._chan_labels = None   # the library dropped the channels with the old tables
 
     def solar_tables(self, guides: bool = False):
         """Host copies of (fluxRadiusCDF, diffFluxCDFs) as the context holds them; with ``guides`` also the library's
@@ -514,6 +515,114 @@ class RayTracer:
         _lib.check(self.lib.sart_finalize_shells_device(self.handle, C.byref(params), C.c_void_p(raw_ptr),
                                                         C.c_void_p(out_ptr if out_ptr is not None else raw_ptr)))
 
+    # -- emission-channel breakdown (include/sart.h "emission-channel breakdown of the histogram trace") ----
+    def set_source_channels(self, rates, total, names=None, couplings=None):
+        """sart_set_source_channels: ``rates`` [T][n_radii][n_energies] (host array, the layout of emission_table's components) and
+        ``total`` [n_radii][n_energies], the table the context's CDFs were made from.  The library keeps rates / total per cell.
+        ``names`` / ``couplings``: one label and one coupling name (COUPLINGS) per channel, carried into trace_channels' result."""
+        rates = np.ascontiguousarray(rates, dtype=np.float64)
+        total = np.ascontiguousarray(total, dtype=np.float64)
+        if rates.ndim != 3 or total.ndim != 2 or rates.shape[1:] != total.shape:
+            raise ValueError("rates must be [T][n_radii][n_energies] and total [n_radii][n_energies]")
+        _lib.check(self.lib.sart_set_source_channels(self.handle, _lib.as_dp(rates), _lib.as_dp(total), rates.shape[0], total.shape[0],
+                                                     total.shape[1]))
+        self._channel_labels(rates.shape[0], names, couplings)
+
+    def set_source_channels_device(self, rates_ptr: int, total_ptr: int, n_channels: int, n_radii: int, n_energies: int, names=None,
+                                   couplings=None):
+        """sart_set_source_channels_device: the same from DEVICE memory (``torch_tensor.data_ptr()``), identical bits."""
+        _lib.check(self.lib.sart_set_source_channels_device(self.handle, C.c_void_p(rates_ptr), C.c_void_p(total_ptr), int(n_channels),
+                                                            int(n_radii), int(n_energies)))
+        self._channel_labels(int(n_channels), names, couplings)
+
+    def _channel_labels(self, t, names, couplings):
+        """The labels of the channels just set (kept with their count: labels of another set of channels are never handed out)."""
+        names = list(names) if names is not None else ["channel%d" % k for k in range(t)]
+        couplings = list(couplings) if couplings is not None else None
+        if len(names) != t or (couplings is not None and len(couplings) != t):
+            raise ValueError("names / couplings must have one entry per channel (%d)" % t)
+        self._chan_labels = (t, names, couplings)
+
+    def _labels_of(self, t):
+        """(names, couplings) of the context's t channels: the labels given when they were set, else channel0 .. and None."""
+        kept = getattr(self, "_chan_labels", None)
+        if kept is not None and kept[0] == t:
+            return list(kept[1]), (list(kept[2]) if kept[2] is not None else None)
+        return ["channel%d" % k for k in range(t)], None
+
+    def clear_source_channels(self):
+        _lib.check(self.lib.sart_clear_source_channels(self.handle))
+        self._chan_labels = None
+
+    def n_source_channels(self) -> int:
+        t = C.c_int32()
+        _lib.check(self.lib.sart_get_source_channels(self.handle, None, C.byref(t)))
+        return t.value
+
+    def source_channels(self) -> np.ndarray:
+        """The fractions the context holds, [T][n_radii][n_energies] (0 where the total is 0)."""
+        t = self.n_source_channels()
+        out = np.empty((t, self._n_radii(), self.full.energies.size))
+        _lib.check(self.lib.sart_get_source_channels(self.handle, _lib.as_dp(out), None))
+        return out
+
+    def set_emission_channels(self, grouping: str = "couplings"):
+        """Channels of a setup whose emission table this library made (emission="agss09" / "agss09-device"): the eight terms of
+        include/sart_emission.h (``grouping="terms"``) or their sums per coupling (``"couplings"``: g_ae, g_agamma, g_anuclei, by
+        TERM_COUPLING).  The components come from emission.emission_table(..., components=True) and are summed per group in numpy."""
+        from . import emission as _emission
+        de = self.full.device_emission
+        if de is not None:
+            if de.get("opcd") is not None:
+                raise ValueError("set_emission_channels: setups with OPCD absorption coefficients are not supported")
+            zones, params = de["zones"], de["params"]
+        elif self.full.meta.get("emission") == "E0-agss09-all-terms-gpu":
+            zones, params = _emission.solar_zones(self._n_radii()), _emission.default_params()
+        else:
+            raise ValueError("set_emission_channels needs a setup made with emission=\"agss09\" or \"agss09-device\" (this one: %r)"
+                             % self.full.meta.get("emission"))
+        total, comp = _emission.emission_table(zones, self.full.energies, params=params, components=True, device=self.device)
+        rates, names, couplings = group_emission_components(comp, grouping)
+        self.set_source_channels(rates, total, names, couplings)
+        return names
+
+    def channel_block_len(self, spectra: bool = True, image_n: int = 256) -> int:
+        """sart_channel_block_len for this context's channels and energy table."""
+        return int(self.lib.sart_channel_block_len(self.n_source_channels(), self.full.energies.size, 1 if spectra else 0, image_n, image_n))
+
+    channels_params = shells_params
+
+    def trace_channels(self, n_rays: int, seed: int = 299792458, ray_id_offset: int = 0, flags: int | None = None, image_n: int = 256,
+                       spectra: bool = True, n_radial_bins: int = 10_000, radial_max: float = 10.0):
+        """trace_histogram (trace_spectra with ``spectra``) plus the emission-channel breakdown (sart_trace_histogram_channels).
+        Returns (image, summary, spectra dict or None, channels dict of per-channel arrays keyed like _lib.CHAN, with ``spectra``
+        also ``energy_weights`` [T][n_energies + 1], with an image ``images`` [T][ny][nx], and ``names`` / ``couplings``)."""
+        p = self.channels_params(n_rays, seed, ray_id_offset, flags, image_n, spectra, n_radial_bins, radial_max)
+        t, n_e = self.n_source_channels(), self.full.energies.size
+        img = np.empty((image_n, image_n))
+        summ = Summary()
+        spec = np.empty(2 * n_radial_bins + 3 * (n_e + 1)) if spectra else None
+        block = np.empty(_lib.channel_block_len(t, n_e, spectra, image_n, image_n))
+        _lib.check(self.lib.sart_trace_histogram_channels(self.handle, C.byref(p), _lib.as_dp(img) if image_n else None, C.byref(summ),
+                                                          _lib.as_dp(spec) if spectra else None, _lib.as_dp(block)))
+        ch = split_channels(block, t, n_e, spectra, image_n, image_n)
+        ch["names"], ch["couplings"] = self._labels_of(t)
+        return (img, {k: summ.v[i] for k, i in _lib.ACC.items()},
+                split_spectra(spec, n_radial_bins, n_e + 1, radial_max) if spectra else None, ch)
+
+    def trace_channels_device(self, params: TraceParams, accumulator_ptr: int, channels_ptr: int):
+        """Asynchronous form: adds into a device accumulator and a device block of channel_block_len(...) slots (raw int64 in fixed64
+        mode).  With ``params.accumulate`` the library adds to what the buffers hold: whatever filled them (a ``torch.zeros`` on
+        torch's stream, say) must have finished, or be ordered on the context's stream (``set_stream``), before this call."""
+        _lib.check(self.lib.sart_trace_histogram_channels_device(self.handle, C.byref(params), C.c_void_p(accumulator_ptr),
+                                                                 C.c_void_p(channels_ptr)))
+
+    def finalize_channels_device(self, params: TraceParams, raw_ptr: int, out_ptr: int | None = None):
+        """Raw FIXED64 channel block (device) -> doubles (device; in place by default).  Asynchronous; what the conversion finds wrong
+        is raised by the next ``synchronize()``."""
+        _lib.check(self.lib.sart_finalize_channels_device(self.handle, C.byref(params), C.c_void_p(raw_ptr),
+                                                          C.c_void_p(out_ptr if out_ptr is not None else raw_ptr)))
+
     # -- fused axion-mass scan (gas stage; include/sart.h "fused axion-mass scan") -------------
     def trace_mass_scan(self, masses_ev, n_rays: int, seed: int = 299792458, ray_id_offset: int = 0, flags: int | None = None):
         """Every ray of [ray_id_offset, ray_id_offset + n_rays) traced ONCE and weighed for every axion mass.  Returns
@@ -692,6 +801,93 @@ def write_shell_csvs(outpath: str, year: str, shells: dict, energies: np.ndarray
                 for k in np.nonzero(shells["energy_counts"][s])[0]:
                     f.write("%d,%d,%.17g,%d,%.17g\n" % (s, k, e[k], int(shells["energy_counts"][s][k]), float(shells["energy_weights"][s][k])))
     return p1, p2
+
+
+channel_block_len = _lib.channel_block_len
+split_channels = _lib.split_channels
+
+# Which coupling every term of the emission table carries (csrc/sart_emission.hip: the g_ae^2, g_agamma^2 and g_anuclei^2 factors of
+# its eight terms, in the order of _lib.EM_TERMS), and the reference values the library's table is made with (readOpacityFile.nim:640-643).
+COUPLINGS = ("g_ae", "g_agamma", "g_anuclei")
+TERM_COUPLING = dict(compton="g_ae", term1="g_ae", ee_brems="g_ae", free_free="g_ae", primakoff="g_agamma", long_plasmon="g_agamma",
+                     trans_plasmon="g_agamma", iron57="g_anuclei")
+REFERENCE_COUPLINGS = dict(g_ae=1e-13, g_agamma=1e-12, g_anuclei=1e-15)
+
+
+def group_emission_components(components, grouping: str):
+    """(rates [T][nR][nE], names, couplings) from the eight components of emission_table: ``"terms"`` keeps them, ``"couplings"``
+    sums them per coupling of TERM_COUPLING (numpy sums, in term order)."""
+    comp = np.asarray(components, dtype=np.float64)
+    assert comp.shape[0] == len(_lib.EM_TERMS)
+    if grouping == "terms":
+        return comp, list(_lib.EM_TERMS), [TERM_COUPLING[t] for t in _lib.EM_TERMS]
+    if grouping == "couplings":
+        rates = np.zeros((len(COUPLINGS),) + comp.shape[1:])
+        for k, term in enumerate(_lib.EM_TERMS):
+            rates[COUPLINGS.index(TERM_COUPLING[term])] += comp[k]
+        return rates, list(COUPLINGS), list(COUPLINGS)
+    raise ValueError("grouping must be \"terms\" or \"couplings\", not %r" % (grouping,))
+
+
+def coupling_signal(channels: dict, g_ae: float | None = None, g_agamma: float | None = None, g_anuclei: float | None = None,
+                    ref: dict | None = None) -> dict:
+    """The expected signal at other couplings from ONE trace_channels result: sum_t s_t X_t with s_t = (g_t / g_t,ref)^2 for the
+    flux, the energy spectrum and the image (those that ``channels`` holds).  ``channels["couplings"]`` names the coupling of every
+    channel; ``ref`` the couplings the emission table was made with (default REFERENCE_COUPLINGS); a coupling left None stays at its
+    reference.  ``flux_error`` is the bound sum_t s_t sqrt(sum w^2_t): the channels share their rays, so their errors are fully
+    correlated and add linearly (triangle inequality) - the exact error sqrt(sum_rays (sum_t s_t c_t)^2) is never larger.
+    This rescales the EMISSION only: the conversion in the magnet carries its own g_agamma^2, which belongs to the setup."""
+    ref = dict(REFERENCE_COUPLINGS, **(ref or {}))
+    g = dict(g_ae=g_ae, g_agamma=g_agamma, g_anuclei=g_anuclei)
+    if channels.get("couplings") is None:
+        raise ValueError("coupling_signal: the channels carry no coupling names (set_source_channels(..., couplings=...))")
+    scale = np.array([1.0 if g[c] is None else (float(g[c]) / ref[c]) ** 2 for c in channels["couplings"]])
+    out = {"scale": scale, "flux": float(np.dot(scale, channels["SUM_WEIGHTS"])),
+           "flux_error": float(np.dot(scale, np.sqrt(channels["SUM_WEIGHTS_SQ"])))}
+    if "energy_weights" in channels:
+        out["energy_weights"] = np.tensordot(scale, channels["energy_weights"], axes=1)
+    if "images" in channels:
+        out["image"] = np.tensordot(scale, channels["images"], axes=1)
+    return out
+
+
+def write_channel_csvs(outpath: str, year: str, channels: dict, energies: np.ndarray, chip_max: float, r_sigma1: float = 0.0,
+                       r_sigma2: float = 0.0):
+    """`flux_by_channel_{year}.csv` (channel, name, contributing rays, flux, its Monte-Carlo error, its fraction of the channels' sum),
+    with energy arrays `energies_by_channel_{year}.csv` (flux per channel and energy bin) and with images one
+    `axion_image_{year}_{name}.csv` per channel (write_image_csv with the chip's width ``chip_max`` and the containment radii of
+    the whole image).  Returns the list of paths."""
+    import os
+    names = channels["names"]
+    flux = np.asarray(channels["SUM_WEIGHTS"], dtype=np.float64)
+    total = float(flux.sum())
+    paths = [os.path.join(outpath, "flux_by_channel_%s.csv" % year)]
+    with open(paths[0], "w") as f:
+        f.write("channel,name,contributing rays,flux,flux error,flux fraction\n")
+        for t, name in enumerate(names):
+            f.write("%d,%s,%d,%.17g,%.17g,%.17g\n" % (t, name, int(channels["N_CONTRIBUTING"][t]), float(flux[t]),
+                                                     float(np.sqrt(channels["SUM_WEIGHTS_SQ"][t])), float(flux[t]) / total if total > 0 else 0.0))
+    if "energy_weights" in channels:
+        paths.append(os.path.join(outpath, "energies_by_channel_%s.csv" % year))
+        e = np.append(np.asarray(energies, dtype=np.float64), np.nan)
+        with open(paths[-1], "w") as f:
+            f.write("channel,name,energy index,energy [keV],flux\n")
+            for t, name in enumerate(names):
+                for k in np.nonzero(channels["energy_weights"][t])[0]:
+                    f.write("%d,%s,%d,%.17g,%.17g\n" % (t, name, k, e[k], float(channels["energy_weights"][t][k])))
+    if "images" in channels:
+        for t, name in enumerate(names):
+            paths.append(os.path.join(outpath, "axion_image_%s_%s.csv" % (year, name)))
+            write_image_csv(paths[-1], channels["images"][t], float(chip_max), r_sigma1, r_sigma2)
+    return paths
+
+
+def read_flux_by_channel_csv(path: str) -> dict:
+    """The columns of a flux_by_channel_{year}.csv, keyed by the header (``name`` as a list of strings, the rest as arrays)."""
+    with open(path) as f:
+        header = f.readline().strip().split(",")
+        rows = [line.strip().split(",") for line in f if line.strip()]
+    return {h: ([r[i] for r in rows] if h == "name" else np.array([float(r[i]) for r in rows])) for i, h in enumerate(header)}
 
 
 def read_shell_breakdown_csv(path: str) -> dict:
