@@ -1832,14 +1832,36 @@ size_t shell_block_len_of(const sart_context* c, const sart_trace_params_t* p) {
   return sart_shell_block_len(c->setup.n_shells, c->n_energies, p->spectra);
 }
 
-// sart_trace_histogram_device, and with `shells_dev` sart_trace_histogram_shells_device: the same host path (quanta, replicas, LDS
-// tile, partials) around trace_histogram_kernel or shell_histogram_kernel; with `chan_dev` sart_trace_histogram_channels_device,
-// around channel_histogram_kernel.
 size_t channel_block_len_of(const sart_context* c, const sart_trace_params_t* p) {
   return sart_channel_block_len(c->n_channels, c->n_energies, p->spectra, p->image_nx, p->image_ny);
 }
 
-int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_dev, double* shells_dev, double* chan_dev = nullptr) {
+// What the host path knows of a breakdown of the histogram trace (kShells, kChannels below): its kernel keeps a table in the last
+// cells of the LDS tile space and stores it once per workgroup, the fold adds those partials into the caller's block.
+struct Breakdown {
+  int tile_max, tile_extra_max;                // widest LDS image tile beside the table: ring 0 free (no stage A0) / all rings in use
+  size_t partial_slots;                        // doubles per workgroup in the partials
+  DevBuf<double> sart_context::*partials;      // the context's per-workgroup tables
+  int (sart_context::*blocks_per_cu)[2];       // cache of kernel_blocks_per_cu, [rotated]
+  int (*kernel_blocks_per_cu)(bool rotated);
+  size_t (*block_len)(const sart_context* c, const sart_trace_params_t* p);
+  // fills the kernel's argument struct and launches the kernel and its folds
+  void (*launch)(sart_context* c, const TraceArgs& a, double* acc_dev, double* block_dev, int n_blocks, bool rotated, bool fixed);
+  // the blocking form: what a launch accepts, the scratch block and its f64 image, the finalize
+  int (*check)(sart_context* c, const sart_trace_params_t* p);
+  DevBuf<double> sart_context::*block;
+  DevBuf<double> sart_context::*block_fin;
+  int (*finalize)(sart_context* c, const sart_trace_params_t* p, const void* raw_dev, double* out_dev);
+};
+struct BreakdownBlock {   // which breakdown a launch fills, if any, and the caller's block
+  const Breakdown* kind = nullptr;
+  double* dev = nullptr;
+};
+
+// sart_trace_histogram_device, and with a breakdown `bd` sart_trace_histogram_shells_device / sart_trace_histogram_channels_device:
+// the same host path (quanta, replicas, LDS tile, partials) around trace_histogram_kernel, shell_histogram_kernel or
+// channel_histogram_kernel.
+int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_dev, BreakdownBlock bd = {}) {
   SART_HIP(hipSetDevice(c->device));
   if (int rc = refresh_derived(c)) return rc;
   if (int rc = sync_blob(c)) return rc;
@@ -1854,8 +1876,7 @@ int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_
     a.fx_scale_w2 = std::ldexp(1.0, -c->weight_sq_exp);
   }
   if (!p->accumulate) SART_HIP(hipMemsetAsync(acc_dev, 0, acc_len_of(c, p) * sizeof(double), c->stream));
-  if (shells_dev && !p->accumulate) SART_HIP(hipMemsetAsync(shells_dev, 0, shell_block_len_of(c, p) * sizeof(double), c->stream));
-  if (chan_dev && !p->accumulate) SART_HIP(hipMemsetAsync(chan_dev, 0, channel_block_len_of(c, p) * sizeof(double), c->stream));
+  if (bd.kind && !p->accumulate) SART_HIP(hipMemsetAsync(bd.dev, 0, bd.kind->block_len(c, p) * sizeof(double), c->stream));
   if (a.n_rays == 0) return 0;
   if (a.n_rays > (1ull << 31)) {   // ray indices inside one launch are 32-bit (stage A0 ring): split
     sart_trace_params_t q = *p;
@@ -1864,7 +1885,7 @@ int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_
       const uint64_t n = std::min<uint64_t>(p->n_rays - done, 1ull << 31);
       q.n_rays = n;
       q.ray_id_offset = p->ray_id_offset + done;
-      if (int rc = histogram_launch(c, &q, acc_dev, shells_dev, chan_dev)) return rc;
+      if (int rc = histogram_launch(c, &q, acc_dev, bd)) return rc;
       done += n;
     }
     return 0;
@@ -1952,17 +1973,11 @@ int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_
         }
         a.tile_x0 = t.x0; a.tile_y0 = t.y0; a.tile_n = t.n;
         a.tile_base = ring_cells_free ? 0 : kTileRingCells;
-        if (shells_dev) {
-          // the shell kernel (generic: its ring 0 is free without stage A0 only) keeps its shell table in the last cells of the
+        if (bd.kind) {
+          // a breakdown's kernel (generic: its ring 0 is free without stage A0 only) keeps its table in the last cells of the
           // tile space: the same tile, narrowed about its centre
           const bool free_s = c->hot.n_zones == 0;
-          const int n = std::min(t.n, free_s ? kShellImageTileMax : kShellImageTileExtraMax);
-          a.tile_x0 = t.x0 + (t.n - n) / 2; a.tile_y0 = t.y0 + (t.n - n) / 2; a.tile_n = n;
-          a.tile_base = free_s ? 0 : kTileRingCells;
-        }
-        if (chan_dev) {   // the channel kernel keeps its channel table there: the same narrowing
-          const bool free_s = c->hot.n_zones == 0;
-          const int n = std::min(t.n, free_s ? kChanImageTileMax : kChanImageTileExtraMax);
+          const int n = std::min(t.n, free_s ? bd.kind->tile_max : bd.kind->tile_extra_max);
           a.tile_x0 = t.x0 + (t.n - n) / 2; a.tile_y0 = t.y0 + (t.n - n) / 2; a.tile_n = n;
           a.tile_base = free_s ? 0 : kTileRingCells;
         }
@@ -1972,66 +1987,28 @@ int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_
       a.replica_mask = 0u;
     }
   }
-  if (shells_dev) {
+  if (bd.kind) {
     const bool rotated = c->params.rotated != 0;   // generic variants: hist_variant_of 1 / 2
-    if (c->blocks_per_cu_shells[rotated] == 0) {
-      c->blocks_per_cu_shells[rotated] = std::max(1, shell_histogram_blocks_per_cu(rotated));
-      if (c->knobs.hist_blocks_per_cu > 0) c->blocks_per_cu_shells[rotated] = c->knobs.hist_blocks_per_cu;
+    int& bpc = (c->*bd.kind->blocks_per_cu)[rotated];
+    if (bpc == 0) {
+      bpc = std::max(1, bd.kind->kernel_blocks_per_cu(rotated));
+      if (c->knobs.hist_blocks_per_cu > 0) bpc = c->knobs.hist_blocks_per_cu;
     }
-    const int n_blocks = grid_for(a.n_rays, c->n_cu, c->blocks_per_cu_shells[rotated], 1024);
+    const int n_blocks = grid_for(a.n_rays, c->n_cu, bpc, 1024);
     const size_t rows = std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4);
     if (c->d_partials.n < static_cast<size_t>(n_blocks) * SART_ACC_COUNT) {
       SART_HIP(hipStreamSynchronize(c->stream));
       if (int rc = c->d_partials.resize(rows * SART_ACC_COUNT)) return rc;
     }
-    if (c->d_shell_partials.n < static_cast<size_t>(n_blocks) * kMaxShells * kShellPartialSlots) {
+    DevBuf<double>& table_partials = c->*bd.kind->partials;
+    if (table_partials.n < static_cast<size_t>(n_blocks) * bd.kind->partial_slots) {
       SART_HIP(hipStreamSynchronize(c->stream));
-      if (int rc = c->d_shell_partials.resize(rows * kMaxShells * kShellPartialSlots)) return rc;
+      if (int rc = table_partials.resize(rows * bd.kind->partial_slots)) return rc;
     }
     a.partials = c->d_partials.p;
-    ShellArgs sh;
-    std::memset(&sh, 0, sizeof sh);
-    sh.block = shells_dev;
-    sh.partials = c->d_shell_partials.p;
-    sh.n_shells = c->setup.n_shells;
-    sh.n_energies1 = c->n_energies + 1;
     {
       TimedLaunch tl(c);
-      launch_shell_histogram(c->hot, c->hotb, c->d_blob.p, a, acc_dev, sh, n_blocks, c->stream, rotated, fixed);
-    }
-    SART_HIP(hipGetLastError());
-    return 0;
-  }
-  if (chan_dev) {
-    const bool rotated = c->params.rotated != 0;   // generic variants: hist_variant_of 1 / 2
-    if (c->blocks_per_cu_channels[rotated] == 0) {
-      c->blocks_per_cu_channels[rotated] = std::max(1, channel_histogram_blocks_per_cu(rotated));
-      if (c->knobs.hist_blocks_per_cu > 0) c->blocks_per_cu_channels[rotated] = c->knobs.hist_blocks_per_cu;
-    }
-    const int n_blocks = grid_for(a.n_rays, c->n_cu, c->blocks_per_cu_channels[rotated], 1024);
-    const size_t rows = std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4);
-    if (c->d_partials.n < static_cast<size_t>(n_blocks) * SART_ACC_COUNT) {
-      SART_HIP(hipStreamSynchronize(c->stream));
-      if (int rc = c->d_partials.resize(rows * SART_ACC_COUNT)) return rc;
-    }
-    if (c->d_chan_partials.n < static_cast<size_t>(n_blocks) * kMaxChannels * kChanPartialSlots) {
-      SART_HIP(hipStreamSynchronize(c->stream));
-      if (int rc = c->d_chan_partials.resize(rows * kMaxChannels * kChanPartialSlots)) return rc;
-    }
-    a.partials = c->d_partials.p;
-    ChannelArgs ch;
-    std::memset(&ch, 0, sizeof ch);
-    ch.block = chan_dev;
-    ch.partials = c->d_chan_partials.p;
-    ch.frac = c->d_chan_frac.p;
-    ch.n_channels = c->n_channels;
-    ch.stride = c->chan_stride;
-    ch.n_radii = c->n_radii;
-    ch.n_energies = c->n_energies;
-    ch.n_energies1 = c->n_energies + 1;
-    {
-      TimedLaunch tl(c);
-      launch_channel_histogram(c->hot, c->hotb, c->d_blob.p, a, acc_dev, ch, n_blocks, c->stream, rotated, fixed);
+      bd.kind->launch(c, a, acc_dev, bd.dev, n_blocks, rotated, fixed);
     }
     SART_HIP(hipGetLastError());
     return 0;
@@ -2055,7 +2032,8 @@ int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_
   return 0;
 }
 
-// params that a shell launch and its finalize accept (the context stays as it is otherwise)
+// params that a shell launch and its finalize accept (the context stays as it is otherwise): the image and spectra checks of every
+// breakdown
 int shells_check(sart_context* c, const sart_trace_params_t* p) {
   if ((p->image_nx < 1 || p->image_ny < 1) && !(p->image_nx == 0 && p->image_ny == 0)) return fail(SART_ERR_INVALID_ARGUMENT, "invalid image specification");
   if (p->image_nx > 0 && (!(p->image_x_max > p->image_x_min) || !(p->image_y_max > p->image_y_min)))
@@ -2065,12 +2043,87 @@ int shells_check(sart_context* c, const sart_trace_params_t* p) {
   if (!c->have_setup) return fail(SART_ERR_NOT_READY, "no setup");
   return 0;
 }
+// params that a channel launch and its finalize accept (the context stays as it is otherwise)
+int channels_check(sart_context* c, const sart_trace_params_t* p) {
+  if (int rc = shells_check(c, p)) return rc;
+  if (c->setup.test_active) return fail(SART_ERR_INVALID_ARGUMENT, "the X-ray test source is active: no solar sampling, no emission channels");
+  if (!c->have_solar || !c->have_channels) return fail(SART_ERR_NOT_READY, "no source channels (sart_set_source_channels)");
+  return 0;
+}
+
+void launch_shells(sart_context* c, const TraceArgs& a, double* acc_dev, double* block_dev, int n_blocks, bool rotated, bool fixed) {
+  ShellArgs sh;
+  std::memset(&sh, 0, sizeof sh);
+  sh.block = block_dev;
+  sh.partials = c->d_shell_partials.p;
+  sh.n_shells = c->setup.n_shells;
+  sh.n_energies1 = c->n_energies + 1;
+  launch_shell_histogram(c->hot, c->hotb, c->d_blob.p, a, acc_dev, sh, n_blocks, c->stream, rotated, fixed);
+}
+void launch_channels(sart_context* c, const TraceArgs& a, double* acc_dev, double* block_dev, int n_blocks, bool rotated, bool fixed) {
+  ChannelArgs ch;
+  std::memset(&ch, 0, sizeof ch);
+  ch.block = block_dev;
+  ch.partials = c->d_chan_partials.p;
+  ch.frac = c->d_chan_frac.p;
+  ch.n_channels = c->n_channels;
+  ch.stride = c->chan_stride;
+  ch.n_radii = c->n_radii;
+  ch.n_energies = c->n_energies;
+  ch.n_energies1 = c->n_energies + 1;
+  launch_channel_histogram(c->hot, c->hotb, c->d_blob.p, a, acc_dev, ch, n_blocks, c->stream, rotated, fixed);
+}
+
+const Breakdown kShells = {kShellImageTileMax, kShellImageTileExtraMax, static_cast<size_t>(kMaxShells) * kShellPartialSlots,
+                           &sart_context::d_shell_partials, &sart_context::blocks_per_cu_shells, shell_histogram_blocks_per_cu,
+                           shell_block_len_of, launch_shells, shells_check, &sart_context::d_sblock, &sart_context::d_sblock_fin,
+                           sart_finalize_shells_device};
+const Breakdown kChannels = {kChanImageTileMax, kChanImageTileExtraMax, static_cast<size_t>(kMaxChannels) * kChanPartialSlots,
+                             &sart_context::d_chan_partials, &sart_context::blocks_per_cu_channels, channel_histogram_blocks_per_cu,
+                             channel_block_len_of, launch_channels, channels_check, &sart_context::d_cblock, &sart_context::d_cblock_fin,
+                             sart_finalize_channels_device};
+
+// The blocking form of a breakdown (sart_trace_histogram_shells / sart_trace_histogram_channels): launch into the context's scratch
+// accumulator and block, finalize both in FIXED64, copy out what the caller asked for.
+int trace_histogram_breakdown(sart_context* c, const sart_trace_params_t* p, const Breakdown& kind, double* image_out,
+                              sart_summary_t* summary, double* spectra_out, double* block_out) {
+  if (!c || !p) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (int rc = kind.check(c, p)) return rc;
+  SART_HIP(hipSetDevice(c->device));
+  DevBuf<double>& block = c->*kind.block;
+  DevBuf<double>& block_fin = c->*kind.block_fin;
+  const size_t len = acc_len_of(c, p), blen = kind.block_len(c, p);
+  if (int rc = c->d_sacc.reserve(len)) return rc;
+  if (int rc = block.reserve(blen)) return rc;
+  sart_trace_params_t q = *p;
+  q.accumulate = 0;   // the blocking form has no accumulator the caller could add into
+  if (int rc = histogram_launch(c, &q, c->d_sacc.p, {&kind, block.p})) return rc;
+  const double* src = c->d_sacc.p;
+  const double* bsrc = block.p;
+  if (c->accum_mode == SART_ACCUM_FIXED64) {
+    if (int rc = c->d_sacc_fin.reserve(len)) return rc;
+    if (int rc = block_fin.reserve(blen)) return rc;
+    if (int rc = sart_finalize_accumulator_device(c, p, c->d_sacc.p, c->d_sacc_fin.p)) return rc;
+    if (int rc = kind.finalize(c, p, block.p, block_fin.p)) return rc;
+    src = c->d_sacc_fin.p;
+    bsrc = block_fin.p;
+  }
+  const size_t nimg = static_cast<size_t>(p->image_nx) * p->image_ny;
+  if (image_out && nimg) SART_HIP(hipMemcpyAsync(image_out, src, nimg * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (summary) SART_HIP(hipMemcpyAsync(summary->v, src + nimg, SART_ACC_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (spectra_out && p->spectra)
+    SART_HIP(hipMemcpyAsync(spectra_out, src + nimg + SART_ACC_COUNT, (len - nimg - SART_ACC_COUNT) * sizeof(double),
+                            hipMemcpyDeviceToHost, c->stream));
+  if (block_out) SART_HIP(hipMemcpyAsync(block_out, bsrc, blen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  SART_HIP(hipStreamSynchronize(c->stream));
+  return status_take(c);
+}
 
 }  // namespace
 
 int sart_trace_histogram_device(sart_context* c, const sart_trace_params_t* p, double* acc_dev) {
   if (!c || !acc_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
-  return histogram_launch(c, p, acc_dev, nullptr);
+  return histogram_launch(c, p, acc_dev);
 }
 
 size_t sart_shell_block_len(int32_t n_shells, int32_t n_energies, int32_t spectra) {
@@ -2081,7 +2134,7 @@ size_t sart_shell_block_len(int32_t n_shells, int32_t n_energies, int32_t spectr
 int sart_trace_histogram_shells_device(sart_context* c, const sart_trace_params_t* p, double* acc_dev, double* shells_dev) {
   if (!c || !p || !acc_dev || !shells_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
   if (int rc = shells_check(c, p)) return rc;
-  return histogram_launch(c, p, acc_dev, shells_dev);
+  return histogram_launch(c, p, acc_dev, {&kShells, shells_dev});
 }
 
 int sart_finalize_shells_device(sart_context* c, const sart_trace_params_t* p, const void* raw_dev, double* out_dev) {
@@ -2098,34 +2151,7 @@ int sart_finalize_shells_device(sart_context* c, const sart_trace_params_t* p, c
 
 int sart_trace_histogram_shells(sart_context* c, const sart_trace_params_t* p, double* image_out, sart_summary_t* summary,
                                 double* spectra_out, double* shells_out) {
-  if (!c || !p) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (int rc = shells_check(c, p)) return rc;
-  SART_HIP(hipSetDevice(c->device));
-  const size_t len = acc_len_of(c, p), slen = shell_block_len_of(c, p);
-  if (int rc = c->d_sacc.reserve(len)) return rc;
-  if (int rc = c->d_sblock.reserve(slen)) return rc;
-  sart_trace_params_t q = *p;
-  q.accumulate = 0;   // the blocking form has no accumulator the caller could add into
-  if (int rc = histogram_launch(c, &q, c->d_sacc.p, c->d_sblock.p)) return rc;
-  const double* src = c->d_sacc.p;
-  const double* ssrc = c->d_sblock.p;
-  if (c->accum_mode == SART_ACCUM_FIXED64) {
-    if (int rc = c->d_sacc_fin.reserve(len)) return rc;
-    if (int rc = c->d_sblock_fin.reserve(slen)) return rc;
-    if (int rc = sart_finalize_accumulator_device(c, p, c->d_sacc.p, c->d_sacc_fin.p)) return rc;
-    if (int rc = sart_finalize_shells_device(c, p, c->d_sblock.p, c->d_sblock_fin.p)) return rc;
-    src = c->d_sacc_fin.p;
-    ssrc = c->d_sblock_fin.p;
-  }
-  const size_t nimg = static_cast<size_t>(p->image_nx) * p->image_ny;
-  if (image_out && nimg) SART_HIP(hipMemcpyAsync(image_out, src, nimg * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (summary) SART_HIP(hipMemcpyAsync(summary->v, src + nimg, SART_ACC_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (spectra_out && p->spectra)
-    SART_HIP(hipMemcpyAsync(spectra_out, src + nimg + SART_ACC_COUNT, (len - nimg - SART_ACC_COUNT) * sizeof(double),
-                            hipMemcpyDeviceToHost, c->stream));
-  if (shells_out) SART_HIP(hipMemcpyAsync(shells_out, ssrc, slen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  SART_HIP(hipStreamSynchronize(c->stream));
-  return status_take(c);
+  return trace_histogram_breakdown(c, p, kShells, image_out, summary, spectra_out, shells_out);
 }
 
 // ---- emission-channel breakdown (include/sart.h) --------------------------------------------
@@ -2173,14 +2199,6 @@ int channels_args_check(sart_context* c, const double* rates, const double* tota
   if (nR != c->n_radii || nE != c->n_energies)
     return fail(SART_ERR_INVALID_ARGUMENT, "n_radii / n_energies are not those of the context's solar tables (" +
                                                std::to_string(c->n_radii) + " x " + std::to_string(c->n_energies) + ")");
-  return 0;
-}
-
-// params that a channel launch and its finalize accept (the context stays as it is otherwise)
-int channels_check(sart_context* c, const sart_trace_params_t* p) {
-  if (int rc = shells_check(c, p)) return rc;
-  if (c->setup.test_active) return fail(SART_ERR_INVALID_ARGUMENT, "the X-ray test source is active: no solar sampling, no emission channels");
-  if (!c->have_solar || !c->have_channels) return fail(SART_ERR_NOT_READY, "no source channels (sart_set_source_channels)");
   return 0;
 }
 
@@ -2240,7 +2258,7 @@ size_t sart_channel_block_len(int32_t n_channels, int32_t n_energies, int32_t sp
 int sart_trace_histogram_channels_device(sart_context* c, const sart_trace_params_t* p, double* acc_dev, double* chan_dev) {
   if (!c || !p || !acc_dev || !chan_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
   if (int rc = channels_check(c, p)) return rc;
-  return histogram_launch(c, p, acc_dev, nullptr, chan_dev);
+  return histogram_launch(c, p, acc_dev, {&kChannels, chan_dev});
 }
 
 int sart_finalize_channels_device(sart_context* c, const sart_trace_params_t* p, const void* raw_dev, double* out_dev) {
@@ -2258,34 +2276,7 @@ int sart_finalize_channels_device(sart_context* c, const sart_trace_params_t* p,
 
 int sart_trace_histogram_channels(sart_context* c, const sart_trace_params_t* p, double* image_out, sart_summary_t* summary,
                                   double* spectra_out, double* channels_out) {
-  if (!c || !p) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (int rc = channels_check(c, p)) return rc;
-  SART_HIP(hipSetDevice(c->device));
-  const size_t len = acc_len_of(c, p), clen = channel_block_len_of(c, p);
-  if (int rc = c->d_sacc.reserve(len)) return rc;
-  if (int rc = c->d_cblock.reserve(clen)) return rc;
-  sart_trace_params_t q = *p;
-  q.accumulate = 0;   // the blocking form has no accumulator the caller could add into
-  if (int rc = histogram_launch(c, &q, c->d_sacc.p, nullptr, c->d_cblock.p)) return rc;
-  const double* src = c->d_sacc.p;
-  const double* csrc = c->d_cblock.p;
-  if (c->accum_mode == SART_ACCUM_FIXED64) {
-    if (int rc = c->d_sacc_fin.reserve(len)) return rc;
-    if (int rc = c->d_cblock_fin.reserve(clen)) return rc;
-    if (int rc = sart_finalize_accumulator_device(c, p, c->d_sacc.p, c->d_sacc_fin.p)) return rc;
-    if (int rc = sart_finalize_channels_device(c, p, c->d_cblock.p, c->d_cblock_fin.p)) return rc;
-    src = c->d_sacc_fin.p;
-    csrc = c->d_cblock_fin.p;
-  }
-  const size_t nimg = static_cast<size_t>(p->image_nx) * p->image_ny;
-  if (image_out && nimg) SART_HIP(hipMemcpyAsync(image_out, src, nimg * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (summary) SART_HIP(hipMemcpyAsync(summary->v, src + nimg, SART_ACC_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (spectra_out && p->spectra)
-    SART_HIP(hipMemcpyAsync(spectra_out, src + nimg + SART_ACC_COUNT, (len - nimg - SART_ACC_COUNT) * sizeof(double),
-                            hipMemcpyDeviceToHost, c->stream));
-  if (channels_out) SART_HIP(hipMemcpyAsync(channels_out, csrc, clen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  SART_HIP(hipStreamSynchronize(c->stream));
-  return status_take(c);
+  return trace_histogram_breakdown(c, p, kChannels, image_out, summary, spectra_out, channels_out);
 }
 
 int sart_trace_histogram(sart_context* c, const sart_trace_params_t* p, double* image_out, sart_summary_t* summary) {

@@ -326,6 +326,11 @@ static_assert(kTileExtraCells == kRingExtraCells + 16 * 512 / 8, "16 waves x 512
 constexpr int kImageTileMax = 64;
 constexpr int kImageTileExtraMax = 45;   // 45 x 45 <= kTileExtraCells: the tile of the variants whose rings are all in use
 
+// The two breakdowns of the histogram trace, per shell and per emission channel, are one pipeline: breakdown_histogram_body
+// (sart_kernels.hip) is the generic histogram kernel with a per-workgroup table in LDS, and shell_histogram_kernel and
+// channel_histogram_kernel are its two users (ShellBreakdown / ChannelBreakdown: the argument struct, the table, its cells).  What
+// follows is what each of them keeps in that table and hands to its fold.
+//
 // Per-shell breakdown of the histogram trace (include/sart.h: sart_trace_histogram_shells_device).  shell_histogram_kernel keeps,
 // per workgroup and shell, four u32 counters and two sums in LDS - in the last kShellTableCells cells behind the tables, where the
 // histogram kernels keep the end of the image tile (its tile is therefore at most kShellImageTileMax / kShellImageTileExtraMax wide)

@@ -2133,360 +2133,6 @@ static_assert(kShellImageTileMax * kShellImageTileMax <= kTileRingCells + kRingE
                   kShellImageTileExtraMax * kShellImageTileExtraMax <= kRingExtraCells - kShellTableCells,
               "the shell kernel's image tile leaves the shell table alone");
 
-template <int BLOCK, bool ROT, bool FIXED>
-__global__ __launch_bounds__(BLOCK) void shell_histogram_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
-                                                                double* __restrict__ acc, HotB HBarg, ShellArgs SHarg) {
-  using Sum = std::conditional_t<FIXED, long long, double>;   // per-lane sums: quanta (FIXED) or f64
-  struct LdsLayout {
-    TablesLds S;
-    double tile_extra[kRingExtraCells - kShellTableCells];   // cells kTileRingCells .. of the image tile
-    uint32_t shell_cnt[kMaxShells][4];                       // per shell: N_SELECTED, N_HIT_NICKEL, N_PASSED_TILL_WINDOW, N_PASSED
-    Sum shell_sum[kMaxShells][2];                            // per shell: sum of w, sum of w^2
-    DevBlob B;
-    TraceArgs Ab;
-    QueueLds<BLOCK / 64> Q;
-  };
-  __shared__ LdsLayout lds;
-  TablesLds& S = lds.S;
-  QueueLds<BLOCK / 64>& Q = lds.Q;
-  static_assert((offsetof(LdsLayout, Q) % 512) == 0, "the rings are addressed with ds_*2st64 offsets");
-  static_assert((BLOCK / 64) * kQueue == kTileRingCells, "ring 0 of this workgroup is the first part of the tile space");
-  static_assert(sizeof(lds.shell_cnt) + sizeof(lds.shell_sum) == kShellTableCells * sizeof(double), "the shell table's cells");
-  // cell t of the LDS image tile: ring 0 (stage A0 off: ray + u3hi columns, 128 doubles per wave), then the cells behind the tables
-  auto tile_cell = [&](uint32_t t) -> double* {
-    return t < (uint32_t)kTileRingCells ? reinterpret_cast<double*>(&Q.w[t >> 7].ray[0]) + (t & 127u)
-                                        : &lds.tile_extra[t - (uint32_t)kTileRingCells];
-  };
-  DevBlob& B = lds.B;
-  TraceArgs& Ab = lds.Ab;
-  {
-    const uint64_t* src = reinterpret_cast<const uint64_t*>(blob);
-    uint64_t* dst = reinterpret_cast<uint64_t*>(&B);
-    for (int i = threadIdx.x; i < (int)(sizeof(DevBlob) / 8); i += BLOCK) dst[i] = src[i];
-    if (threadIdx.x == 0) Ab = A;
-    __syncthreads();
-  }
-  const DevParams& Pb = B.P;
-  const DevTables& Tb = B.T;
-  {
-    uint64_t* q = reinterpret_cast<uint64_t*>(&Q);
-    for (int i = threadIdx.x; i < (int)(sizeof(Q) / 8); i += BLOCK) q[i] = 0ull;
-    for (int i = threadIdx.x; i < kRingExtraCells - kShellTableCells; i += BLOCK) lds.tile_extra[i] = 0.0;
-    for (int i = threadIdx.x; i < kMaxShells * 4; i += BLOCK) lds.shell_cnt[i >> 2][i & 3] = 0u;
-    for (int i = threadIdx.x; i < kMaxShells * 2; i += BLOCK) lds.shell_sum[i >> 1][i & 1] = 0;
-  }
-  stage_tables<BLOCK>(S, Pb, Tb);   // (its barrier orders the zeroing above before the first use)
-  const LdsTables L{S.sincos, S.rcdf_hi, Tb.flux_radius_cdf, S.rguide, S.shells, S.lut};
-
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint64_t waves_total = (uint64_t)gridDim.x * (BLOCK / 64);
-  const uint64_t wave_global = (uint64_t)blockIdx.x * (BLOCK / 64) + wave;
-  const bool early_reject = H.n_zones > 0;   // wave-uniform; the host builds no zones for the X-ray test source
-  const uint64_t first_chunk = A.ray_id_offset >> 8;
-  uint64_t id_base = first_chunk << 8;
-  asm volatile("" : "+s"(id_base));
-  const uint32_t rel_begin = (uint32_t)(A.ray_id_offset & 255u);
-  const uint32_t rel_end = rel_begin + (uint32_t)A.n_rays;
-  const uint32_t n_chunks = (rel_end + 255u) >> 8;
-
-  uint32_t n_reached = 0, n_shell = 0, n_nickel = 0, n_till = 0, n_passed = 0;   // wave-uniform
-  uint32_t n_outside = 0;    // per lane: passed rays outside the image
-  Sum sum_w = 0, sum_w2 = 0, sum_x = 0, sum_y = 0, sum_r = 0;
-  long long sum_wo = 0;      // FIXED: weights of the passed rays outside the image
-  uint32_t h0 = 0, t0 = 0;   // ring 0 (A0 -> A1)
-  uint32_t h1 = 0, t1 = 0;   // ring 1 (A1 -> B)
-  auto ring_sync = [] {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
-  auto prefix_of = [](uint64_t mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-  };
-  auto shell_of = [](int shell) { return min((uint32_t)shell, (uint32_t)(kMaxShells - 1)); };   // (phase A: shell < n_shells <= 64)
-
-  // phase A as in trace_histogram_kernel's generic variants; every selected ray counts for its shell, those that the
-  // shell0_miss_radius compare ends here included (their shell is shell 0)
-  auto run_phase_a = [&](uint32_t rel, bool valid, uint32_t u3_hi) {
-    SART_STAGE_MARK("A1");
-    __builtin_amdgcn_s_setprio(SART_PRIO_A1);
-    RayState st;
-    bool sampled = false, reached = false;
-    double radial;
-    HotA Hl;
-    reload_hot(Hl);
-    LaneMasks M;
-    (void)phase_a<false, ROT ? 1 : 0, false, false>(Hl, Pb, L, A.seed_lo, A.seed_hi, id_base + (uint64_t)rel, u3_hi, st, sampled, reached, radial, M);
-    const uint64_t valid_m = ballot64(valid);
-    n_reached += (uint32_t)__popcll(valid_m & M.reached);
-    const uint64_t selected = valid_m & M.ok;
-    n_shell += (uint32_t)__popcll(selected);
-    if (__builtin_amdgcn_inverse_ballot_w64(selected))
-      __hip_atomic_fetch_add(&lds.shell_cnt[shell_of(st.shell)][0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    const uint64_t mask = selected & ~ballot64(radial < Pb.shell0_miss_radius);
-    const uint32_t cnt = (uint32_t)__popcll(mask);
-    if (__builtin_amdgcn_inverse_ballot_w64(mask)) {
-      const uint32_t slot = (t1 + prefix_of(mask)) % kQueue;
-      Q.w[wave].X0[slot] = st.X0; Q.w[wave].Y0[slot] = st.Y0;
-      Q.w[wave].tsx[slot] = st.tsx; Q.w[wave].tsy[slot] = st.tsy;
-      Q.w[wave].path[slot] = st.path_cb;
-      Q.w[wave].u5[slot] = st.u5;
-      Q.w[wave].idx[slot] = st.r_idx | (st.shell << 16);
-    }
-    t1 += cnt;
-    __builtin_amdgcn_s_setprio(0);
-  };
-
-  auto run_phase_b = [&](uint32_t n_valid) {
-    SART_STAGE_MARK("B");
-    __builtin_amdgcn_s_setprio(SART_PRIO_B);
-    RayState st;
-    const bool valid = (uint32_t)lane < n_valid;
-    const uint32_t slot = (h1 + (uint32_t)lane) % kQueue;
-    RayOut out;
-    {
-      st.X0 = Q.w[wave].X0[slot]; st.Y0 = Q.w[wave].Y0[slot];
-      st.tsx = Q.w[wave].tsx[slot]; st.tsy = Q.w[wave].tsy[slot];
-      st.path_cb = Q.w[wave].path[slot];
-      st.u5 = Q.w[wave].u5[slot];
-      st.u5_hi = upper32_of_uniform(st.u5);   // u5 = word / 2^32 (uniforms_of): the word back, exactly
-      if (!ROT) {
-        st.zcb = -(H.dz3 - H.dz1);
-      } else {
-        st.zcb = zcb_rotated(Pb.rx_s, -Pb.rx_c * Pb.ry_s, Pb.rx_c * Pb.ry_c, Pb.half_length_telescope, st.X0 + Pb.entrance_x,
-                             st.Y0 + Pb.entrance_y, st.tsx, st.tsy, H.dz3 - H.dz1);
-      }
-      const int packed = Q.w[wave].idx[slot];
-      st.r_idx = packed & 0xFFFF;
-      st.shell = packed >> 16;
-      const DevBlob& Bo = lds_opaque(B);
-      HotB HB;
-      reload_kernarg(HB, offsetof(ShellKernArgs, HB));
-      asm volatile("" :: "s"(HB.cdf_hi32), "s"(HB.energy_guide), "s"(HB.energy_tab), "s"(HB.refl), "s"(HB.refl_n_angles), "s"(HB.cdf_stride));
-      phase_b<false, false, -1, false>(Bo.P, L, HB, lds_opaque(Ab), st, H.test_active ? Pb.n_energies : -1, valid, out, nullptr);
-    }
-    h1 += n_valid;
-    __builtin_amdgcn_s_setprio(SART_PRIO_ACC);
-    n_nickel += (uint32_t)__popcll(out.m_nickel);
-    n_till += (uint32_t)__popcll(out.m_till);
-    n_passed += (uint32_t)__popcll(out.m_passed);
-    const uint32_t sh = shell_of(st.shell);
-    if (__builtin_amdgcn_inverse_ballot_w64(out.m_nickel))
-      __hip_atomic_fetch_add(&lds.shell_cnt[sh][1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (__builtin_amdgcn_inverse_ballot_w64(out.m_till))
-      __hip_atomic_fetch_add(&lds.shell_cnt[sh][2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (out.passed) {
-      SART_STAGE_MARK("ACC");
-      TraceArgs Al;
-      reload_kernarg(Al, offsetof(ShellKernArgs, A));
-      asm volatile("" :: "s"(Al.replicas), "s"(Al.replica_mask), "s"(Al.replica_stride), "s"(Al.image_nx), "s"(Al.image_ny),
-                   "s"(Al.image_x_min), "s"(Al.image_y_min), "s"(Al.image_inv_step_x), "s"(Al.image_inv_step_y), "s"(Al.spectra),
-                   "s"(Al.tile_x0), "s"(Al.tile_y0), "s"(Al.tile_n), "s"(Al.tile_base));
-      __hip_atomic_fetch_add(&lds.shell_cnt[sh][3], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      long long w_fx = 0;   // FIXED: this ray's weight in quanta (what the image, the sums and the spectra add)
-      if constexpr (FIXED) {
-        w_fx = to_fixed(out.weight, Al.fx_scale_w);
-        const long long w2_fx = to_fixed(out.weight * out.weight, Al.fx_scale_w2);
-        sum_w += w_fx;
-        sum_w2 += w2_fx;
-        sum_x += to_fixed(out.px, kFixedPositionScale);
-        sum_y += to_fixed(out.py, kFixedPositionScale);
-        sum_r += to_fixed(out.rdet, kFixedPositionScale);
-        // the same integers the scalars add: the per-shell sums add up to SUM_WEIGHTS / SUM_WEIGHTS_SQ exactly
-        __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(&lds.shell_sum[sh][0]), (unsigned long long)w_fx, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(&lds.shell_sum[sh][1]), (unsigned long long)w2_fx, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_WORKGROUP);
-      } else {
-        sum_w += out.weight;
-        sum_w2 = fma(out.weight, out.weight, sum_w2);
-        sum_x += out.px;
-        sum_y += out.py;
-        sum_r += out.rdet;
-        __hip_atomic_fetch_add(&lds.shell_sum[sh][0], out.weight, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(&lds.shell_sum[sh][1], out.weight * out.weight, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      }
-      // prepareHeatmap (:838-842), as trace_histogram_kernel bins it
-      const double fx = (out.px - Al.image_x_min) * Al.image_inv_step_x;
-      const double fy = (out.py - Al.image_y_min) * Al.image_inv_step_y;
-      const int nx = Al.image_nx, ny = Al.image_ny;
-      const uint64_t inside_m = ballot64(fx >= 0.0) & ballot64(fx < (double)nx) & ballot64(fy >= 0.0) & ballot64(fy < (double)ny);
-      const bool inside = __builtin_amdgcn_inverse_ballot_w64(inside_m);
-      n_outside += inside ? 0u : 1u;
-      if constexpr (FIXED) {
-        if (out.m_passed & ~inside_m) sum_wo += inside ? 0ll : w_fx;
-      }
-      double* const img = Al.replicas + (size_t)((uint32_t)wave_global & Al.replica_mask) * (size_t)Al.replica_stride;
-      if (inside) {
-        const uint32_t ix = (uint32_t)(int)fx, iy = (uint32_t)(int)fy;
-        const uint32_t tn = (uint32_t)Al.tile_n;
-        const uint32_t tx = ix - (uint32_t)Al.tile_x0, ty = iy - (uint32_t)Al.tile_y0;
-        if ((tx < tn) & (ty < tn)) {
-          const uint32_t t = ty * tn + tx + (uint32_t)Al.tile_base;   // < kTileRingCells + kRingExtraCells - kShellTableCells (host)
-          if constexpr (FIXED)
-            __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(tile_cell(t)), (unsigned long long)w_fx, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_WORKGROUP);
-          else
-            __hip_atomic_fetch_add(tile_cell(t), out.weight, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        } else {
-          const uint32_t pix = iy * (uint32_t)nx + ix;
-          typedef __attribute__((address_space(1))) char* gbytes;
-          if constexpr (FIXED) atomic_add_slot_i64((double*)((gbytes)img + pix * 8u), w_fx);
-          else unsafeAtomicAdd((double*)((gbytes)img + pix * 8u), out.weight);
-        }
-      }
-      if (Al.spectra) {   // wave-uniform: the spectra behind the scalars, and the same energy bins per shell in the block
-        double* rad = acc + (size_t)nx * (size_t)ny + SART_ACC_COUNT;
-        double* en = rad + 2 * (size_t)Al.n_radial_bins;
-        const size_t ne1 = (size_t)Pb.n_energies + 1;
-        const int rb = min((int)(out.rdet * Al.radial_inv_bin), Al.n_radial_bins - 1);
-        ShellArgs SHl;
-        reload_kernarg(SHl, offsetof(ShellKernArgs, SH));
-        double* const sen = SHl.block + (size_t)SHl.n_shells * SART_SHELL_ROW + (size_t)sh * ne1 + (size_t)out.e_idx;   // counts[sh][e]
-        const size_t sw_off = (size_t)SHl.n_shells * ne1;                                                             // -> weights[sh][e]
-        if constexpr (FIXED) {
-          atomic_add_slot_i64(&rad[rb], 1);
-          atomic_add_slot_i64(&rad[(size_t)Al.n_radial_bins + rb], w_fx);
-          atomic_add_slot_i64(&en[out.e_idx], 1);
-          atomic_add_slot_i64(&en[ne1 + out.e_idx], w_fx);
-          atomic_add_slot_i64(&en[2 * ne1 + out.e_idx], to_fixed(out.reflect, kFixedReflectScale));
-          atomic_add_slot_i64(sen, 1);
-          atomic_add_slot_i64(sen + sw_off, w_fx);
-        } else {
-          unsafeAtomicAdd(&rad[rb], 1.0);
-          unsafeAtomicAdd(&rad[(size_t)Al.n_radial_bins + rb], out.weight);
-          unsafeAtomicAdd(&en[out.e_idx], 1.0);
-          unsafeAtomicAdd(&en[ne1 + out.e_idx], out.weight);
-          unsafeAtomicAdd(&en[2 * ne1 + out.e_idx], out.reflect);
-          unsafeAtomicAdd(sen, 1.0);
-          unsafeAtomicAdd(sen + sw_off, out.weight);
-        }
-      }
-    }
-    __builtin_amdgcn_s_setprio(0);
-  };
-
-  // stage A0 as in the generic histogram variants (zone bounds re-read from the kernel arguments per pass)
-  uint32_t chunk = (uint32_t)wave_global;
-  const uint32_t lane4 = 4u * (uint32_t)lane;
-  uint32_t pass = 0;
-  U4 stream = U4{0u, 0u, 0u, 0u};
-  for (;;) {
-    const bool have_new = chunk < n_chunks;   // wave-uniform
-    SART_STAGE_MARK("LOOP");
-    if (have_new) {
-      SART_STAGE_MARK("A0");
-      if (pass == 0u) stream = stream_block(((first_chunk + (uint64_t)chunk) << 6) + (uint64_t)lane, A.seed_lo, A.seed_hi);
-      const uint32_t w = word_of(stream, pass);
-      const uint32_t rel = ((chunk << 8) + pass) + lane4;
-      if (early_reject) {
-        ZoneTable Z;
-        reload_zones(Z);
-        uint64_t dead_m = 0, reached_m = 0;
-#pragma unroll
-        for (int z = 0; z < kMaxZones; ++z) {
-          const uint64_t in = ballot64(w >= Z.lo[z]) & ballot64(w <= Z.hi[z]);
-          dead_m |= in;
-          reached_m |= ((Z.zone_reached >> z) & 1u) ? in : 0ull;
-        }
-        const uint32_t chunk_lo = chunk << 8;
-        uint64_t valid_m = ~0ull;
-        if ((chunk_lo < rel_begin) | (chunk_lo + 256u > rel_end)) valid_m = ballot64(rel >= rel_begin) & ballot64(rel < rel_end);
-        n_reached += (uint32_t)__popcll(valid_m & reached_m);
-        const uint64_t mask = valid_m & ~dead_m;
-        if (__builtin_amdgcn_inverse_ballot_w64(mask)) {
-          const uint32_t slot = (t0 + prefix_of(mask)) % kQueue;
-          Q.w[wave].ray[slot] = rel;
-          Q.w[wave].u3hi[slot] = w;
-        }
-        t0 += (uint32_t)__popcll(mask);
-      } else {
-        run_phase_a(rel, (rel >= rel_begin) & (rel < rel_end), w);
-      }
-      pass = (pass + 1u) & 3u;
-      if (pass == 0u) chunk += (uint32_t)waves_total;
-      ring_sync();
-    }
-    if (early_reject) {
-      const uint32_t n0 = t0 - h0;
-      if ((n0 >= 64u) | (!have_new & (n0 > 0u))) {
-        const uint32_t m = min(n0, 64u);
-        const bool v = (uint32_t)lane < m;
-        const uint32_t slot = (h0 + (uint32_t)lane) % kQueue;
-        const uint32_t rel = Q.w[wave].ray[slot];
-        const uint32_t w = Q.w[wave].u3hi[slot];
-        h0 += m;
-        run_phase_a(rel, v, w);
-        ring_sync();
-      }
-    }
-    const uint32_t n1 = t1 - h1;
-    const bool draining = !have_new & (t0 == h0);
-    if ((n1 >= 64u) | (draining & (n1 > 0u))) {
-      run_phase_b(min(n1, 64u));
-      ring_sync();
-    }
-    if (draining & (t1 == h1)) break;
-  }
-
-  SART_STAGE_MARK("EPILOGUE");
-  // flush of the LDS image tile: one global atomic per non-empty tile pixel and workgroup
-  if (A.tile_n > 0) {
-    __syncthreads();
-    const uint32_t tn = (uint32_t)A.tile_n, n_tile = tn * tn;
-    double* const img = A.replicas + (size_t)((uint32_t)wave_global & A.replica_mask) * (size_t)A.replica_stride;
-    for (uint32_t t = threadIdx.x; t < n_tile; t += BLOCK) {
-      const double v = *tile_cell(t + (uint32_t)A.tile_base);
-      if (__double_as_longlong(v) != 0ll) {
-        const uint32_t ty = t / tn, tx = t - ty * tn;
-        double* const px = &img[(size_t)((uint32_t)A.tile_y0 + ty) * (size_t)A.image_nx + ((uint32_t)A.tile_x0 + tx)];
-        if constexpr (FIXED) atomic_add_slot_i64(px, __double_as_longlong(v));
-        else unsafeAtomicAdd(px, v);
-      }
-    }
-  }
-  // scalars: as trace_histogram_kernel (wave reduction -> LDS staging in wave 0's first ring columns -> one store per workgroup)
-  __syncthreads();
-  Sum (*const red)[SART_ACC_COUNT] = reinterpret_cast<Sum (*)[SART_ACC_COUNT]>(&Q.w[0].X0[0]);
-  Sum sw, sw2, sxx, syy, srr;
-  if constexpr (FIXED) {
-    sw = wave_sum_i64(sum_w); sw2 = wave_sum_i64(sum_w2); sxx = wave_sum_i64(sum_x); syy = wave_sum_i64(sum_y); srr = wave_sum_i64(sum_r);
-  } else {
-    sw = wave_sum(sum_w); sw2 = wave_sum(sum_w2); sxx = wave_sum(sum_x); syy = wave_sum(sum_y); srr = wave_sum(sum_r);
-  }
-  const long long swo = FIXED ? wave_sum_i64(sum_wo) : 0ll;
-  const long long n_out = wave_sum_i64((long long)n_outside);
-  if (lane == 0) {
-    Sum* r = red[wave];
-    for (int k = 0; k < SART_ACC_COUNT; ++k) r[k] = 0;
-    r[SART_ACC_SUM_WEIGHTS] = sw;
-    r[SART_ACC_SUM_WEIGHTS_SQ] = sw2;
-    r[SART_ACC_SUM_X] = sxx;
-    r[SART_ACC_SUM_Y] = syy;
-    r[SART_ACC_SUM_R] = srr;
-    r[SART_ACC_N_PASSED] = (Sum)n_passed;
-    r[SART_ACC_N_PASSED_TILL_WINDOW] = (Sum)n_till;
-    r[SART_ACC_N_HIT_NICKEL] = (Sum)n_nickel;
-    r[SART_ACC_N_REACHED_TELESCOPE] = (Sum)n_reached;
-    r[SART_ACC_N_SHELL_SELECTED] = (Sum)n_shell;
-    r[SART_ACC_N_OUTSIDE_IMAGE] = (Sum)n_out;
-    if constexpr (FIXED) r[SART_ACC_SUM_WEIGHTS_OUTSIDE] = swo;
-  }
-  __syncthreads();
-  if (threadIdx.x < SART_ACC_COUNT) {
-    Sum t = 0;
-    for (int w = 0; w < BLOCK / 64; ++w) t += red[w][threadIdx.x];
-    reinterpret_cast<Sum*>(A.partials)[(size_t)blockIdx.x * SART_ACC_COUNT + threadIdx.x] = t;
-  }
-  // the shell table of this workgroup (every wave has left the loop: the barriers above)
-  for (int i = threadIdx.x; i < kMaxShells * kShellPartialSlots; i += BLOCK) {
-    const int s = i / kShellPartialSlots, j = i - s * kShellPartialSlots;
-    const Sum v = j < 4 ? (Sum)lds.shell_cnt[s][j] : lds.shell_sum[s][j - 4];
-    reinterpret_cast<Sum*>(SHarg.partials)[(size_t)blockIdx.x * (kMaxShells * kShellPartialSlots) + i] = v;
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
 // emission-channel breakdown of the histogram trace (include/sart.h: sart_trace_histogram_channels_device)
 // ------------------------------------------------------------------------------------------------
@@ -2511,15 +2157,44 @@ static_assert(offsetof(ChanKernArgs, A) == offsetof(HistKernArgs, A) && offsetof
                   offsetof(ChanKernArgs, CH) == offsetof(HistKernArgs, SC),
               "the channel kernel shares the argument offsets of the histogram kernel");
 
-template <int BLOCK, bool ROT, bool FIXED>
-__global__ __launch_bounds__(BLOCK) void channel_histogram_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
-                                                                  double* __restrict__ acc, HotB HBarg, ChannelArgs CHarg) {
+// ------------------------------------------------------------------------------------------------
+// the one pipeline of both breakdowns: breakdown_histogram_body
+// ------------------------------------------------------------------------------------------------
+// What a breakdown is to the body: its argument struct and where the kernel arguments hold it, its per-workgroup table in LDS (in
+// the last kTableCells cells behind the tables, the image tile's extra cells in front of it) and the slots it stores of it per
+// workgroup.  What the breakdown does to a ray stands in the body itself, under `if constexpr (BD::kShells)`: one ray can be followed
+// through one function.
+struct ShellBreakdown {
+  static constexpr bool kShells = true;
+  using Args = ShellArgs;
+  static constexpr size_t kArgsOffset = offsetof(ShellKernArgs, SH);
+  static constexpr int kTableCells = kShellTableCells;
+  template <class Sum>
+  struct Table {
+    uint32_t cnt[kMaxShells][4];   // per shell: N_SELECTED, N_HIT_NICKEL, N_PASSED_TILL_WINDOW, N_PASSED
+    Sum sum[kMaxShells][2];        // per shell: sum of w, sum of w^2
+  };
+};
+struct ChannelBreakdown {
+  static constexpr bool kShells = false;
+  using Args = ChannelArgs;
+  static constexpr size_t kArgsOffset = offsetof(ChanKernArgs, CH);
+  static constexpr int kTableCells = kChanTableCells;
+  template <class Sum>
+  struct Table {
+    Sum sum[kMaxChannels][3][kChanLanes];     // per channel: sum of c, sum of c^2, sum of c outside the image
+    uint32_t cnt[kMaxChannels][kChanLanes];   // per channel: N_CONTRIBUTING
+  };
+};
+
+template <int BLOCK, bool ROT, bool FIXED, class BD>
+__device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* __restrict__ blob, TraceArgs A, double* __restrict__ acc,
+                                                         typename BD::Args BDarg) {
   using Sum = std::conditional_t<FIXED, long long, double>;   // per-lane sums: quanta (FIXED) or f64
   struct LdsLayout {
     TablesLds S;
-    double tile_extra[kRingExtraCells - kChanTableCells];    // cells kTileRingCells .. of the image tile
-    Sum chan_sum[kMaxChannels][3][kChanLanes];               // per channel: sum of c, sum of c^2, sum of c outside the image
-    uint32_t chan_cnt[kMaxChannels][kChanLanes];             // per channel: N_CONTRIBUTING
+    double tile_extra[kRingExtraCells - BD::kTableCells];   // cells kTileRingCells .. of the image tile
+    typename BD::template Table<Sum> tab;
     DevBlob B;
     TraceArgs Ab;
     QueueLds<BLOCK / 64> Q;
@@ -2529,7 +2204,7 @@ __global__ __launch_bounds__(BLOCK) void channel_histogram_kernel(HotA H, const 
   QueueLds<BLOCK / 64>& Q = lds.Q;
   static_assert((offsetof(LdsLayout, Q) % 512) == 0, "the rings are addressed with ds_*2st64 offsets");
   static_assert((BLOCK / 64) * kQueue == kTileRingCells, "ring 0 of this workgroup is the first part of the tile space");
-  static_assert(sizeof(lds.chan_cnt) + sizeof(lds.chan_sum) == kChanTableCells * sizeof(double), "the channel table's cells");
+  static_assert(sizeof(lds.tab) == BD::kTableCells * sizeof(double), "the breakdown table's cells");
   // cell t of the LDS image tile: ring 0 (stage A0 off: ray + u3hi columns, 128 doubles per wave), then the cells behind the tables
   auto tile_cell = [&](uint32_t t) -> double* {
     return t < (uint32_t)kTileRingCells ? reinterpret_cast<double*>(&Q.w[t >> 7].ray[0]) + (t & 127u)
@@ -2549,9 +2224,14 @@ __global__ __launch_bounds__(BLOCK) void channel_histogram_kernel(HotA H, const 
   {
     uint64_t* q = reinterpret_cast<uint64_t*>(&Q);
     for (int i = threadIdx.x; i < (int)(sizeof(Q) / 8); i += BLOCK) q[i] = 0ull;
-    for (int i = threadIdx.x; i < kRingExtraCells - kChanTableCells; i += BLOCK) lds.tile_extra[i] = 0.0;
-    for (int i = threadIdx.x; i < kMaxChannels * 3 * kChanLanes; i += BLOCK) (&lds.chan_sum[0][0][0])[i] = 0;
-    if (threadIdx.x < kMaxChannels * kChanLanes) (&lds.chan_cnt[0][0])[threadIdx.x] = 0u;
+    for (int i = threadIdx.x; i < kRingExtraCells - BD::kTableCells; i += BLOCK) lds.tile_extra[i] = 0.0;
+    if constexpr (BD::kShells) {
+      for (int i = threadIdx.x; i < kMaxShells * 4; i += BLOCK) lds.tab.cnt[i >> 2][i & 3] = 0u;
+      for (int i = threadIdx.x; i < kMaxShells * 2; i += BLOCK) lds.tab.sum[i >> 1][i & 1] = 0;
+    } else {
+      for (int i = threadIdx.x; i < kMaxChannels * 3 * kChanLanes; i += BLOCK) (&lds.tab.sum[0][0][0])[i] = 0;
+      if (threadIdx.x < kMaxChannels * kChanLanes) (&lds.tab.cnt[0][0])[threadIdx.x] = 0u;
+    }
   }
   stage_tables<BLOCK>(S, Pb, Tb);   // (its barrier orders the zeroing above before the first use)
   const LdsTables L{S.sincos, S.rcdf_hi, Tb.flux_radius_cdf, S.rguide, S.shells, S.lut};
@@ -2582,8 +2262,10 @@ __global__ __launch_bounds__(BLOCK) void channel_histogram_kernel(HotA H, const 
   auto prefix_of = [](uint64_t mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
   };
+  [[maybe_unused]] auto shell_of = [](int shell) { return min((uint32_t)shell, (uint32_t)(kMaxShells - 1)); };   // (phase A: shell < n_shells <= 64)
 
-  // phase A as in trace_histogram_kernel's generic variants
+  // phase A as in trace_histogram_kernel's generic variants.  Shells: every selected ray counts for its shell, those that the
+  // shell0_miss_radius compare ends here included (their shell is shell 0)
   auto run_phase_a = [&](uint32_t rel, bool valid, uint32_t u3_hi) {
     SART_STAGE_MARK("A1");
     __builtin_amdgcn_s_setprio(SART_PRIO_A1);
@@ -2598,6 +2280,10 @@ __global__ __launch_bounds__(BLOCK) void channel_histogram_kernel(HotA H, const 
     n_reached += (uint32_t)__popcll(valid_m & M.reached);
     const uint64_t selected = valid_m & M.ok;
     n_shell += (uint32_t)__popcll(selected);
+    if constexpr (BD::kShells) {
+      if (__builtin_amdgcn_inverse_ballot_w64(selected))
+        __hip_atomic_fetch_add(&lds.tab.cnt[shell_of(st.shell)][0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
     const uint64_t mask = selected & ~ballot64(radial < Pb.shell0_miss_radius);
     const uint32_t cnt = (uint32_t)__popcll(mask);
     if (__builtin_amdgcn_inverse_ballot_w64(mask)) {
@@ -2636,7 +2322,7 @@ __global__ __launch_bounds__(BLOCK) void channel_histogram_kernel(HotA H, const 
       st.shell = packed >> 16;
       const DevBlob& Bo = lds_opaque(B);
       HotB HB;
-      reload_kernarg(HB, offsetof(ChanKernArgs, HB));
+      reload_kernarg(HB, offsetof(HistKernArgs, HB));
       asm volatile("" :: "s"(HB.cdf_hi32), "s"(HB.energy_guide), "s"(HB.energy_tab), "s"(HB.refl), "s"(HB.refl_n_angles), "s"(HB.cdf_stride));
       phase_b<false, false, -1, false>(Bo.P, L, HB, lds_opaque(Ab), st, H.test_active ? Pb.n_energies : -1, valid, out, nullptr);
     }
@@ -2645,37 +2331,48 @@ __global__ __launch_bounds__(BLOCK) void channel_histogram_kernel(HotA H, const 
     n_nickel += (uint32_t)__popcll(out.m_nickel);
     n_till += (uint32_t)__popcll(out.m_till);
     n_passed += (uint32_t)__popcll(out.m_passed);
+    [[maybe_unused]] const uint32_t sh = shell_of(st.shell);   // (shells)
+    if constexpr (BD::kShells) {
+      if (__builtin_amdgcn_inverse_ballot_w64(out.m_nickel))
+        __hip_atomic_fetch_add(&lds.tab.cnt[sh][1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (__builtin_amdgcn_inverse_ballot_w64(out.m_till))
+        __hip_atomic_fetch_add(&lds.tab.cnt[sh][2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
     if (out.passed) {
       SART_STAGE_MARK("ACC");
-      // this ray's fractions: requested first, used behind the accumulator's own work.  The indices are clamped to the table (host:
-      // its shape is the solar tables' and it is < 4 GB, so the byte offset is 32-bit).
-      ChannelArgs CHl;
-      reload_kernarg(CHl, offsetof(ChanKernArgs, CH));
-      asm volatile("" :: "s"(CHl.block), "s"(CHl.frac), "s"(CHl.n_channels), "s"(CHl.stride), "s"(CHl.n_radii), "s"(CHl.n_energies),
-                   "s"(CHl.n_energies1));
-      // (the first half of the run here, the second - strides of 8 only: the same 64-byte line, a cache hit by then - in front of the
-      // channel loop, where the first four channels' work covers it: all eight in flight across the accumulator's work spill registers)
-      double f[kMaxChannels];
-      const uint32_t f_off = ((uint32_t)min(max(st.r_idx, 0), CHl.n_radii - 1) * (uint32_t)CHl.n_energies +
-                              (uint32_t)min(max(out.e_idx, 0), CHl.n_energies - 1)) * ((uint32_t)CHl.stride * 8u);
+      [[maybe_unused]] typename BD::Args BDl;     // (shells: re-read in the spectra branch)
+      [[maybe_unused]] double f[kMaxChannels];    // channels: this ray's fractions
+      [[maybe_unused]] uint32_t f_off = 0u;
+      if constexpr (!BD::kShells) {
+        // this ray's fractions: requested first, used behind the accumulator's own work.  The indices are clamped to the table (host:
+        // its shape is the solar tables' and it is < 4 GB, so the byte offset is 32-bit).
+        reload_kernarg(BDl, BD::kArgsOffset);
+        asm volatile("" :: "s"(BDl.block), "s"(BDl.frac), "s"(BDl.n_channels), "s"(BDl.stride), "s"(BDl.n_radii), "s"(BDl.n_energies),
+                     "s"(BDl.n_energies1));
+        // (the first half of the run here, the second - strides of 8 only: the same 64-byte line, a cache hit by then - in front of the
+        // channel loop, where the first four channels' work covers it: all eight in flight across the accumulator's work spill registers)
+        f_off = ((uint32_t)min(max(st.r_idx, 0), BDl.n_radii - 1) * (uint32_t)BDl.n_energies +
+                 (uint32_t)min(max(out.e_idx, 0), BDl.n_energies - 1)) * ((uint32_t)BDl.stride * 8u);
 #pragma unroll
-      for (int k = 0; k < kMaxChannels; ++k) f[k] = 0.0;
-      if (CHl.stride == 1) {   // wave-uniform
-        f[0] = gload<double>(CHl.frac, f_off);
-      } else {
+        for (int k = 0; k < kMaxChannels; ++k) f[k] = 0.0;
+        if (BDl.stride == 1) {   // wave-uniform
+          f[0] = gload<double>(BDl.frac, f_off);
+        } else {
 #pragma unroll
-        for (int k = 0; k < kMaxChannels / 4; ++k)
-          if (2 * k < CHl.stride) {
-            const d2 v = gload<d2>(CHl.frac, f_off + 16u * (uint32_t)k);
-            f[2 * k] = v.x;
-            f[2 * k + 1] = v.y;
-          }
+          for (int k = 0; k < kMaxChannels / 4; ++k)
+            if (2 * k < BDl.stride) {
+              const d2 v = gload<d2>(BDl.frac, f_off + 16u * (uint32_t)k);
+              f[2 * k] = v.x;
+              f[2 * k + 1] = v.y;
+            }
+        }
       }
       TraceArgs Al;
-      reload_kernarg(Al, offsetof(ChanKernArgs, A));
+      reload_kernarg(Al, offsetof(HistKernArgs, A));
       asm volatile("" :: "s"(Al.replicas), "s"(Al.replica_mask), "s"(Al.replica_stride), "s"(Al.image_nx), "s"(Al.image_ny),
                    "s"(Al.image_x_min), "s"(Al.image_y_min), "s"(Al.image_inv_step_x), "s"(Al.image_inv_step_y), "s"(Al.spectra),
                    "s"(Al.tile_x0), "s"(Al.tile_y0), "s"(Al.tile_n), "s"(Al.tile_base));
+      if constexpr (BD::kShells) __hip_atomic_fetch_add(&lds.tab.cnt[sh][3], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       long long w_fx = 0;   // FIXED: this ray's weight in quanta (what the image, the sums and the spectra add)
       if constexpr (FIXED) {
         w_fx = to_fixed(out.weight, Al.fx_scale_w);
@@ -2685,12 +2382,23 @@ __global__ __launch_bounds__(BLOCK) void channel_histogram_kernel(HotA H, const 
         sum_x += to_fixed(out.px, kFixedPositionScale);
         sum_y += to_fixed(out.py, kFixedPositionScale);
         sum_r += to_fixed(out.rdet, kFixedPositionScale);
+        if constexpr (BD::kShells) {
+          // the same integers the scalars add: the per-shell sums add up to SUM_WEIGHTS / SUM_WEIGHTS_SQ exactly
+          __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(&lds.tab.sum[sh][0]), (unsigned long long)w_fx, __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_WORKGROUP);
+          __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(&lds.tab.sum[sh][1]), (unsigned long long)w2_fx, __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
       } else {
         sum_w += out.weight;
         sum_w2 = fma(out.weight, out.weight, sum_w2);
         sum_x += out.px;
         sum_y += out.py;
         sum_r += out.rdet;
+        if constexpr (BD::kShells) {
+          __hip_atomic_fetch_add(&lds.tab.sum[sh][0], out.weight, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          __hip_atomic_fetch_add(&lds.tab.sum[sh][1], out.weight * out.weight, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
       }
       // prepareHeatmap (:838-842), as trace_histogram_kernel bins it
       const double fx = (out.px - Al.image_x_min) * Al.image_inv_step_x;
@@ -2703,14 +2411,14 @@ __global__ __launch_bounds__(BLOCK) void channel_histogram_kernel(HotA H, const 
         if (out.m_passed & ~inside_m) sum_wo += inside ? 0ll : w_fx;
       }
       double* const img = Al.replicas + (size_t)((uint32_t)wave_global & Al.replica_mask) * (size_t)Al.replica_stride;
-      uint32_t c_pix = 0u;   // the ray's pixel, for the channel images
+      [[maybe_unused]] uint32_t c_pix = 0u;   // the ray's pixel, for the channel images
       if (inside) {
         const uint32_t ix = (uint32_t)(int)fx, iy = (uint32_t)(int)fy;
-        c_pix = iy * (uint32_t)nx + ix;
+        if constexpr (!BD::kShells) c_pix = iy * (uint32_t)nx + ix;
         const uint32_t tn = (uint32_t)Al.tile_n;
         const uint32_t tx = ix - (uint32_t)Al.tile_x0, ty = iy - (uint32_t)Al.tile_y0;
         if ((tx < tn) & (ty < tn)) {
-          const uint32_t t = ty * tn + tx + (uint32_t)Al.tile_base;   // < kTileRingCells + kRingExtraCells - kChanTableCells (host)
+          const uint32_t t = ty * tn + tx + (uint32_t)Al.tile_base;   // < kTileRingCells + kRingExtraCells - BD::kTableCells (host)
           if constexpr (FIXED)
             __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(tile_cell(t)), (unsigned long long)w_fx, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2723,63 +2431,78 @@ __global__ __launch_bounds__(BLOCK) void channel_histogram_kernel(HotA H, const 
           else unsafeAtomicAdd((double*)((gbytes)img + pix * 8u), out.weight);
         }
       }
-      if (Al.spectra) {   // wave-uniform: the spectra behind the scalars
+      if (Al.spectra) {   // wave-uniform: the spectra behind the scalars; shells: and the same energy bins per shell in the block
         double* rad = acc + (size_t)nx * (size_t)ny + SART_ACC_COUNT;
         double* en = rad + 2 * (size_t)Al.n_radial_bins;
         const size_t ne1 = (size_t)Pb.n_energies + 1;
         const int rb = min((int)(out.rdet * Al.radial_inv_bin), Al.n_radial_bins - 1);
+        [[maybe_unused]] double* sen = nullptr;   // shells: counts[sh][e]
+        [[maybe_unused]] size_t sw_off = 0;       //         -> weights[sh][e]
+        if constexpr (BD::kShells) {
+          reload_kernarg(BDl, BD::kArgsOffset);
+          sen = BDl.block + (size_t)BDl.n_shells * SART_SHELL_ROW + (size_t)sh * ne1 + (size_t)out.e_idx;
+          sw_off = (size_t)BDl.n_shells * ne1;
+        }
         if constexpr (FIXED) {
           atomic_add_slot_i64(&rad[rb], 1);
           atomic_add_slot_i64(&rad[(size_t)Al.n_radial_bins + rb], w_fx);
           atomic_add_slot_i64(&en[out.e_idx], 1);
           atomic_add_slot_i64(&en[ne1 + out.e_idx], w_fx);
           atomic_add_slot_i64(&en[2 * ne1 + out.e_idx], to_fixed(out.reflect, kFixedReflectScale));
+          if constexpr (BD::kShells) {
+            atomic_add_slot_i64(sen, 1);
+            atomic_add_slot_i64(sen + sw_off, w_fx);
+          }
         } else {
           unsafeAtomicAdd(&rad[rb], 1.0);
           unsafeAtomicAdd(&rad[(size_t)Al.n_radial_bins + rb], out.weight);
           unsafeAtomicAdd(&en[out.e_idx], 1.0);
           unsafeAtomicAdd(&en[ne1 + out.e_idx], out.weight);
           unsafeAtomicAdd(&en[2 * ne1 + out.e_idx], out.reflect);
+          if constexpr (BD::kShells) {
+            unsafeAtomicAdd(sen, 1.0);
+            unsafeAtomicAdd(sen + sw_off, out.weight);
+          }
         }
       }
       // the channels: c_t = w f_t, ONE product; the same c_t to the row, the ray's energy bin and its pixel (or the row's OUTSIDE)
-      {
+      if constexpr (!BD::kShells) {
         const uint32_t cl = (uint32_t)lane & (uint32_t)(kChanLanes - 1);
-        const size_t c_ne1 = (size_t)CHl.n_energies1, c_nimg = (size_t)nx * (size_t)ny;
-        double* const c_en = CHl.block + (size_t)CHl.n_channels * SART_CHAN_ROW;                  // energy_weights[t][e]
-        double* const c_img = c_en + (Al.spectra ? (size_t)CHl.n_channels * c_ne1 : (size_t)0);   // images [t][ny][nx]
-        if (CHl.stride == 8) {   // wave-uniform: the second half of the run
+        const size_t c_ne1 = (size_t)BDl.n_energies1, c_nimg = (size_t)nx * (size_t)ny;
+        double* const c_en = BDl.block + (size_t)BDl.n_channels * SART_CHAN_ROW;                  // energy_weights[t][e]
+        double* const c_img = c_en + (Al.spectra ? (size_t)BDl.n_channels * c_ne1 : (size_t)0);   // images [t][ny][nx]
+        if (BDl.stride == 8) {   // wave-uniform: the second half of the run
 #pragma unroll
           for (int k = kMaxChannels / 4; k < kMaxChannels / 2; ++k) {
-            const d2 v = gload<d2>(CHl.frac, f_off + 16u * (uint32_t)k);
+            const d2 v = gload<d2>(BDl.frac, f_off + 16u * (uint32_t)k);
             f[2 * k] = v.x;
             f[2 * k + 1] = v.y;
           }
         }
 #pragma unroll
         for (int t = 0; t < kMaxChannels; ++t) {
-          if (t >= CHl.n_channels) break;   // wave-uniform
+          if (t >= BDl.n_channels) break;   // wave-uniform
           const double ft = f[t];
-          if (ft > 0.0) __hip_atomic_fetch_add(&lds.chan_cnt[t][cl], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          if (ft > 0.0) __hip_atomic_fetch_add(&lds.tab.cnt[t][cl], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           const double c = out.weight * ft;
           if (c != 0.0) {
             if constexpr (FIXED) {
               const long long c_fx = to_fixed(c, Al.fx_scale_w);
               const long long c2_fx = to_fixed(c * c, Al.fx_scale_w2);
-              __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(&lds.chan_sum[t][0][cl]), (unsigned long long)c_fx,
+              __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(&lds.tab.sum[t][0][cl]), (unsigned long long)c_fx,
                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-              __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(&lds.chan_sum[t][1][cl]), (unsigned long long)c2_fx,
+              __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(&lds.tab.sum[t][1][cl]), (unsigned long long)c2_fx,
                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
               if (inside) atomic_add_slot_i64(c_img + (size_t)t * c_nimg + c_pix, c_fx);
               else
-                __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(&lds.chan_sum[t][2][cl]), (unsigned long long)c_fx,
+                __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(&lds.tab.sum[t][2][cl]), (unsigned long long)c_fx,
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
               if (Al.spectra) atomic_add_slot_i64(c_en + (size_t)t * c_ne1 + (size_t)out.e_idx, c_fx);
             } else {
-              __hip_atomic_fetch_add(&lds.chan_sum[t][0][cl], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-              __hip_atomic_fetch_add(&lds.chan_sum[t][1][cl], c * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              __hip_atomic_fetch_add(&lds.tab.sum[t][0][cl], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              __hip_atomic_fetch_add(&lds.tab.sum[t][1][cl], c * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
               if (inside) unsafeAtomicAdd(c_img + (size_t)t * c_nimg + c_pix, c);
-              else __hip_atomic_fetch_add(&lds.chan_sum[t][2][cl], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              else __hip_atomic_fetch_add(&lds.tab.sum[t][2][cl], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
               if (Al.spectra) unsafeAtomicAdd(c_en + (size_t)t * c_ne1 + (size_t)out.e_idx, c);
             }
           }
@@ -2901,19 +2624,37 @@ __global__ __launch_bounds__(BLOCK) void channel_histogram_kernel(HotA H, const 
     for (int w = 0; w < BLOCK / 64; ++w) t += red[w][threadIdx.x];
     reinterpret_cast<Sum*>(A.partials)[(size_t)blockIdx.x * SART_ACC_COUNT + threadIdx.x] = t;
   }
-  // the channel table of this workgroup (every wave has left the loop: the barriers above)
-  if (threadIdx.x < kMaxChannels * kChanPartialSlots) {
+  // the breakdown table of this workgroup (every wave has left the loop: the barriers above)
+  if constexpr (BD::kShells) {
+    for (int i = threadIdx.x; i < kMaxShells * kShellPartialSlots; i += BLOCK) {
+      const int s = i / kShellPartialSlots, j = i - s * kShellPartialSlots;
+      const Sum v = j < 4 ? (Sum)lds.tab.cnt[s][j] : lds.tab.sum[s][j - 4];
+      reinterpret_cast<Sum*>(BDarg.partials)[(size_t)blockIdx.x * (kMaxShells * kShellPartialSlots) + i] = v;
+    }
+  } else if (threadIdx.x < kMaxChannels * kChanPartialSlots) {
     const int t = threadIdx.x / kChanPartialSlots, j = threadIdx.x - t * kChanPartialSlots;
     Sum v = 0;
     if (j < 3) {
-      for (int l = 0; l < kChanLanes; ++l) v += lds.chan_sum[t][j][l];
+      for (int l = 0; l < kChanLanes; ++l) v += lds.tab.sum[t][j][l];
     } else {
       uint32_t n = 0u;
-      for (int l = 0; l < kChanLanes; ++l) n += lds.chan_cnt[t][l];
+      for (int l = 0; l < kChanLanes; ++l) n += lds.tab.cnt[t][l];
       v = (Sum)n;
     }
-    reinterpret_cast<Sum*>(CHarg.partials)[(size_t)blockIdx.x * (kMaxChannels * kChanPartialSlots) + threadIdx.x] = v;
+    reinterpret_cast<Sum*>(BDarg.partials)[(size_t)blockIdx.x * (kMaxChannels * kChanPartialSlots) + threadIdx.x] = v;
   }
+}
+
+// The two kernels: their names, template parameters and parameter lists are what the host launches and the code objects' tests know.
+template <int BLOCK, bool ROT, bool FIXED>
+__global__ __launch_bounds__(BLOCK) void shell_histogram_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
+                                                                double* __restrict__ acc, HotB HBarg, ShellArgs SHarg) {
+  breakdown_histogram_body<BLOCK, ROT, FIXED, ShellBreakdown>(H, blob, A, acc, SHarg);
+}
+template <int BLOCK, bool ROT, bool FIXED>
+__global__ __launch_bounds__(BLOCK) void channel_histogram_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
+                                                                  double* __restrict__ acc, HotB HBarg, ChannelArgs CHarg) {
+  breakdown_histogram_body<BLOCK, ROT, FIXED, ChannelBreakdown>(H, blob, A, acc, CHarg);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -5177,22 +4918,35 @@ void launch_ascan_images(const HotA& H, const HotB& HB, const DevBlob* blob, con
   }
 }
 
-// The per-shell histogram launch (generic variants: `rotated` = hist_variant_of 2): the kernel, then the folds of
-// launch_trace_histogram (scalars, replicas) and the fold of the shell table into the caller's block.
-int shell_histogram_blocks_per_cu(bool rotated) {
+// The breakdown launches (generic variants: `rotated` = hist_variant_of 2): the kernel, then the folds of launch_trace_histogram
+// (scalars, replicas) and the fold of the breakdown's table - one workgroup per row: shell or channel - into the caller's block.
+template <class Args>
+struct BreakdownKernels {
+  void (*trace[4])(HotA, const DevBlob*, TraceArgs, double*, HotB, Args);   // [kernel_index(rotated, fixed)]
+  void (*fold[2])(double*, const double*, int);                             // [fixed ? 0 : 1]
+};
+// (the instantiations stand in the order in which the code object has always held them: <ROT, FIXED> = <1, 0>, <0, 0>, <0, 1>, <1, 1>)
+static int kernel_index(bool rotated, bool fixed) { return fixed ? (rotated ? 3 : 2) : (rotated ? 0 : 1); }
+static const BreakdownKernels<ShellArgs> kShellKernels = {
+    {shell_histogram_kernel<1024, true, false>, shell_histogram_kernel<1024, false, false>, shell_histogram_kernel<1024, false, true>,
+     shell_histogram_kernel<1024, true, true>},
+    {fold_shells_kernel<true>, fold_shells_kernel<false>}};
+static const BreakdownKernels<ChannelArgs> kChannelKernels = {
+    {channel_histogram_kernel<1024, true, false>, channel_histogram_kernel<1024, false, false>,
+     channel_histogram_kernel<1024, false, true>, channel_histogram_kernel<1024, true, true>},
+    {fold_channels_kernel<true>, fold_channels_kernel<false>}};
+
+template <class Args>
+static int breakdown_blocks_per_cu(const BreakdownKernels<Args>& K, bool rotated) {
   int n = 0;
-  const hipError_t e = rotated ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, shell_histogram_kernel<1024, true, false>, 1024, 0)
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, shell_histogram_kernel<1024, false, false>, 1024, 0);
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, K.trace[kernel_index(rotated, false)], 1024, 0);
   return (e == hipSuccess && n > 0) ? n : 1;
 }
-void launch_shell_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, double* acc, const ShellArgs& SH,
-                            int n_blocks, hipStream_t stream, bool rotated, bool fixed) {
-  switch ((rotated ? 2 : 0) + (fixed ? 1 : 0)) {
-    case 0: hipLaunchKernelGGL((shell_histogram_kernel<1024, false, false>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, SH); break;
-    case 1: hipLaunchKernelGGL((shell_histogram_kernel<1024, false, true>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, SH); break;
-    case 2: hipLaunchKernelGGL((shell_histogram_kernel<1024, true, false>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, SH); break;
-    default: hipLaunchKernelGGL((shell_histogram_kernel<1024, true, true>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, SH); break;
-  }
+template <class Args>
+static void launch_breakdown_histogram(const BreakdownKernels<Args>& K, const HotA& H, const HotB& HB, const DevBlob* blob,
+                                       const TraceArgs& A, double* acc, const Args& BD, int n_rows, int n_blocks, hipStream_t stream,
+                                       bool rotated, bool fixed) {
+  hipLaunchKernelGGL(K.trace[kernel_index(rotated, fixed)], dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, BD);
   const int n_img = A.image_nx * A.image_ny;
   if (fixed) {
     long long* const acc_i = reinterpret_cast<long long*>(acc);
@@ -5201,14 +4955,23 @@ void launch_shell_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, 
     if (A.replica_mask != 0u)
       hipLaunchKernelGGL(fold_replicas_kernel<long long>, dim3((n_img + 255) / 256), dim3(256), 0, stream, acc_i,
                          reinterpret_cast<long long*>(A.replicas), n_img, (int)A.replica_mask + 1, A.replica_stride);
-    hipLaunchKernelGGL(fold_shells_kernel<true>, dim3(SH.n_shells), dim3(64), 0, stream, SH.block, SH.partials, n_blocks);
-    return;
+  } else {
+    hipLaunchKernelGGL(fold_scalars_kernel, dim3(1), dim3(256), 0, stream, acc + n_img, A.partials, n_blocks, (double)A.n_rays);
+    if (A.replica_mask != 0u)
+      hipLaunchKernelGGL(fold_replicas_kernel<double>, dim3((n_img + 255) / 256), dim3(256), 0, stream, acc, A.replicas, n_img,
+                         (int)A.replica_mask + 1, A.replica_stride);
   }
-  hipLaunchKernelGGL(fold_scalars_kernel, dim3(1), dim3(256), 0, stream, acc + n_img, A.partials, n_blocks, (double)A.n_rays);
-  if (A.replica_mask != 0u)
-    hipLaunchKernelGGL(fold_replicas_kernel<double>, dim3((n_img + 255) / 256), dim3(256), 0, stream, acc, A.replicas, n_img,
-                       (int)A.replica_mask + 1, A.replica_stride);
-  hipLaunchKernelGGL(fold_shells_kernel<false>, dim3(SH.n_shells), dim3(64), 0, stream, SH.block, SH.partials, n_blocks);
+  hipLaunchKernelGGL(K.fold[fixed ? 0 : 1], dim3(n_rows), dim3(64), 0, stream, BD.block, BD.partials, n_blocks);
+}
+int shell_histogram_blocks_per_cu(bool rotated) { return breakdown_blocks_per_cu(kShellKernels, rotated); }
+int channel_histogram_blocks_per_cu(bool rotated) { return breakdown_blocks_per_cu(kChannelKernels, rotated); }
+void launch_shell_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, double* acc, const ShellArgs& SH,
+                            int n_blocks, hipStream_t stream, bool rotated, bool fixed) {
+  launch_breakdown_histogram(kShellKernels, H, HB, blob, A, acc, SH, SH.n_shells, n_blocks, stream, rotated, fixed);
+}
+void launch_channel_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, double* acc, const ChannelArgs& CH,
+                              int n_blocks, hipStream_t stream, bool rotated, bool fixed) {
+  launch_breakdown_histogram(kChannelKernels, H, HB, blob, A, acc, CH, CH.n_channels, n_blocks, stream, rotated, fixed);
 }
 void launch_finalize_shells(const void* in, double* out, int n_shells, int n_energies1, int spectra, double q_w, double q_w2,
                             void* check_dev, hipStream_t stream) {
@@ -5217,39 +4980,6 @@ void launch_finalize_shells(const void* in, double* out, int n_shells, int n_ene
                      static_cast<FixedCheck*>(check_dev));
 }
 
-// The emission-channel histogram launch (generic variants: `rotated` = hist_variant_of 2): the kernel, then the folds of
-// launch_trace_histogram (scalars, replicas) and the fold of the channel table into the caller's block.
-int channel_histogram_blocks_per_cu(bool rotated) {
-  int n = 0;
-  const hipError_t e = rotated ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, channel_histogram_kernel<1024, true, false>, 1024, 0)
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, channel_histogram_kernel<1024, false, false>, 1024, 0);
-  return (e == hipSuccess && n > 0) ? n : 1;
-}
-void launch_channel_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, double* acc, const ChannelArgs& CH,
-                              int n_blocks, hipStream_t stream, bool rotated, bool fixed) {
-  switch ((rotated ? 2 : 0) + (fixed ? 1 : 0)) {
-    case 0: hipLaunchKernelGGL((channel_histogram_kernel<1024, false, false>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, CH); break;
-    case 1: hipLaunchKernelGGL((channel_histogram_kernel<1024, false, true>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, CH); break;
-    case 2: hipLaunchKernelGGL((channel_histogram_kernel<1024, true, false>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, CH); break;
-    default: hipLaunchKernelGGL((channel_histogram_kernel<1024, true, true>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, CH); break;
-  }
-  const int n_img = A.image_nx * A.image_ny;
-  if (fixed) {
-    long long* const acc_i = reinterpret_cast<long long*>(acc);
-    hipLaunchKernelGGL(fold_scalars_fixed_kernel, dim3(1), dim3(256), 0, stream, acc_i + n_img,
-                       reinterpret_cast<const long long*>(A.partials), n_blocks, (long long)A.n_rays);
-    if (A.replica_mask != 0u)
-      hipLaunchKernelGGL(fold_replicas_kernel<long long>, dim3((n_img + 255) / 256), dim3(256), 0, stream, acc_i,
-                         reinterpret_cast<long long*>(A.replicas), n_img, (int)A.replica_mask + 1, A.replica_stride);
-    hipLaunchKernelGGL(fold_channels_kernel<true>, dim3(CH.n_channels), dim3(64), 0, stream, CH.block, CH.partials, n_blocks);
-    return;
-  }
-  hipLaunchKernelGGL(fold_scalars_kernel, dim3(1), dim3(256), 0, stream, acc + n_img, A.partials, n_blocks, (double)A.n_rays);
-  if (A.replica_mask != 0u)
-    hipLaunchKernelGGL(fold_replicas_kernel<double>, dim3((n_img + 255) / 256), dim3(256), 0, stream, acc, A.replicas, n_img,
-                       (int)A.replica_mask + 1, A.replica_stride);
-  hipLaunchKernelGGL(fold_channels_kernel<false>, dim3(CH.n_channels), dim3(64), 0, stream, CH.block, CH.partials, n_blocks);
-}
 void launch_finalize_channels(const void* in, double* out, int n_channels, int n_energies1, int spectra, size_t n_img, double q_w,
                               double q_w2, void* check_dev, hipStream_t stream) {
   FinalizeChannelsArgs F{n_channels, n_energies1, spectra, 0, (long long)n_img, q_w, q_w2};
