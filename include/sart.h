@@ -833,6 +833,55 @@ int sart_trace_histogram_channels(sart_context* ctx, const sart_trace_params_t* 
 int sart_finalize_channels_device(sart_context* ctx, const sart_trace_params_t* params, const void* channels_fixed_device,
                                   double* out_f64_device);
 
+/* ---- solar-origin map of the histogram trace ------------------------------------ */
+/*
+ * Every solar ray is drawn in one cell (radius index r, energy index e) of the emission table (raytracer.nim:425-471, CDFs
+ * :2670-2705), and past its cell its weight depends on geometry and energy alone, never on the emission rates.  These entry points
+ * are sart_trace_histogram_device plus the detected weight per cell, D[r][e] = sum of w over the passed rays drawn there: the
+ * response of the helioscope over the solar table.  One trace then gives the radial profile of the detected flux across the Sun
+ * (sum_e D), the acceptance per cell (D / (N_RAYS cell mass)) and - by importance reweighting on the host - the flux, spectrum and
+ * profile for ANY other emission table on the same grid: sum_cells D[c] rates'[c] / rates[c] (the E^2 r^2 factors of :2686 cancel).
+ * The emission-channel breakdown above is the special case rates' = rates_t <= rates, fixed before the launch.
+ *
+ *   accumulator_device  exactly what sart_trace_histogram_device accumulates for the same params (image, scalars, spectra, flux-only
+ *                       launches): the contract of the per-shell and per-channel entries - bit for bit in SART_ACCUM_FIXED64 against
+ *                       the generic kernel variants, up to the summation order in f64
+ *   origin_device       a flat array of sart_origin_block_len(n_radii, n_energies) 8-byte slots (f64, or raw int64 in FIXED64; ranks
+ *                       reduce it as it is - sart_reduce_across_devices, as int64 in FIXED64 - then finalize):
+ *                         1. the head, SART_ORIGIN_HEAD slots: SART_ORIGIN_N_PASSED, _SUM_WEIGHTS, _SUM_WEIGHTS_SQ (= SART_ACC_N_PASSED,
+ *                            _SUM_WEIGHTS, _SUM_WEIGHTS_SQ) and in raw FIXED64 the high limbs SART_ORIGIN_SUM_WEIGHTS_HI / _SQ_HI:
+ *                            value = (hi 2^40 + lo) quantum, 0 <= lo < 2^40 after a launch; the other slots are reserved (0)
+ *                         2. cells[n_radii][n_energies][SART_ORIGIN_CELL]: SART_ORIGIN_N (passed rays drawn in the cell),
+ *                            SART_ORIGIN_SUM_WEIGHTS (sum of w; FIXED64: of rint(w / quantum)), SART_ORIGIN_SUM_WEIGHTS_SQ (sum of w^2;
+ *                            FIXED64: of the integer the ray adds to SART_ACC_SUM_WEIGHTS_SQ); slot 3 is reserved (0).  One aligned
+ *                            32-byte cell per (r, e): the shape is that of the context's solar tables.
+ * In FIXED64 and exactly as integers: sum of the cells = head = the accumulator's scalars, and the sum over r of the cells at energy
+ * index e is the accumulator's energy-count and energy-weight bin e (every passed ray adds the same integers everywhere).
+ * Quanta: the accumulator's, frozen in the same way; params->accumulate applies to both buffers.
+ * SART_ERR_INVALID_ARGUMENT, context unchanged: the X-ray test source is active (no solar draw), a NULL pointer, an invalid image
+ * or spectra specification.  SART_ERR_NOT_READY without solar tables.
+ * Cost: the generic histogram variants plus three global atomics per passed ray into a 94 MB map at 1968 x 1500 (no replicas, no LDS
+ * staging: millions of cells); the LDS image tile is 55 x 55 instead of 64 x 64.  Measured on BabyIAXO / XMM with image and spectra:
+ * 108 ms per 1e9 rays against 81 of the generic histogram launch (1.34 x; FIXED64: 111 against 83, 1.33 x) - profiles/r16_origin_rate.txt,
+ * DESIGN.md 3.2e.
+ */
+enum { SART_ORIGIN_N = 0, SART_ORIGIN_SUM_WEIGHTS = 1, SART_ORIGIN_SUM_WEIGHTS_SQ = 2, SART_ORIGIN_CELL = 4,
+       SART_ORIGIN_N_PASSED = 0, SART_ORIGIN_SUM_WEIGHTS_HI = 4, SART_ORIGIN_SUM_WEIGHTS_SQ_HI = 5, SART_ORIGIN_HEAD = 8 };
+/* 8-byte slots of an origin block: SART_ORIGIN_HEAD + n_radii n_energies SART_ORIGIN_CELL. */
+size_t sart_origin_block_len(int32_t n_radii, int32_t n_energies);
+/* DEVICE memory; asynchronous on the context's stream. */
+int sart_trace_histogram_origin_device(sart_context* ctx, const sart_trace_params_t* params, double* accumulator_device,
+                                       double* origin_device);
+/* Blocking form with HOST outputs (each may be NULL), finalized in FIXED64 mode.  Starts from zero: params->accumulate is not read. */
+int sart_trace_histogram_origin(sart_context* ctx, const sart_trace_params_t* params, double* image_out_host, sart_summary_t* summary_out,
+                                double* spectra_out_host, double* origin_out_host);
+/* Raw FIXED64 block -> doubles with the context's frozen quanta (device pointers; in place allowed); asynchronous.  Checks, surfacing as
+ * SART_ERR_ACCUMULATOR from the next sart_synchronize: a slot negative or >= 2^62; the cells' N must add up to the head's N_PASSED and
+ * their SUM_WEIGHTS / SUM_WEIGHTS_SQ to the head's, exactly as integers.  Squared weights
+ * that average below 2^6 quanta per passed ray read NaN in every SUM_WEIGHTS_SQ slot and are no error. */
+int sart_finalize_origin_device(sart_context* ctx, const sart_trace_params_t* params, const void* origin_fixed_device,
+                                double* out_f64_device);
+
 /* ---- multi-GPU ---------------------------------------------------------- */
 /*
  * Sum the fused accumulators of n contexts (one per GPU of this process) into the one of contexts[root]:

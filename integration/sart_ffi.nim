@@ -200,6 +200,18 @@ proc sart_trace_histogram_channels*(ctx: ptr SartContext, p: ptr SartTraceParams
                                     spectraOutHost: ptr cdouble, channelsOutHost: ptr cdouble): cint {.importc, header: sartH.}
 proc sart_finalize_channels_device*(ctx: ptr SartContext, p: ptr SartTraceParams, channelsFixedDevice: pointer,
                                     outF64Device: ptr cdouble): cint {.importc, header: sartH.}
+## solar-origin map of the histogram trace: the detected weight per cell (radius index, energy index) of the solar emission table the
+## passed rays were drawn in.  The block: a head of 8 slots (N_PASSED, sum w, sum w^2, their FIXED64 high limbs in slots 4, 5), then
+## cells [nRadii][nEnergies][4] (N, sum w, sum w^2, reserved)
+const SartOriginHead* = 8
+const SartOriginCell* = 4
+proc sart_origin_block_len*(nRadii, nEnergies: int32): csize_t {.importc, header: sartH.}
+proc sart_trace_histogram_origin_device*(ctx: ptr SartContext, p: ptr SartTraceParams, accumulatorDevice: ptr cdouble,
+                                         originDevice: ptr cdouble): cint {.importc, header: sartH.}
+proc sart_trace_histogram_origin*(ctx: ptr SartContext, p: ptr SartTraceParams, imageOutHost: ptr cdouble, summaryOut: ptr SartSummary,
+                                  spectraOutHost: ptr cdouble, originOutHost: ptr cdouble): cint {.importc, header: sartH.}
+proc sart_finalize_origin_device*(ctx: ptr SartContext, p: ptr SartTraceParams, originFixedDevice: pointer,
+                                  outF64Device: ptr cdouble): cint {.importc, header: sartH.}
 proc sart_reduce_across_devices*(contexts: ptr ptr SartContext, accumulatorsDevice: ptr ptr cdouble, n: int32, nDoubles: csize_t,
                                  root: int32): cint {.importc, header: sartH.}
 proc sart_enable_kernel_timing*(ctx: ptr SartContext, enable: cint): cint {.importc, header: sartH.}

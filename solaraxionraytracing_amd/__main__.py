@@ -9,6 +9,7 @@
         [--shellBreakdown]                                               (not in the reference: see below)
         [--emissionChannels {terms,couplings}]                           (not in the reference: see below)
         [--events PATH.npz [--eventColumns a,b,c]]                       (not in the reference: see below)
+        [--originMap]                                                    (not in the reference: see below)
 
 Same switches, same two modes (full run = calculateFluxFractions, :2755-2776; angular scan, :2778-2815).  What differs:
 `--rays` replaces the compile-time constant NumberOfPointsSun (:251, default 1e6), plots are never made (the numbers
@@ -32,7 +33,12 @@ combined with --xrayTest or a solar-model CSV, nor with --shellBreakdown: one br
 --events PATH.npz (full-run mode only) also writes the passed rays themselves, as columns in ray order (the `axionsPass` that
 generateResultPlots plots from, :2253-2289): one array per name of --eventColumns (default pointdataX, pointdataY, pointdataR,
 energiesAx, weights, shellNumber, ray_id; any field of the Axion record, `flags`, `kinds_packed`, `ray_id`) and the four counts
-n_rays, n_passed, n_passed_till_window, n_hit_nickel.  The rays are those of the image: same seed, same ids."""
+n_rays, n_passed, n_passed_till_window, n_hit_nickel.  The rays are those of the image: same seed, same ids.
+--originMap (full-run mode only; not beside --xrayTest, --shellBreakdown or --emissionChannels: one breakdown per run) also keeps the
+detected weight per cell (solar radius, energy) of the emission table the passed rays were drawn in, from the one trace, and writes
+`origin_map_{year}.npz` (counts, weights, weights_sq [n_radii][n_energies], radii, energies, n_rays and the traced rates) and
+`flux_by_solar_radius_{year}.csv`.  `python -m solaraxionraytracing_amd.reweight origin_map_{year}.npz --solarModel FILE.csv` then
+gives the flux for another solar model on the same grid without a new trace (origin.py)."""
 from __future__ import annotations
 
 import argparse
@@ -41,7 +47,7 @@ import sys
 
 import numpy as np
 
-from . import _lib, config as cfgmod
+from . import _lib, config as cfgmod, origin
 from .raytracer import (RayTracer, angle_image_names, containment_radii, initFullSetup, performAngularScan, performAxionMassScan,
                         performEnergyScan, write_channel_csvs, write_image_csv, write_shell_csvs)
 
@@ -79,6 +85,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--emissionChannels", choices=("terms", "couplings"), default=None,
                     help="extension (full-run mode): the result per emission process (terms) or per coupling (couplings) from the one "
                          "trace; switches the emission table to the all-terms AGSS09 table made on the GPU")
+    ap.add_argument("--originMap", action="store_true",
+                    help="extension (full-run mode): the detected flux per (solar radius, energy) cell of the emission table, "
+                         "origin_map_{year}.npz and flux_by_solar_radius_{year}.csv; reweightable to another solar model "
+                         "(python -m solaraxionraytracing_amd.reweight)")
     ap.add_argument("--events", default="", metavar="PATH.npz",
                     help="extension (full-run mode): the passed rays as columns, in ray order, and the four counts, as a numpy .npz")
     ap.add_argument("--eventColumns", default=",".join(EVENT_COLUMNS), help="comma-separated columns of --events (default: %(default)s)")
@@ -115,6 +125,13 @@ def check_scan_args(ap: argparse.ArgumentParser, args) -> None:
             ap.error("--emissionChannels needs the solar source: it cannot be combined with --xrayTest")
         if getattr(args, "shellBreakdown", False):
             ap.error("--emissionChannels cannot be combined with --shellBreakdown (one breakdown per run)")
+    if getattr(args, "originMap", False):
+        if energy_scan_requested(args) or args.massScanMax > args.massScanMin or args.angularScanMin != args.angularScanMax:
+            ap.error("--originMap belongs to the full run: it cannot be combined with a mass, angular or energy scan")
+        if args.xrayTest:
+            ap.error("--originMap needs the solar source: it cannot be combined with --xrayTest")
+        if getattr(args, "shellBreakdown", False) or getattr(args, "emissionChannels", None):
+            ap.error("--originMap cannot be combined with --shellBreakdown or --emissionChannels (one breakdown per run)")
     if not energy_scan_requested(args):
         return
     if args.massScanMax > args.massScanMin or args.angularScanMin != args.angularScanMax:
@@ -179,6 +196,11 @@ def main(argv=None) -> int:
             ap.error("--emissionChannels cannot be combined with a solar-model CSV (%s): its components are not known"
                      % full.meta.get("emission"))
         print("--emissionChannels: the emission table of this run is the all-terms AGSS09 table made on the GPU")
+    if args.originMap:
+        if full.setup.test_active:
+            ap.error("--originMap needs the solar source: the config's X-ray test source is active")
+        if full.em_rates is None:
+            ap.error("--originMap needs the emission table on the host (this setup makes it on the device: %s)" % full.meta.get("emission"))
     n = int(args.rays)
     os.makedirs(args.outpath, exist_ok=True)
     print("Flags:", [name for name, bit in (("cfIgnoreDetWindow", _lib.CF_IGNORE_DET_WINDOW), ("cfIgnoreGasAbs", _lib.CF_IGNORE_GAS_ABS),
@@ -217,6 +239,8 @@ def main(argv=None) -> int:
             elif args.emissionChannels:
                 rt.set_emission_channels(args.emissionChannels)
                 img, s, spec, chans = rt.trace_channels(n, seed=args.seed, flags=flags)
+            elif args.originMap:
+                img, s, spec, omap = rt.trace_origin(n, seed=args.seed, flags=flags)
             else:
                 img, s, spec = rt.trace_spectra(n, seed=args.seed, flags=flags)
             write_result(os.path.join(args.outpath, "axion_image_%s.csv" % year), img, s, spec, full.setup.chip_x_max)
@@ -227,6 +251,12 @@ def main(argv=None) -> int:
                 r1w, r2w = containment_radii(spec)[2:]
                 for path in write_channel_csvs(args.outpath, year, chans, full.energies, full.setup.chip_x_max, r1w, r2w):
                     print("wrote", path)
+            if args.originMap:
+                path = os.path.join(args.outpath, "origin_map_%s.npz" % year)
+                np.savez_compressed(path, counts=omap["counts"], weights=omap["weights"], weights_sq=omap["weights_sq"], radii=full.radii,
+                                    energies=full.energies, n_rays=np.float64(s["N_RAYS"]), rates=full.em_rates)
+                print("wrote", path)
+                print("wrote", origin.write_radial_csv(os.path.join(args.outpath, "flux_by_solar_radius_%s.csv" % year), omap, full.radii))
             if args.events:
                 cols, counts = rt.trace_columns(n, event_columns(args), seed=args.seed, flags=flags)
                 np.savez(args.events, **cols, **counts)

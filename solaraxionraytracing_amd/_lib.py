@@ -66,6 +66,12 @@ CHAN_ROW = 8
 CHAN = dict(SUM_WEIGHTS=0, SUM_WEIGHTS_SQ=1, N_CONTRIBUTING=2, SUM_WEIGHTS_OUTSIDE=3)
 CHAN_HI = dict(SUM_WEIGHTS=4, SUM_WEIGHTS_SQ=5, SUM_WEIGHTS_OUTSIDE=7)
 CHAN_RESERVED = 6
+# solar-origin map (include/sart.h: SART_ORIGIN_*): a head of ORIGIN_HEAD slots, then cells[n_radii][n_energies][ORIGIN_CELL]
+ORIGIN_HEAD = 8
+ORIGIN_CELL = 4
+ORIGIN = dict(N=0, SUM_WEIGHTS=1, SUM_WEIGHTS_SQ=2)
+ORIGIN_HEAD_SLOTS = dict(N_PASSED=0, SUM_WEIGHTS=1, SUM_WEIGHTS_SQ=2)
+ORIGIN_HEAD_HI = dict(SUM_WEIGHTS=4, SUM_WEIGHTS_SQ=5)
 
 
 def energy_scan_len(n_energies: int) -> int:
@@ -118,6 +124,22 @@ def split_channels(block, n_channels: int, n_energies: int, spectra: bool, nx: i
     if nx > 0 and ny > 0:
         out["images"] = block[o:].reshape(t, int(ny), int(nx)).copy()
     return out
+
+
+def origin_block_len(n_radii: int, n_energies: int) -> int:
+    """sart_origin_block_len: 8-byte slots of a solar-origin block."""
+    return ORIGIN_HEAD + max(int(n_radii), 0) * max(int(n_energies), 0) * ORIGIN_CELL
+
+
+def split_origin(block, n_radii: int, n_energies: int) -> dict:
+    """``head`` (dict, keys of ORIGIN_HEAD_SLOTS) and the maps ``counts``, ``weights``, ``weights_sq`` [n_radii][n_energies] from a
+    finalized origin block."""
+    import numpy as np
+    block = np.asarray(block, dtype=np.float64)
+    assert block.size == origin_block_len(n_radii, n_energies)
+    cells = block[ORIGIN_HEAD:].reshape(int(n_radii), int(n_energies), ORIGIN_CELL)
+    return dict(head={k: float(block[i]) for k, i in ORIGIN_HEAD_SLOTS.items()}, counts=cells[:, :, ORIGIN["N"]].copy(),
+                weights=cells[:, :, ORIGIN["SUM_WEIGHTS"]].copy(), weights_sq=cells[:, :, ORIGIN["SUM_WEIGHTS_SQ"]].copy())
 
 
 def split_energy_scan(acc, n_energies: int):
@@ -339,6 +361,10 @@ SART_SYMBOLS = {
     "sart_trace_histogram_channels_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p, C.c_void_p]),
     "sart_trace_histogram_channels": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _P(Summary), _dp, _dp]),
     "sart_finalize_channels_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p, C.c_void_p]),
+    "sart_origin_block_len": (C.c_size_t, [_i, _i]),
+    "sart_trace_histogram_origin_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p, C.c_void_p]),
+    "sart_trace_histogram_origin": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _P(Summary), _dp, _dp]),
+    "sart_finalize_origin_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p, C.c_void_p]),
     "sart_reduce_across_devices": (C.c_int, [_P(C.c_void_p), _P(C.c_void_p), _i, C.c_size_t, _i]),
     "sart_enable_kernel_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "sart_get_kernel_timing": (C.c_int, [C.c_void_p, _dp, _P(C.c_int64)]),

@@ -58,6 +58,10 @@ void launch_finalize_channels(const void* in, double* out, int n_channels, int n
                               double q_w2, void* check_dev, hipStream_t stream);
 void launch_channel_fractions(const double* rates_dev, const double* total_dev, double* frac_dev, int n_channels, int stride,
                               size_t n_cells, unsigned long long* first_bad_dev, hipStream_t stream);
+int origin_histogram_blocks_per_cu(bool rotated);
+void launch_origin_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, double* acc, const OriginArgs& OG,
+                             int n_blocks, hipStream_t stream, bool rotated, bool fixed);
+void launch_finalize_origin(const void* in, double* out, size_t n_cells, double q_w, double q_w2, void* check_dev, hipStream_t stream);
 int histogram_block_of(int variant);
 void launch_trace_records(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, sart_axion_t* out, int n_blocks,
                           hipStream_t stream, const double* uniforms_dev);
@@ -306,6 +310,9 @@ struct sart_context {
   int n_channels = 0, chan_stride = 0;
   DevBuf<double> d_chan_frac, d_chan_partials, d_cblock, d_cblock_fin;
   int blocks_per_cu_channels[2] = {0, 0};
+  // solar-origin map (sart_trace_histogram_origin*): per-workgroup head sums, the blocking form's scratch block and its f64 image
+  DevBuf<double> d_origin_partials, d_oblock, d_oblock_fin;
+  int blocks_per_cu_origin[2] = {0, 0};
 
   // timing
   bool timing = false;
@@ -1836,7 +1843,9 @@ size_t channel_block_len_of(const sart_context* c, const sart_trace_params_t* p)
   return sart_channel_block_len(c->n_channels, c->n_energies, p->spectra, p->image_nx, p->image_ny);
 }
 
-// What the host path knows of a breakdown of the histogram trace (kShells, kChannels below): its kernel keeps a table in the last
+size_t origin_block_len_of(const sart_context* c, const sart_trace_params_t*) { return sart_origin_block_len(c->n_radii, c->n_energies); }
+
+// What the host path knows of a breakdown of the histogram trace (kShells, kChannels, kOrigin below): its kernel keeps a table in the last
 // cells of the LDS tile space and stores it once per workgroup, the fold adds those partials into the caller's block.
 struct Breakdown {
   int tile_max, tile_extra_max;                // widest LDS image tile beside the table: ring 0 free (no stage A0) / all rings in use
@@ -1858,9 +1867,9 @@ struct BreakdownBlock {   // which breakdown a launch fills, if any, and the cal
   double* dev = nullptr;
 };
 
-// sart_trace_histogram_device, and with a breakdown `bd` sart_trace_histogram_shells_device / sart_trace_histogram_channels_device:
-// the same host path (quanta, replicas, LDS tile, partials) around trace_histogram_kernel, shell_histogram_kernel or
-// channel_histogram_kernel.
+// sart_trace_histogram_device, and with a breakdown `bd` sart_trace_histogram_shells_device / sart_trace_histogram_channels_device /
+// sart_trace_histogram_origin_device: the same host path (quanta, replicas, LDS tile, partials) around trace_histogram_kernel,
+// shell_histogram_kernel, channel_histogram_kernel or origin_histogram_kernel.
 int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_dev, BreakdownBlock bd = {}) {
   SART_HIP(hipSetDevice(c->device));
   if (int rc = refresh_derived(c)) return rc;
@@ -2051,6 +2060,14 @@ int channels_check(sart_context* c, const sart_trace_params_t* p) {
   return 0;
 }
 
+// params that an origin launch and its finalize accept (the context stays as it is otherwise)
+int origin_check(sart_context* c, const sart_trace_params_t* p) {
+  if (int rc = shells_check(c, p)) return rc;
+  if (c->setup.test_active) return fail(SART_ERR_INVALID_ARGUMENT, "the X-ray test source is active: no solar sampling, no origin map");
+  if (!c->have_solar) return fail(SART_ERR_NOT_READY, "no solar tables");
+  return 0;
+}
+
 void launch_shells(sart_context* c, const TraceArgs& a, double* acc_dev, double* block_dev, int n_blocks, bool rotated, bool fixed) {
   ShellArgs sh;
   std::memset(&sh, 0, sizeof sh);
@@ -2074,6 +2091,16 @@ void launch_channels(sart_context* c, const TraceArgs& a, double* acc_dev, doubl
   launch_channel_histogram(c->hot, c->hotb, c->d_blob.p, a, acc_dev, ch, n_blocks, c->stream, rotated, fixed);
 }
 
+void launch_origin(sart_context* c, const TraceArgs& a, double* acc_dev, double* block_dev, int n_blocks, bool rotated, bool fixed) {
+  OriginArgs og;
+  std::memset(&og, 0, sizeof og);
+  og.block = block_dev;
+  og.partials = c->d_origin_partials.p;
+  og.n_radii = c->n_radii;
+  og.n_energies = c->n_energies;
+  launch_origin_histogram(c->hot, c->hotb, c->d_blob.p, a, acc_dev, og, n_blocks, c->stream, rotated, fixed);
+}
+
 const Breakdown kShells = {kShellImageTileMax, kShellImageTileExtraMax, static_cast<size_t>(kMaxShells) * kShellPartialSlots,
                            &sart_context::d_shell_partials, &sart_context::blocks_per_cu_shells, shell_histogram_blocks_per_cu,
                            shell_block_len_of, launch_shells, shells_check, &sart_context::d_sblock, &sart_context::d_sblock_fin,
@@ -2083,7 +2110,12 @@ const Breakdown kChannels = {kChanImageTileMax, kChanImageTileExtraMax, static_c
                              channel_block_len_of, launch_channels, channels_check, &sart_context::d_cblock, &sart_context::d_cblock_fin,
                              sart_finalize_channels_device};
 
-// The blocking form of a breakdown (sart_trace_histogram_shells / sart_trace_histogram_channels): launch into the context's scratch
+const Breakdown kOrigin = {kOriginImageTileMax, kOriginImageTileExtraMax, static_cast<size_t>(kOriginPartialSlots),
+                           &sart_context::d_origin_partials, &sart_context::blocks_per_cu_origin, origin_histogram_blocks_per_cu,
+                           origin_block_len_of, launch_origin, origin_check, &sart_context::d_oblock, &sart_context::d_oblock_fin,
+                           sart_finalize_origin_device};
+
+// The blocking form of a breakdown (sart_trace_histogram_shells / sart_trace_histogram_channels / sart_trace_histogram_origin): launch into the context's scratch
 // accumulator and block, finalize both in FIXED64, copy out what the caller asked for.
 int trace_histogram_breakdown(sart_context* c, const sart_trace_params_t* p, const Breakdown& kind, double* image_out,
                               sart_summary_t* summary, double* spectra_out, double* block_out) {
@@ -2277,6 +2309,35 @@ int sart_finalize_channels_device(sart_context* c, const sart_trace_params_t* p,
 int sart_trace_histogram_channels(sart_context* c, const sart_trace_params_t* p, double* image_out, sart_summary_t* summary,
                                   double* spectra_out, double* channels_out) {
   return trace_histogram_breakdown(c, p, kChannels, image_out, summary, spectra_out, channels_out);
+}
+
+// ---- solar-origin map (include/sart.h) -------------------------------------------------------
+size_t sart_origin_block_len(int32_t n_radii, int32_t n_energies) {
+  const size_t nr = n_radii > 0 ? static_cast<size_t>(n_radii) : 0u, ne = n_energies > 0 ? static_cast<size_t>(n_energies) : 0u;
+  return static_cast<size_t>(SART_ORIGIN_HEAD) + nr * ne * static_cast<size_t>(SART_ORIGIN_CELL);
+}
+
+int sart_trace_histogram_origin_device(sart_context* c, const sart_trace_params_t* p, double* acc_dev, double* origin_dev) {
+  if (!c || !p || !acc_dev || !origin_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (int rc = origin_check(c, p)) return rc;
+  return histogram_launch(c, p, acc_dev, {&kOrigin, origin_dev});
+}
+
+int sart_finalize_origin_device(sart_context* c, const sart_trace_params_t* p, const void* raw_dev, double* out_dev) {
+  if (!c || !p || !raw_dev || !out_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (int rc = origin_check(c, p)) return rc;
+  if (!c->quanta_frozen) return fail(SART_ERR_NOT_READY, "no FIXED64 launch has fixed the quanta yet");
+  SART_HIP(hipSetDevice(c->device));
+  if (int rc = status_ensure(c)) return rc;
+  launch_finalize_origin(raw_dev, out_dev, static_cast<size_t>(c->n_radii) * static_cast<size_t>(c->n_energies),
+                         std::ldexp(1.0, c->weight_exp), std::ldexp(1.0, c->weight_sq_exp), c->d_status.p, c->stream);
+  SART_HIP(hipGetLastError());
+  return status_enqueue_copy(c);
+}
+
+int sart_trace_histogram_origin(sart_context* c, const sart_trace_params_t* p, double* image_out, sart_summary_t* summary,
+                                double* spectra_out, double* origin_out) {
+  return trace_histogram_breakdown(c, p, kOrigin, image_out, summary, spectra_out, origin_out);
 }
 
 int sart_trace_histogram(sart_context* c, const sart_trace_params_t* p, double* image_out, sart_summary_t* summary) {

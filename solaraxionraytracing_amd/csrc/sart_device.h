@@ -326,10 +326,11 @@ static_assert(kTileExtraCells == kRingExtraCells + 16 * 512 / 8, "16 waves x 512
 constexpr int kImageTileMax = 64;
 constexpr int kImageTileExtraMax = 45;   // 45 x 45 <= kTileExtraCells: the tile of the variants whose rings are all in use
 
-// The two breakdowns of the histogram trace, per shell and per emission channel, are one pipeline: breakdown_histogram_body
-// (sart_kernels.hip) is the generic histogram kernel with a per-workgroup table in LDS, and shell_histogram_kernel and
-// channel_histogram_kernel are its two users (ShellBreakdown / ChannelBreakdown: the argument struct, the table, its cells).  What
-// follows is what each of them keeps in that table and hands to its fold.
+// The three breakdowns of the histogram trace, per shell, per emission channel and per cell of the solar table, are one pipeline:
+// breakdown_histogram_body (sart_kernels.hip) is the generic histogram kernel with a per-workgroup table in LDS, and
+// shell_histogram_kernel, channel_histogram_kernel and origin_histogram_kernel are its users (ShellBreakdown / ChannelBreakdown /
+// OriginBreakdown: the argument struct, the table, its cells).  What follows is what each of them keeps in that table and hands to
+// its fold.
 //
 // Per-shell breakdown of the histogram trace (include/sart.h: sart_trace_histogram_shells_device).  shell_histogram_kernel keeps,
 // per workgroup and shell, four u32 counters and two sums in LDS - in the last kShellTableCells cells behind the tables, where the
@@ -371,5 +372,28 @@ struct ChannelArgs {
   int32_t n_energies1, _pad;
 };
 static_assert(sizeof(ChannelArgs) == 48, "the kernel re-reads ChannelArgs with scalar loads");
+
+// Solar-origin map of the histogram trace (include/sart.h: sart_trace_histogram_origin_device).  origin_histogram_kernel adds every
+// passed ray to the cell (r_idx, e_idx) it was drawn in - three global atomics into one 32-byte cell of the caller's block: the map
+// has millions of cells, so no replicas and no LDS staging - and keeps, per workgroup and wave, the head's three sums (N_PASSED, sum
+// of w, sum of w^2: the wave's own scalars) in the last kOriginTableCells cells behind the tables (its image tile is therefore at most
+// kOriginImageTileMax / kOriginImageTileExtraMax wide), stored once to partials[n_blocks][kOriginPartialSlots]; fold_origin_kernel adds
+// those to the head of the caller's block.
+constexpr int kOriginPartialSlots = 4;   // N_PASSED, sum of w, sum of w^2, unused
+constexpr int kOriginTableCells = 16 * kOriginPartialSlots;   // one row per wave of a 1024-thread workgroup
+constexpr int kOriginImageTileMax = 55;        // 55 x 55 <= kTileRingCells + kRingExtraCells - kOriginTableCells
+constexpr int kOriginImageTileExtraMax = 32;   // 32 x 32 <= kRingExtraCells - kOriginTableCells
+static_assert(kOriginImageTileMax * kOriginImageTileMax <= kTileRingCells + kRingExtraCells - kOriginTableCells &&
+                  (kOriginImageTileMax + 1) * (kOriginImageTileMax + 1) > kTileRingCells + kRingExtraCells - kOriginTableCells &&
+                  kOriginImageTileExtraMax * kOriginImageTileExtraMax <= kRingExtraCells - kOriginTableCells &&
+                  (kOriginImageTileExtraMax + 1) * (kOriginImageTileExtraMax + 1) > kRingExtraCells - kOriginTableCells,
+              "the origin kernel's image tile is the largest square that leaves its table alone");
+struct OriginArgs {
+  double* block;          // the caller's block: SART_ORIGIN_HEAD slots, then cells[n_radii][n_energies][SART_ORIGIN_CELL]
+  double* partials;       // [n_blocks][kOriginPartialSlots] per-workgroup sums (plain stores)
+  int32_t n_radii, n_energies;   // the map's shape (the kernel clamps its indices to it)
+  double _pad;
+};
+static_assert(sizeof(OriginArgs) == 32, "the kernel re-reads OriginArgs with scalar loads");
 
 }  // namespace sart

@@ -2158,14 +2158,36 @@ static_assert(offsetof(ChanKernArgs, A) == offsetof(HistKernArgs, A) && offsetof
               "the channel kernel shares the argument offsets of the histogram kernel");
 
 // ------------------------------------------------------------------------------------------------
-// the one pipeline of both breakdowns: breakdown_histogram_body
+// solar-origin map of the histogram trace (include/sart.h: sart_trace_histogram_origin_device)
 // ------------------------------------------------------------------------------------------------
-// What a breakdown is to the body: its argument struct and where the kernel arguments hold it, its per-workgroup table in LDS (in
-// the last kTableCells cells behind the tables, the image tile's extra cells in front of it) and the slots it stores of it per
-// workgroup.  What the breakdown does to a ray stands in the body itself, under `if constexpr (BD::kShells)`: one ray can be followed
-// through one function.
+// The third user of the pipeline: the same accumulator plus, per passed ray, three global atomics (N, w, w^2) into the 32-byte cell
+// (r_idx, e_idx) of the caller's map - r_idx travels through ring 1, e_idx comes out of phase B - issued under the live mask of the
+// passed lanes behind the accumulator's own atomics.  The head of the block (N_PASSED and the two sums: what the cells must add up to)
+// is the wave's own scalars, kept per wave in the last kOriginTableCells cells behind the tables, summed and stored once per workgroup
+// and folded by fold_origin_kernel.
+struct OriginKernArgs {
+  HotA H;
+  const DevBlob* blob;
+  TraceArgs A;
+  double* acc;
+  HotB HB;
+  OriginArgs OG;
+};
+static_assert(offsetof(OriginKernArgs, A) == offsetof(HistKernArgs, A) && offsetof(OriginKernArgs, HB) == offsetof(HistKernArgs, HB) &&
+                  offsetof(OriginKernArgs, OG) == offsetof(HistKernArgs, SC),
+              "the origin kernel shares the argument offsets of the histogram kernel");
+static_assert(SART_ORIGIN_CELL == 4 && SART_ORIGIN_HEAD % SART_ORIGIN_CELL == 0, "a ray's three atomics fall into one aligned 32-byte cell");
+
+// ------------------------------------------------------------------------------------------------
+// the one pipeline of the three breakdowns: breakdown_histogram_body
+// ------------------------------------------------------------------------------------------------
+// What a breakdown is to the body: its kind, its argument struct and where the kernel arguments hold it, its per-workgroup table in
+// LDS (in the last kTableCells cells behind the tables, the image tile's extra cells in front of it) and the slots it stores of it
+// per workgroup.  What the breakdown does to a ray stands in the body itself, under `if constexpr (kShells / kChannels / kOrigin)`:
+// one ray can be followed through one function.
+enum class BreakdownKind { Shells, Channels, Origin };
 struct ShellBreakdown {
-  static constexpr bool kShells = true;
+  static constexpr BreakdownKind kKind = BreakdownKind::Shells;
   using Args = ShellArgs;
   static constexpr size_t kArgsOffset = offsetof(ShellKernArgs, SH);
   static constexpr int kTableCells = kShellTableCells;
@@ -2176,7 +2198,7 @@ struct ShellBreakdown {
   };
 };
 struct ChannelBreakdown {
-  static constexpr bool kShells = false;
+  static constexpr BreakdownKind kKind = BreakdownKind::Channels;
   using Args = ChannelArgs;
   static constexpr size_t kArgsOffset = offsetof(ChanKernArgs, CH);
   static constexpr int kTableCells = kChanTableCells;
@@ -2186,11 +2208,24 @@ struct ChannelBreakdown {
     uint32_t cnt[kMaxChannels][kChanLanes];   // per channel: N_CONTRIBUTING
   };
 };
+struct OriginBreakdown {
+  static constexpr BreakdownKind kKind = BreakdownKind::Origin;
+  using Args = OriginArgs;
+  static constexpr size_t kArgsOffset = offsetof(OriginKernArgs, OG);
+  static constexpr int kTableCells = kOriginTableCells;
+  template <class Sum>
+  struct Table {
+    Sum head[kOriginTableCells / kOriginPartialSlots][kOriginPartialSlots];   // per wave: N_PASSED, sum of w, sum of w^2, unused
+  };
+};
 
 template <int BLOCK, bool ROT, bool FIXED, class BD>
 __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* __restrict__ blob, TraceArgs A, double* __restrict__ acc,
                                                          typename BD::Args BDarg) {
   using Sum = std::conditional_t<FIXED, long long, double>;   // per-lane sums: quanta (FIXED) or f64
+  constexpr bool kShells = BD::kKind == BreakdownKind::Shells, kChannels = BD::kKind == BreakdownKind::Channels,
+                 kOrigin = BD::kKind == BreakdownKind::Origin;
+  static_assert(!kOrigin || BLOCK / 64 == kOriginTableCells / kOriginPartialSlots, "one row of the origin table per wave");
   struct LdsLayout {
     TablesLds S;
     double tile_extra[kRingExtraCells - BD::kTableCells];   // cells kTileRingCells .. of the image tile
@@ -2225,13 +2260,13 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
     uint64_t* q = reinterpret_cast<uint64_t*>(&Q);
     for (int i = threadIdx.x; i < (int)(sizeof(Q) / 8); i += BLOCK) q[i] = 0ull;
     for (int i = threadIdx.x; i < kRingExtraCells - BD::kTableCells; i += BLOCK) lds.tile_extra[i] = 0.0;
-    if constexpr (BD::kShells) {
+    if constexpr (kShells) {
       for (int i = threadIdx.x; i < kMaxShells * 4; i += BLOCK) lds.tab.cnt[i >> 2][i & 3] = 0u;
       for (int i = threadIdx.x; i < kMaxShells * 2; i += BLOCK) lds.tab.sum[i >> 1][i & 1] = 0;
-    } else {
+    } else if constexpr (kChannels) {
       for (int i = threadIdx.x; i < kMaxChannels * 3 * kChanLanes; i += BLOCK) (&lds.tab.sum[0][0][0])[i] = 0;
       if (threadIdx.x < kMaxChannels * kChanLanes) (&lds.tab.cnt[0][0])[threadIdx.x] = 0u;
-    }
+    }   // (origin: every wave writes its whole row in the epilogue)
   }
   stage_tables<BLOCK>(S, Pb, Tb);   // (its barrier orders the zeroing above before the first use)
   const LdsTables L{S.sincos, S.rcdf_hi, Tb.flux_radius_cdf, S.rguide, S.shells, S.lut};
@@ -2280,7 +2315,7 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
     n_reached += (uint32_t)__popcll(valid_m & M.reached);
     const uint64_t selected = valid_m & M.ok;
     n_shell += (uint32_t)__popcll(selected);
-    if constexpr (BD::kShells) {
+    if constexpr (kShells) {
       if (__builtin_amdgcn_inverse_ballot_w64(selected))
         __hip_atomic_fetch_add(&lds.tab.cnt[shell_of(st.shell)][0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
@@ -2332,7 +2367,7 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
     n_till += (uint32_t)__popcll(out.m_till);
     n_passed += (uint32_t)__popcll(out.m_passed);
     [[maybe_unused]] const uint32_t sh = shell_of(st.shell);   // (shells)
-    if constexpr (BD::kShells) {
+    if constexpr (kShells) {
       if (__builtin_amdgcn_inverse_ballot_w64(out.m_nickel))
         __hip_atomic_fetch_add(&lds.tab.cnt[sh][1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       if (__builtin_amdgcn_inverse_ballot_w64(out.m_till))
@@ -2343,7 +2378,7 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
       [[maybe_unused]] typename BD::Args BDl;     // (shells: re-read in the spectra branch)
       [[maybe_unused]] double f[kMaxChannels];    // channels: this ray's fractions
       [[maybe_unused]] uint32_t f_off = 0u;
-      if constexpr (!BD::kShells) {
+      if constexpr (kChannels) {
         // this ray's fractions: requested first, used behind the accumulator's own work.  The indices are clamped to the table (host:
         // its shape is the solar tables' and it is < 4 GB, so the byte offset is 32-bit).
         reload_kernarg(BDl, BD::kArgsOffset);
@@ -2372,17 +2407,18 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
       asm volatile("" :: "s"(Al.replicas), "s"(Al.replica_mask), "s"(Al.replica_stride), "s"(Al.image_nx), "s"(Al.image_ny),
                    "s"(Al.image_x_min), "s"(Al.image_y_min), "s"(Al.image_inv_step_x), "s"(Al.image_inv_step_y), "s"(Al.spectra),
                    "s"(Al.tile_x0), "s"(Al.tile_y0), "s"(Al.tile_n), "s"(Al.tile_base));
-      if constexpr (BD::kShells) __hip_atomic_fetch_add(&lds.tab.cnt[sh][3], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if constexpr (kShells) __hip_atomic_fetch_add(&lds.tab.cnt[sh][3], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       long long w_fx = 0;   // FIXED: this ray's weight in quanta (what the image, the sums and the spectra add)
+      [[maybe_unused]] long long w2_fx = 0;   //        and its squared weight's (what SUM_WEIGHTS_SQ adds; origin: and the ray's cell)
       if constexpr (FIXED) {
         w_fx = to_fixed(out.weight, Al.fx_scale_w);
-        const long long w2_fx = to_fixed(out.weight * out.weight, Al.fx_scale_w2);
+        w2_fx = to_fixed(out.weight * out.weight, Al.fx_scale_w2);
         sum_w += w_fx;
         sum_w2 += w2_fx;
         sum_x += to_fixed(out.px, kFixedPositionScale);
         sum_y += to_fixed(out.py, kFixedPositionScale);
         sum_r += to_fixed(out.rdet, kFixedPositionScale);
-        if constexpr (BD::kShells) {
+        if constexpr (kShells) {
           // the same integers the scalars add: the per-shell sums add up to SUM_WEIGHTS / SUM_WEIGHTS_SQ exactly
           __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(&lds.tab.sum[sh][0]), (unsigned long long)w_fx, __ATOMIC_RELAXED,
                                  __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2395,7 +2431,7 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
         sum_x += out.px;
         sum_y += out.py;
         sum_r += out.rdet;
-        if constexpr (BD::kShells) {
+        if constexpr (kShells) {
           __hip_atomic_fetch_add(&lds.tab.sum[sh][0], out.weight, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           __hip_atomic_fetch_add(&lds.tab.sum[sh][1], out.weight * out.weight, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
@@ -2414,7 +2450,7 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
       [[maybe_unused]] uint32_t c_pix = 0u;   // the ray's pixel, for the channel images
       if (inside) {
         const uint32_t ix = (uint32_t)(int)fx, iy = (uint32_t)(int)fy;
-        if constexpr (!BD::kShells) c_pix = iy * (uint32_t)nx + ix;
+        if constexpr (kChannels) c_pix = iy * (uint32_t)nx + ix;
         const uint32_t tn = (uint32_t)Al.tile_n;
         const uint32_t tx = ix - (uint32_t)Al.tile_x0, ty = iy - (uint32_t)Al.tile_y0;
         if ((tx < tn) & (ty < tn)) {
@@ -2438,7 +2474,7 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
         const int rb = min((int)(out.rdet * Al.radial_inv_bin), Al.n_radial_bins - 1);
         [[maybe_unused]] double* sen = nullptr;   // shells: counts[sh][e]
         [[maybe_unused]] size_t sw_off = 0;       //         -> weights[sh][e]
-        if constexpr (BD::kShells) {
+        if constexpr (kShells) {
           reload_kernarg(BDl, BD::kArgsOffset);
           sen = BDl.block + (size_t)BDl.n_shells * SART_SHELL_ROW + (size_t)sh * ne1 + (size_t)out.e_idx;
           sw_off = (size_t)BDl.n_shells * ne1;
@@ -2449,7 +2485,7 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
           atomic_add_slot_i64(&en[out.e_idx], 1);
           atomic_add_slot_i64(&en[ne1 + out.e_idx], w_fx);
           atomic_add_slot_i64(&en[2 * ne1 + out.e_idx], to_fixed(out.reflect, kFixedReflectScale));
-          if constexpr (BD::kShells) {
+          if constexpr (kShells) {
             atomic_add_slot_i64(sen, 1);
             atomic_add_slot_i64(sen + sw_off, w_fx);
           }
@@ -2459,14 +2495,32 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
           unsafeAtomicAdd(&en[out.e_idx], 1.0);
           unsafeAtomicAdd(&en[ne1 + out.e_idx], out.weight);
           unsafeAtomicAdd(&en[2 * ne1 + out.e_idx], out.reflect);
-          if constexpr (BD::kShells) {
+          if constexpr (kShells) {
             unsafeAtomicAdd(sen, 1.0);
             unsafeAtomicAdd(sen + sw_off, out.weight);
           }
         }
       }
+      // the origin map: the ray's cell (r_idx, e_idx) takes 1, w and w^2 - FIXED: the integers the scalars add, so the cells add up to
+      // the head exactly -, three atomics into one aligned 32-byte cell behind the accumulator's own.  The indices are clamped to the
+      // map (host: its shape is the solar tables').
+      if constexpr (kOrigin) {
+        reload_kernarg(BDl, BD::kArgsOffset);
+        const size_t cell = (size_t)min(max(st.r_idx, 0), BDl.n_radii - 1) * (size_t)BDl.n_energies +
+                            (size_t)min(max(out.e_idx, 0), BDl.n_energies - 1);
+        double* const oc = BDl.block + SART_ORIGIN_HEAD + cell * SART_ORIGIN_CELL;
+        if constexpr (FIXED) {
+          atomic_add_slot_i64(oc + SART_ORIGIN_N, 1);
+          atomic_add_slot_i64(oc + SART_ORIGIN_SUM_WEIGHTS, w_fx);
+          atomic_add_slot_i64(oc + SART_ORIGIN_SUM_WEIGHTS_SQ, w2_fx);
+        } else {
+          unsafeAtomicAdd(oc + SART_ORIGIN_N, 1.0);
+          unsafeAtomicAdd(oc + SART_ORIGIN_SUM_WEIGHTS, out.weight);
+          unsafeAtomicAdd(oc + SART_ORIGIN_SUM_WEIGHTS_SQ, out.weight * out.weight);
+        }
+      }
       // the channels: c_t = w f_t, ONE product; the same c_t to the row, the ray's energy bin and its pixel (or the row's OUTSIDE)
-      if constexpr (!BD::kShells) {
+      if constexpr (kChannels) {
         const uint32_t cl = (uint32_t)lane & (uint32_t)(kChanLanes - 1);
         const size_t c_ne1 = (size_t)BDl.n_energies1, c_nimg = (size_t)nx * (size_t)ny;
         double* const c_en = BDl.block + (size_t)BDl.n_channels * SART_CHAN_ROW;                  // energy_weights[t][e]
@@ -2617,6 +2671,12 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
     r[SART_ACC_N_SHELL_SELECTED] = (Sum)n_shell;
     r[SART_ACC_N_OUTSIDE_IMAGE] = (Sum)n_out;
     if constexpr (FIXED) r[SART_ACC_SUM_WEIGHTS_OUTSIDE] = swo;
+    if constexpr (kOrigin) {   // the head's row of this wave: the very sums the scalars take
+      lds.tab.head[wave][0] = (Sum)n_passed;
+      lds.tab.head[wave][1] = sw;
+      lds.tab.head[wave][2] = sw2;
+      lds.tab.head[wave][3] = 0;
+    }
   }
   __syncthreads();
   if (threadIdx.x < SART_ACC_COUNT) {
@@ -2625,7 +2685,13 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
     reinterpret_cast<Sum*>(A.partials)[(size_t)blockIdx.x * SART_ACC_COUNT + threadIdx.x] = t;
   }
   // the breakdown table of this workgroup (every wave has left the loop: the barriers above)
-  if constexpr (BD::kShells) {
+  if constexpr (kOrigin) {
+    if (threadIdx.x < kOriginPartialSlots) {
+      Sum t = 0;
+      for (int w = 0; w < BLOCK / 64; ++w) t += lds.tab.head[w][threadIdx.x];
+      reinterpret_cast<Sum*>(BDarg.partials)[(size_t)blockIdx.x * kOriginPartialSlots + threadIdx.x] = t;
+    }
+  } else if constexpr (kShells) {
     for (int i = threadIdx.x; i < kMaxShells * kShellPartialSlots; i += BLOCK) {
       const int s = i / kShellPartialSlots, j = i - s * kShellPartialSlots;
       const Sum v = j < 4 ? (Sum)lds.tab.cnt[s][j] : lds.tab.sum[s][j - 4];
@@ -2645,7 +2711,7 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
   }
 }
 
-// The two kernels: their names, template parameters and parameter lists are what the host launches and the code objects' tests know.
+// The three kernels: their names, template parameters and parameter lists are what the host launches and the code objects' tests know.
 template <int BLOCK, bool ROT, bool FIXED>
 __global__ __launch_bounds__(BLOCK) void shell_histogram_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
                                                                 double* __restrict__ acc, HotB HBarg, ShellArgs SHarg) {
@@ -2655,6 +2721,11 @@ template <int BLOCK, bool ROT, bool FIXED>
 __global__ __launch_bounds__(BLOCK) void channel_histogram_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
                                                                   double* __restrict__ acc, HotB HBarg, ChannelArgs CHarg) {
   breakdown_histogram_body<BLOCK, ROT, FIXED, ChannelBreakdown>(H, blob, A, acc, CHarg);
+}
+template <int BLOCK, bool ROT, bool FIXED>
+__global__ __launch_bounds__(BLOCK) void origin_histogram_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
+                                                                 double* __restrict__ acc, HotB HBarg, OriginArgs OGarg) {
+  breakdown_histogram_body<BLOCK, ROT, FIXED, OriginBreakdown>(H, blob, A, acc, OGarg);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4325,6 +4396,120 @@ __global__ __launch_bounds__(256) void finalize_channels_kernel(const long long*
   o[SART_CHAN_SUM_WEIGHTS_OUTSIDE] = ((double)v[SART_CHAN_SUM_WEIGHTS_OUTSIDE_HI] * two40 + (double)v[SART_CHAN_SUM_WEIGHTS_OUTSIDE]) * F.q_w;
 }
 
+// Head of the origin block (include/sart.h: SART_ORIGIN_*) += the per-workgroup sums of one origin_histogram_kernel launch.  One
+// workgroup, 64 threads = 4 slots (3 used) x 16 groups of workgroups, the summation tree of fold_channels_kernel.  FIXED: integers,
+// the two sums in two limbs (hi 2^40 + lo, lo in [0, 2^40)).
+template <bool FIXED>
+__global__ __launch_bounds__(64) void fold_origin_kernel(double* __restrict__ block_, const double* __restrict__ partials_, int n_blocks) {
+  using Sum = std::conditional_t<FIXED, long long, double>;
+  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
+  Sum* const head = reinterpret_cast<Sum*>(block_);
+  const Sum* const part = reinterpret_cast<const Sum*>(partials_);
+  __shared__ Sum red_lo[16][kOriginPartialSlots], red_hi[16][kOriginPartialSlots];
+  const int j = threadIdx.x & (kOriginPartialSlots - 1), g = threadIdx.x / kOriginPartialSlots;
+  Sum lo = 0, hi = 0;
+  for (int b = g; b < n_blocks; b += 16) {
+    const Sum p = part[(size_t)b * kOriginPartialSlots + j];
+    if constexpr (FIXED) { lo += p & kMask; hi += p >> kFixedLimbBits; } else lo += p;
+  }
+  red_lo[g][j] = lo;
+  red_hi[g][j] = hi;
+  __syncthreads();
+  if (g != 0 || j > 2) return;
+  lo = 0; hi = 0;
+  for (int i = 0; i < 16; ++i) { lo += red_lo[i][j]; hi += red_hi[i][j]; }
+  // partial slot 0 is the counter N_PASSED, 1 / 2 the sums
+  if (j == 0) {
+    if constexpr (FIXED) head[SART_ORIGIN_N_PASSED] += (hi << kFixedLimbBits) + lo; else head[SART_ORIGIN_N_PASSED] += lo;
+  } else {
+    const int s = j == 1 ? SART_ORIGIN_SUM_WEIGHTS : SART_ORIGIN_SUM_WEIGHTS_SQ, sh = j == 1 ? SART_ORIGIN_SUM_WEIGHTS_HI : SART_ORIGIN_SUM_WEIGHTS_SQ_HI;
+    if constexpr (FIXED) {
+      lo += head[s];
+      head[s] = lo & kMask;
+      head[sh] += hi + (lo >> kFixedLimbBits);
+    } else {
+      head[s] += lo;
+    }
+  }
+}
+
+// Raw FIXED64 origin block -> doubles (sart_finalize_origin_device), in two steps.  finalize_origin_kernel: the cells, one thread
+// per cell in a grid-wide loop; each slot is read and written by the same thread (in place allowed), the head is only read (whether
+// the squared weights are resolved: every SUM_WEIGHTS_SQ slot reads NaN where they are not).  Every slot must be in [0, 2^62), and the
+// column sums of the cells - N, and the two sums in two limbs - go through a wave reduction to the context's FixedCheck scratch
+// (pix: weights, rad: squared weights, en_lo: counts; zeroed by the host).  finalize_origin_head_kernel, behind it: the exact
+// conservation laws of the block - every passed ray adds 1 to N_PASSED and to its cell's N, and the same two integers to the head's
+// sums and to its cell's - and the head itself.
+struct FinalizeOriginArgs {
+  long long n_cells;
+  double q_w, q_w2;
+};
+__device__ __forceinline__ bool origin_squares_resolved(const long long* head) {
+  const double two40 = (double)(1ll << kFixedLimbBits);
+  const double n_passed = (double)head[SART_ORIGIN_N_PASSED];
+  const double sw2 = (double)head[SART_ORIGIN_SUM_WEIGHTS_SQ_HI] * two40 + (double)head[SART_ORIGIN_SUM_WEIGHTS_SQ];
+  return !(n_passed >= kFixedMinRaysForMeans) || sw2 >= 64.0 * n_passed;
+}
+__global__ __launch_bounds__(256) void finalize_origin_kernel(const long long* in, double* out, FinalizeOriginArgs F, FixedCheck* C) {
+  uint32_t* const status = &C->status;
+  const bool sq_ok = origin_squares_resolved(in);
+  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
+  long long cnt = 0, w_lo = 0, w_hi = 0, w2_lo = 0, w2_hi = 0;   // this thread's cells (a few: the limbs cannot overflow)
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < F.n_cells; i += stride) {
+    const size_t o = (size_t)SART_ORIGIN_HEAD + (size_t)i * SART_ORIGIN_CELL;
+    const long long n = in[o + SART_ORIGIN_N], w = in[o + SART_ORIGIN_SUM_WEIGHTS], w2 = in[o + SART_ORIGIN_SUM_WEIGHTS_SQ], r = in[o + 3];
+    fixed_status_check_slot(n, status);
+    fixed_status_check_slot(w, status);
+    fixed_status_check_slot(w2, status);
+    fixed_status_check_slot(r, status);
+    cnt += n;
+    w_lo += w & kMask;
+    w_hi += w >> kFixedLimbBits;
+    w2_lo += w2 & kMask;
+    w2_hi += w2 >> kFixedLimbBits;
+    out[o + SART_ORIGIN_N] = (double)n;
+    out[o + SART_ORIGIN_SUM_WEIGHTS] = (double)w * F.q_w;
+    out[o + SART_ORIGIN_SUM_WEIGHTS_SQ] = sq_ok ? (double)w2 * F.q_w2 : __builtin_nan("");
+    out[o + 3] = 0.0;
+  }
+  // (every thread is back here: whole waves reduce)
+  cnt = wave_sum_i64(cnt);
+  w_lo = wave_sum_i64(w_lo); w_hi = wave_sum_i64(w_hi);
+  w2_lo = wave_sum_i64(w2_lo); w2_hi = wave_sum_i64(w2_hi);
+  if ((threadIdx.x & 63) == 0) {
+    auto add = [](long long* dst, long long v) { if (v != 0) atomicAdd(reinterpret_cast<unsigned long long*>(dst), (unsigned long long)v); };
+    add(&C->en_lo, cnt);
+    add(&C->pix_lo, w_lo & kMask);
+    add(&C->pix_hi, w_hi + (w_lo >> kFixedLimbBits));
+    add(&C->rad_lo, w2_lo & kMask);
+    add(&C->rad_hi, w2_hi + (w2_lo >> kFixedLimbBits));
+  }
+}
+__global__ __launch_bounds__(64) void finalize_origin_head_kernel(const long long* in, double* out, FinalizeOriginArgs F, FixedCheck* C) {
+  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
+  if (threadIdx.x != 0) return;
+  uint32_t* const status = &C->status;
+  long long v[SART_ORIGIN_HEAD];
+  for (int j = 0; j < SART_ORIGIN_HEAD; ++j) { v[j] = in[j]; fixed_status_check_slot(v[j], status); }
+  auto same = [&](long long alo, long long ahi, long long blo, long long bhi) {
+    ahi += alo >> kFixedLimbBits; alo &= kMask;
+    bhi += blo >> kFixedLimbBits; blo &= kMask;
+    return alo == blo && ahi == bhi;
+  };
+  if (C->en_lo != v[SART_ORIGIN_N_PASSED] || !same(C->pix_lo, C->pix_hi, v[SART_ORIGIN_SUM_WEIGHTS], v[SART_ORIGIN_SUM_WEIGHTS_HI]) ||
+      !same(C->rad_lo, C->rad_hi, v[SART_ORIGIN_SUM_WEIGHTS_SQ], v[SART_ORIGIN_SUM_WEIGHTS_SQ_HI]))
+    atomicOr(status, kFixedStatusNotConserved);
+  const double two40 = (double)(1ll << kFixedLimbBits);
+  const double sw = (double)v[SART_ORIGIN_SUM_WEIGHTS_HI] * two40 + (double)v[SART_ORIGIN_SUM_WEIGHTS];
+  const double sw2 = (double)v[SART_ORIGIN_SUM_WEIGHTS_SQ_HI] * two40 + (double)v[SART_ORIGIN_SUM_WEIGHTS_SQ];
+  const bool sq_ok = origin_squares_resolved(v);
+  for (int j = 0; j < SART_ORIGIN_HEAD; ++j) out[j] = 0.0;
+  out[SART_ORIGIN_N_PASSED] = (double)v[SART_ORIGIN_N_PASSED];
+  out[SART_ORIGIN_SUM_WEIGHTS] = sw * F.q_w;
+  out[SART_ORIGIN_SUM_WEIGHTS_SQ] = sq_ok ? sw2 * F.q_w2 : __builtin_nan("");
+}
+
 // The fraction table of sart_set_source_channels[_device]: frac[cell stride + t] = rates[t][cell] / total[cell] (IEEE division; 0
 // where total == 0), t >= T padded with 0, a fraction in (1, 1 + 2^-49] stored as 1.  One thread per cell (r, e).  *first_bad (set to
 // ~0 by the host) = min over the offending entries of (cell 8 + t) 4 + code: 1 a negative or non-finite rate, 2 a fraction above
@@ -4935,6 +5120,10 @@ static const BreakdownKernels<ChannelArgs> kChannelKernels = {
     {channel_histogram_kernel<1024, true, false>, channel_histogram_kernel<1024, false, false>,
      channel_histogram_kernel<1024, false, true>, channel_histogram_kernel<1024, true, true>},
     {fold_channels_kernel<true>, fold_channels_kernel<false>}};
+static const BreakdownKernels<OriginArgs> kOriginKernels = {
+    {origin_histogram_kernel<1024, true, false>, origin_histogram_kernel<1024, false, false>,
+     origin_histogram_kernel<1024, false, true>, origin_histogram_kernel<1024, true, true>},
+    {fold_origin_kernel<true>, fold_origin_kernel<false>}};
 
 template <class Args>
 static int breakdown_blocks_per_cu(const BreakdownKernels<Args>& K, bool rotated) {
@@ -4972,6 +5161,20 @@ void launch_shell_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, 
 void launch_channel_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, double* acc, const ChannelArgs& CH,
                               int n_blocks, hipStream_t stream, bool rotated, bool fixed) {
   launch_breakdown_histogram(kChannelKernels, H, HB, blob, A, acc, CH, CH.n_channels, n_blocks, stream, rotated, fixed);
+}
+int origin_histogram_blocks_per_cu(bool rotated) { return breakdown_blocks_per_cu(kOriginKernels, rotated); }
+void launch_origin_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, double* acc, const OriginArgs& OG,
+                             int n_blocks, hipStream_t stream, bool rotated, bool fixed) {
+  launch_breakdown_histogram(kOriginKernels, H, HB, blob, A, acc, OG, 1, n_blocks, stream, rotated, fixed);   // (one row: the head)
+}
+void launch_finalize_origin(const void* in, double* out, size_t n_cells, double q_w, double q_w2, void* check_dev, hipStream_t stream) {
+  FinalizeOriginArgs F{(long long)n_cells, q_w, q_w2};
+  FixedCheck* const C = static_cast<FixedCheck*>(check_dev);
+  (void)hipMemsetAsync(reinterpret_cast<char*>(C) + 8, 0, offsetof(FixedCheck, fail) - 8, stream);   // everything but the status word and the failure record
+  const unsigned n_blocks = (unsigned)std::min<size_t>((n_cells + 255) / 256, 2048);
+  if (n_blocks > 0)
+    hipLaunchKernelGGL(finalize_origin_kernel, dim3(n_blocks), dim3(256), 0, stream, reinterpret_cast<const long long*>(in), out, F, C);
+  hipLaunchKernelGGL(finalize_origin_head_kernel, dim3(1), dim3(64), 0, stream, reinterpret_cast<const long long*>(in), out, F, C);
 }
 void launch_finalize_shells(const void* in, double* out, int n_shells, int n_energies1, int spectra, double q_w, double q_w2,
                             void* check_dev, hipStream_t stream) {

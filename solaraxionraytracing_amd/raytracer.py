@@ -44,6 +44,10 @@ class FullRaytraceSetup:
     # emission="agss09-device": the sampling tables are made on the GPU by the context that uploads this setup (emission
     # kernel -> CDFs -> guides, nothing crosses PCIe); fluxRadiusCDF / diffFluxCDFs stay None until fetch_solar_tables()
     device_emission: dict | None = None
+    # the grid and the emission table the CDFs were made from (None where the table exists on the device only): what a solar-origin
+    # map is reweighted against (origin.py)
+    radii: np.ndarray | None = None
+    em_rates: np.ndarray | None = None
 
     def fetch_solar_tables(self, tracer: "RayTracer"):
         """Host copies of the CDFs a context built on the device (for the CPU oracle, plots, files)."""
@@ -132,7 +136,8 @@ def initFullSetup(experiment: int = _lib.ES_BABYIAXO, detector: int = _lib.DK_IN
     meta = {"emission": meta_em, "reflectivity": meta_r}
     if dev_em is not None and dev_em.get("notes"):
         meta["notes"] = list(dev_em["notes"])
-    return FullRaytraceSetup(setup, np.ascontiguousarray(energies), rcdf, ecdf, refl, det, flags, meta=meta, device_emission=dev_em)
+    return FullRaytraceSetup(setup, np.ascontiguousarray(energies), rcdf, ecdf, refl, det, flags, meta=meta, device_emission=dev_em,
+                             radii=np.ascontiguousarray(radii), em_rates=None if em is None else np.ascontiguousarray(em, dtype=np.float64))
 
 
 def columns_from_records(records: np.ndarray, columns, ray_ids=None) -> dict:
@@ -623,6 +628,42 @@ class RayTracer:
         _lib.check(self.lib.sart_finalize_channels_device(self.handle, C.byref(params), C.c_void_p(raw_ptr),
                                                           C.c_void_p(out_ptr if out_ptr is not None else raw_ptr)))
 
+    # -- solar-origin map (include/sart.h "solar-origin map of the histogram trace") -----------
+    def origin_block_len(self) -> int:
+        """sart_origin_block_len for this context's solar tables."""
+        return int(self.lib.sart_origin_block_len(self._n_radii(), self.full.energies.size))
+
+    origin_params = shells_params
+
+    def trace_origin(self, n_rays: int, seed: int = 299792458, ray_id_offset: int = 0, flags: int | None = None, image_n: int = 256,
+                     spectra: bool = True, n_radial_bins: int = 10_000, radial_max: float = 10.0):
+        """trace_histogram (trace_spectra with ``spectra``) plus the solar-origin map (sart_trace_histogram_origin): the detected
+        weight per cell (radius index, energy index) of the emission table the passed rays were drawn in.  Returns (image, summary,
+        spectra dict or None, origin dict: ``head`` and the maps ``counts``, ``weights``, ``weights_sq`` [n_radii][n_energies]); see
+        solaraxionraytracing_amd.origin for what the maps answer."""
+        p = self.origin_params(n_rays, seed, ray_id_offset, flags, image_n, spectra, n_radial_bins, radial_max)
+        n_r, n_e = self._n_radii(), self.full.energies.size
+        img = np.empty((image_n, image_n))
+        summ = Summary()
+        spec = np.empty(2 * n_radial_bins + 3 * (n_e + 1)) if spectra else None
+        block = np.empty(_lib.origin_block_len(n_r, n_e))
+        _lib.check(self.lib.sart_trace_histogram_origin(self.handle, C.byref(p), _lib.as_dp(img) if image_n else None, C.byref(summ),
+                                                        _lib.as_dp(spec) if spectra else None, _lib.as_dp(block)))
+        return (img, {k: summ.v[i] for k, i in _lib.ACC.items()},
+                split_spectra(spec, n_radial_bins, n_e + 1, radial_max) if spectra else None, split_origin(block, n_r, n_e))
+
+    def trace_origin_device(self, params: TraceParams, accumulator_ptr: int, origin_ptr: int):
+        """Asynchronous form: adds into a device accumulator and a device block of origin_block_len() slots (raw int64 in fixed64
+        mode); ``params.accumulate`` as in trace_channels_device."""
+        _lib.check(self.lib.sart_trace_histogram_origin_device(self.handle, C.byref(params), C.c_void_p(accumulator_ptr),
+                                                               C.c_void_p(origin_ptr)))
+
+    def finalize_origin_device(self, params: TraceParams, raw_ptr: int, out_ptr: int | None = None):
+        """Raw FIXED64 origin block (device) -> doubles (device; in place by default).  Asynchronous; what the conversion finds wrong
+        is raised by the next ``synchronize()``."""
+        _lib.check(self.lib.sart_finalize_origin_device(self.handle, C.byref(params), C.c_void_p(raw_ptr),
+                                                        C.c_void_p(out_ptr if out_ptr is not None else raw_ptr)))
+
     # -- fused axion-mass scan (gas stage; include/sart.h "fused axion-mass scan") -------------
     def trace_mass_scan(self, masses_ev, n_rays: int, seed: int = 299792458, ray_id_offset: int = 0, flags: int | None = None):
         """Every ray of [ray_id_offset, ray_id_offset + n_rays) traced ONCE and weighed for every axion mass.  Returns
@@ -805,6 +846,8 @@ def write_shell_csvs(outpath: str, year: str, shells: dict, energies: np.ndarray
 
 channel_block_len = _lib.channel_block_len
 split_channels = _lib.split_channels
+origin_block_len = _lib.origin_block_len
+split_origin = _lib.split_origin
 
 # Which coupling every term of the emission table carries (csrc/sart_emission.hip: the g_ae^2, g_agamma^2 and g_anuclei^2 factors of
 # its eight terms, in the order of _lib.EM_TERMS), and the reference values the library's table is made with (readOpacityFile.nim:640-643).
