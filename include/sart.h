@@ -721,7 +721,10 @@ int sart_finalize_energy_scan_device(sart_context* ctx, const sart_trace_params_
  *   shells_device       the block: n_shells rows of SART_SHELL_ROW 8-byte slots (f64, or int64 when raw SART_ACCUM_FIXED64)
  *                         SART_SHELL_N_SELECTED            rays that selected shell s (sum over shells = SART_ACC_N_SHELL_SELECTED;
  *                                                          rays that stage A0 or the shell0_miss_radius shortcut end there count
- *                                                          as shell 0, where they are)
+ *                                                          as shell 0, where they are; the mirror-miss shortcut of the plain
+ *                                                          histogram trace - rays of the shells above that surely miss the first
+ *                                                          mirror and hit the nickel end in phase A - is not part of the breakdown
+ *                                                          kernels: there such a ray goes through phase B, same counts)
  *                         SART_SHELL_N_HIT_NICKEL          stopped by shell s's nickel (:2040-2057)   (= SART_ACC_N_HIT_NICKEL)
  *                         SART_SHELL_N_PASSED_TILL_WINDOW                                             (= SART_ACC_N_PASSED_TILL_WINDOW)
  *                         SART_SHELL_N_PASSED                                                         (= SART_ACC_N_PASSED)

@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <mutex>
 #include <string>
@@ -65,6 +66,7 @@ void launch_finalize_origin(const void* in, double* out, size_t n_cells, double 
 int histogram_block_of(int variant);
 void launch_trace_records(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, sart_axion_t* out, int n_blocks,
                           hipStream_t stream, const double* uniforms_dev);
+void launch_mirror_miss_count(const HotA& H, const DevBlob* blob, const TraceArgs& A, unsigned long long* counts, int n_blocks, hipStream_t stream);
 int records_block();
 int compact_chunk_max();
 void launch_compact_records(const sart_axion_t* rec, uint32_t n, sart_axion_t* out, unsigned long long capacity, uint32_t* block_counts,
@@ -194,7 +196,7 @@ struct sart_context {
     uint32_t debug_flags = 0;        // SART_DEBUG_FLAGS=<hex>: 0x20000000 stage A0 drops every ray, 0x10000000 stage A1 does
 #endif
     bool no_early_reject = false;    // SART_NO_EARLY_REJECT: stage A0 off
-    bool no_sure_miss = false;       // SART_NO_SURE_MISS: rays that provably miss the innermost shell's mirror go through phase B
+    bool no_sure_miss = false;       // SART_NO_SURE_MISS: rays that provably miss their shell's first mirror go through phase B (both shortcuts off)
     bool no_image_tile = false;      // SART_NO_IMAGE_TILE: small focal spots go to global atomics only (as before the tile)
     bool no_path_const = false;      // SART_NO_PATH_CONST: never use the constant-path kernel variant (5)
     bool no_host_prefault = false;   // SART_NO_HOST_PREFAULT: sart_trace_records leaves the caller's buffer as it finds it
@@ -712,6 +714,81 @@ double shell0_miss_radius_of(const sart_setup_t& s, const DevParams& P, int n_ra
   return -1.0;
 }
 
+// DevParams::mirror_miss_radius and mirror_miss_slope_sq: R1[j_min - 1] for the lowest shell j_min >= 1 such that every shell from
+// j_min outwards has the two proofs below, and the bound m^2 on the squared slope that proof (b) holds under; radius +infinity
+// where no shell has them (and for the X-ray test source, cones and a turned telescope: no slope bound, no paraboloid, z of
+// pointExitCB per ray).  A ray whose radial distance at the entrance plane is above R1[j_min - 1] selects a shell j >= j_min (the
+// first shell with R1 > radial, :1932-1957).  In the telescope frame the ray is (X0 + z tsx, Y0 + z tsy, z) with |(tsx, tsy)| <=
+// s_max (unrotated: the magnet-frame slopes).  Both values travel as floats, the radius rounded up and the slope bound down.
+//
+// (a) A sure miss of mirror 1.  pick_root solves f(z) = a z^2 + 2 hb z + c with a = A0 - m1_k, hb = D0 + m1_hb, c = Q0 - m1_cc and
+// accepts a root in (0, m1_zhi).  Paraboloid: m1_k = 0, so a = A0 >= 0, and m1_zhi = l cos(beta) <= l (both checked per shell).
+// f(z) is the ray's squared distance from the axis minus the paraboloid's squared radius r3^2 + e (l - z), so f(l) = |(X0 + l tsx,
+// Y0 + l tsy)|^2 - r3^2 (m1_cc - 2 l m1_hb = r3^2 = n1_r3sq up to their rounding, which is measured here and counted below).  The
+// kernel tests |(X0 + l tsx, Y0 + l tsy)|^2 + eps < n1_r3sq, eps = kMirrorMissEps: f(l) < -eps.  |D0| <= R1 s_max (radial < R1 of
+// the selected shell), so hb >= m1_hb - R1 s_max =: hb_min, required > 1e-3: with a >= 0 then f' = 2 (a z + hb) > 0 on [0, l], f
+// rises, and c = f(0) <= f(l) - 2 l hb_min < -eps as well.  c < 0 <= a and hb > 0 as doubles: pick_root's q = -hb - sqrt(..) < 0,
+// its roots q^2 raq (the sign of a q: negative, or an infinity for a = 0) and c a raq carry their signs whatever the rounding, so
+// the first is not accepted.  The other, z+ = c / q > 0, is where the convex f returns to 0 behind l: f(z+) - f(l) <= f'(z+) (z+ - l)
+// with f'(z+) = 2 sqrt(hb^2 - a c), so z+ >= l + eps / (2 S), S = (R1 s_max + m1_hb) + s_max R1 >= sqrt(hb^2 + a |c|).
+// pick_root's value of it carries a relative error below eta = 2^-46 (64 ulp: disc, the square root, q, a q, the reciprocal with its
+// Newton step and two products are below 2 ulp each) and is rejected once z+ (1 - eta) >= l, which eps >= 4 eta l S ensures.  The
+// kernel's evaluation of the left side and phase B's rounding of a, hb, c move f(l) by less than 16 ulp of R1^2 + 2 l (R1 s_max +
+// m1_hb) + (s_max l)^2.  A shell counts as proved only if eps is 1e4 times the sum of all three (BabyIAXO / XMM: eps = 1e-3 mm^2
+// against 2e-10; in radial distance at the mirror's end eps is 2e-6 mm).  An a of exactly 0, or one that underflows in a q, gives
+// infinities or NaN in both roots: a miss as well.
+//
+// (b) Its nickel verdict is "hit".  A ray that missed gets z1 = zcb = -(dz3 - dz1) and the normal of normal_z_general at p =
+// (X0 + zcb tsx, Y0 + zcb tsy): n = rho (e_rho, kappa), rho = |p|, kappa = r3 tan(beta) / sqrt(r3^2 + e (l - zcb)) - one value per
+// shell.  With w = (tsx, tsy, 1) and A0 = tsx^2 + tsy^2: n.w = rho (sigma + kappa), sigma = e_rho . (tsx, tsy), |sigma| <= sqrt(A0),
+// so for A0 < m^2 <= s_max^2 and m < kappa:  sin(a1) = |n.w| / (|n| |w|) >= (kappa - m) / sqrt((1 + kappa^2) (1 + s_max^2)).
+// lineHitsNickel (:1706-1734) in the kernel's form is sin^2(a1) (lz^2 + num^2) > num^2 with lz = l - zcb > 0 and num = nickel_num
+// > 0: true for every such ray of shell j if m <= m_j = kappa - t sqrt((1 + kappa^2) (1 + s_max^2)), t^2 = num^2 (1 + 1e-6) /
+// (lz^2 + num^2) - six orders above the rounding of either side.  m = min(s_max, the smallest m_j of the shells that take part); a
+// shell with m_j < 0.4 s_max ends the list (it would narrow the test for every shell: at the solar core's slopes, where the
+// rays are, nothing is lost above that).  With the full solar table s_max alone (m_j >= s_max) proves 21 of BabyIAXO / XMM's 58
+// shells, m = 0.57 s_max all 57.  rho > 0: R1[j - 1] - |zcb| s_max > 0 is checked.  Phase B would count such a ray in
+// N_HIT_NICKEL and end it there (:2045).
+struct MirrorMissBounds {
+  float radius, slope_sq;
+};
+MirrorMissBounds mirror_miss_bounds_of(const sart_setup_t& s, const DevParams& P, const std::vector<ShellDev>& shells, int n_radii) {
+  const MirrorMissBounds never = {std::numeric_limits<float>::infinity(), 0.0f};
+  if (P.test_active || n_radii < 1 || !P.telescope_wolter || P.rotated || s.n_shells < 2) return never;
+  const double R = P.radius_cb;
+  const double r_sun_max = (0.0015 + (n_radii - 1) * 0.0005) * P.sun_radius;
+  const double s_max = (r_sun_max + R) / (P.sun_distance + P.length_b - r_sun_max) * (1.0 + 1e-6);
+  const HotA h = hot_of(P);
+  const double l = P.l_mirror, zcb = -(h.dz3 - h.dz1), lz = l - zcb;
+  if (!(l > 0.0) || !(zcb <= 0.0)) return never;
+  const double eta = std::ldexp(1.0, -46), ulp16 = std::ldexp(1.0, -49);
+  int j_min = s.n_shells;
+  double m = s_max;
+  for (int j = s.n_shells - 1; j >= 1; --j) {
+    const ShellDev& sh = shells[static_cast<size_t>(j)];
+    // (a)
+    const double hb_max = sh.r1 * s_max + sh.m1_hb, hb_min = sh.m1_hb - sh.r1 * s_max, S = hb_max + s_max * sh.r1;
+    const double moved = 4.0 * eta * l * S + ulp16 * (sh.r1 * sh.r1 + 2.0 * l * hb_max + s_max * l * s_max * l) +
+                         std::fabs(sh.m1_cc - 2.0 * l * sh.m1_hb - sh.n1_r3sq);
+    const bool a_ok = sh.m1_k == 0.0 && sh.m1_zhi <= l && hb_min > 1e-3 && kMirrorMissEps > 1e4 * moved;
+    // (b)
+    const double kappa = sh.n1_r3t / std::sqrt(sh.n1_r3sq + sh.n1_e * lz), num = sh.nickel_num;
+    const double t = std::sqrt(num * num * (1.0 + 1e-6) / (lz * lz + num * num));
+    const double m_j = kappa - t * std::sqrt((1.0 + kappa * kappa) * (1.0 + s_max * s_max));
+    const bool b_ok = num > 0.0 && shells[static_cast<size_t>(j) - 1].r1 + zcb * s_max > 0.0 && m_j >= 0.4 * s_max;
+    if (!(a_ok && b_ok)) break;
+    m = std::min(m, m_j);
+    j_min = j;
+  }
+  if (j_min >= s.n_shells) return never;
+  MirrorMissBounds b;
+  b.radius = static_cast<float>(shells[static_cast<size_t>(j_min) - 1].r1);
+  if (static_cast<double>(b.radius) < shells[static_cast<size_t>(j_min) - 1].r1) b.radius = std::nextafterf(b.radius, std::numeric_limits<float>::infinity());
+  b.slope_sq = static_cast<float>(m * m);
+  if (static_cast<double>(b.slope_sq) > m * m) b.slope_sq = std::nextafterf(b.slope_sq, 0.0f);
+  return b;
+}
+
 // A bound on the angle of the telescope's rotation (rotateInY o rotateInX about (0, 0, lT/2), raytracer.nim:1888-1894) for
 // telescope_turned_y = angle_y_deg: the angle of a product of two rotations is at most the sum of their angles.  Exactly 0 for a
 // telescope that is not turned (then build_zones adds no margin: the zones of rounds 1-5).  With SART_NO_TILT_ZONES set in the
@@ -819,6 +896,12 @@ int sync_blob(sart_context* c) {
   SART_HIP(hipStreamSynchronize(c->stream));
   c->params.shell0_miss_radius =
       (c->knobs.no_sure_miss || c->knobs.no_early_reject) ? -1.0 : shell0_miss_radius_of(c->setup, c->params, c->n_radii);
+  {
+    const MirrorMissBounds off = {std::numeric_limits<float>::infinity(), 0.0f};
+    const MirrorMissBounds b = (c->knobs.no_sure_miss || c->knobs.no_early_reject) ? off : mirror_miss_bounds_of(c->setup, c->params, c->shells, c->n_radii);
+    c->params.mirror_miss_radius = b.radius;
+    c->params.mirror_miss_slope_sq = b.slope_sq;
+  }
   DevBlob b;
   std::memset(&b, 0, sizeof b);
   b.P = c->params;
@@ -1426,6 +1509,41 @@ __attribute__((visibility("default"))) int sart_internal_shell0_miss_radius(sart
   if (int rc = refresh_derived(c)) return rc;
   if (int rc = sync_blob(c)) return rc;
   *out = c->params.shell0_miss_radius;
+  return 0;
+}
+
+// Test entry (not in sart.h): the mirror-miss shortcut as the next launch would use it.  radius, slope_sq: DevParams::
+// mirror_miss_radius (+infinity: off) and mirror_miss_slope_sq.  thresholds[n_shells] (may be NULL): per shell the value below which the ray's squared distance from the axis at
+// z = l_mirror must lie for it to end in phase A, n1_r3sq - kMirrorMissEps, or -infinity for a shell the shortcut leaves alone.  counts[5] (may be NULL; then params may be NULL too): mirror_miss_count_kernel's counts for the rays of
+// `params`, taken by that kernel alone.
+__attribute__((visibility("default"))) int sart_internal_mirror_miss(sart_context* c, const sart_trace_params_t* params, double* radius,
+                                                                     double* slope_sq, double* thresholds, unsigned long long* counts) {
+  if (!c || !radius || !slope_sq) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  SART_HIP(hipSetDevice(c->device));
+  if (int rc = refresh_derived(c)) return rc;
+  if (int rc = sync_blob(c)) return rc;
+  const double rmin = c->params.mirror_miss_radius;
+  *radius = rmin;
+  *slope_sq = c->params.mirror_miss_slope_sq;
+  if (thresholds) {
+    for (int j = 0; j < c->setup.n_shells; ++j) {
+      const ShellDev& sh = c->shells[static_cast<size_t>(j)];
+      const bool on = j > 0 && sh.r1 > rmin;   // (rmin is R1 of the shell below the lowest one that takes part, rounded up to a float)
+      thresholds[j] = on ? sh.n1_r3sq - kMirrorMissEps : -std::numeric_limits<double>::infinity();
+    }
+  }
+  if (counts) {
+    TraceArgs a;
+    if (int rc = make_args(c, params, a)) return rc;
+    DevBuf<unsigned long long> d_counts;
+    const unsigned long long zero[5] = {0, 0, 0, 0, 0};
+    if (int rc = d_counts.upload(zero, 5)) return rc;
+    if (a.n_rays > 0)
+      launch_mirror_miss_count(c->hot, c->d_blob.p, a, d_counts.p, grid_for(a.n_rays, c->n_cu, 4, records_block()), c->stream);
+    SART_HIP(hipGetLastError());
+    SART_HIP(hipMemcpyAsync(counts, d_counts.p, sizeof zero, hipMemcpyDeviceToHost, c->stream));
+    SART_HIP(hipStreamSynchronize(c->stream));
+  }
   return 0;
 }
 

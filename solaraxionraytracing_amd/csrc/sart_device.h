@@ -101,7 +101,7 @@ struct DevParams {
   int32_t n_radii, n_energies;
   int32_t radius_span;        // max entries of fluxRadiusCDF between two guide marks a draw can meet (informational: the kernel reads four
                               // candidates and searches on only in a wider bracket)
-  int32_t _pad0;
+  int32_t lut_n;              // cells of the shell selection's look-up table (here: its slot beside lut_inv_step holds mirror_miss_radius)
   // ---- X-ray test source (raytracer.nim:1765-1806) ----
   int32_t test_active, test_parallel;
   double test_x, test_y, test_z, test_radius, test_radius_sq, test_collimator_z;
@@ -115,7 +115,14 @@ struct DevParams {
   // ---- shell selection (raytracer.nim:1932-1957) ----
   double r1_last;             // allR1[^1]
   double lut_inv_step;
-  int32_t lut_n, _pad1;
+  // The mirror-miss shortcut of trace_histogram_kernel.  A ray whose radial distance at the entrance plane lies above
+  // mirror_miss_radius selects a shell for which the host has proved two things (sart_api.hip: mirror_miss_bounds_of): (a) if the ray
+  // at z = l_mirror is more than kMirrorMissEps (mm^2, squared distances from the axis) inside the first mirror's radius there,
+  // pick_root accepts neither root of the mirror's quadratic; (b) if its squared slope tsx^2 + tsy^2 is below mirror_miss_slope_sq,
+  // the nickel test of a ray that missed the first mirror is true.  The kernel makes those compares in phase A and ends such a ray
+  // there with +1 in N_HIT_NICKEL, which is all phase B would have made of it.  Radius +infinity: the shortcut is off.  (Two floats,
+  // rounded to the safe side, in the eight bytes the block has to spare.)
+  float mirror_miss_radius, mirror_miss_slope_sq;
   // A ray that selects the innermost shell (none below it, so no nickel test, :1719) from a radial distance below this value
   // provably stays inside that shell's first mirror over its whole length: neither root of findPosParabolic lies in the
   // mirror (:677-682), the input point comes back and the ray ends at the no-hit test (:2055) with every counter untouched.
@@ -323,6 +330,9 @@ constexpr int kTileRingCells = 2048;
 constexpr int kRingExtraCells = 1090;
 constexpr int kTileExtraCells = 2114;
 static_assert(kTileExtraCells == kRingExtraCells + 16 * 512 / 8, "16 waves x 512 bytes");
+// Margin of the end-radius compare of the mirror-miss shortcut, mm^2 (DevParams::mirror_miss_radius; the host checks per shell that it
+// is more than 1e4 times what rounding can move either side by)
+constexpr double kMirrorMissEps = 1e-3;
 constexpr int kImageTileMax = 64;
 constexpr int kImageTileExtraMax = 45;   // 45 x 45 <= kTileExtraCells: the tile of the variants whose rings are all in use
 

@@ -849,9 +849,11 @@ __device__ __forceinline__ void phase_a_bore(const HotA& H, const DevParams& P, 
 
 // ---- second half: telescope frame -> opaque structures -> shell selection (:1878-1957) ----
 // `R`: the telescope's rotation; `shell0`-style shortcuts stay with the caller.  Returns true if the ray goes on to the mirrors.
+// `r3sq` (optional): n1_r3sq of the selected shell - the squared radius of its paraboloid at z = l_mirror - for the caller's
+// mirror-miss shortcut.
 template <bool FAST, int ROT>
 __device__ __forceinline__ bool phase_a_telescope(const HotA& H, const DevParams& P, const TelRot& R, const LdsTables& L, const BoreRay& br,
-                                                  RayState& st, double& radial_out, LaneMasks& M) {
+                                                  RayState& st, double& radial_out, LaneMasks& M, double* r3sq = nullptr) {
   const bool cfg_rotated = (ROT < 0) ? (H.rotated != 0) : (ROT != 0);
   const bool cfg_holes = FAST ? false : (H.telescope_kind == SART_TK_XMM && H.inner_blocks < 0);
   const double x1 = br.x1, y1 = br.y1, x3 = br.x3, y3 = br.y3, sx = br.sx, sy = br.sy;
@@ -982,18 +984,26 @@ __device__ __forceinline__ bool phase_a_telescope(const HotA& H, const DevParams
   M.ok = okm;
   st.shell = min(j, nS - 1);
   radial_out = radial;
+  if (r3sq) {
+    // read beside c_r1 / c_ro for the cell's shell and the one above it (the selected shell is one of the two): no LDS round trip
+    // behind the selection.  (jc + 1 == nS only for a ray without a shell; the record behind the last one is still LDS of the table
+    // block, and `ok` is false for that ray.)
+    const double c_r3sq = L.shells[jc].n1_r3sq, u_r3sq = L.shells[jc + 1].n1_r3sq;
+    *r3sq = step ? u_r3sq : c_r3sq;
+  }
   return ok;
 }
 
 // Both halves back to back (histogram and record kernels).
 template <bool FAST, int ROT, bool ZEXT, bool NOWALL = false, bool WORD = false>
 __device__ __forceinline__ bool phase_a_core(const HotA& H, const DevParams& P, const LdsTables& L, const Uniforms& U, RayState& st,
-                                             bool& sampled, bool& reached, double& radial_out, LaneMasks& M, const SinCosCoef* held = nullptr) {
+                                             bool& sampled, bool& reached, double& radial_out, LaneMasks& M, const SinCosCoef* held = nullptr,
+                                             double* r3sq = nullptr) {
   static_assert(!ZEXT || (FAST && ROT == 0), "the z-extent form needs the magnet-frame slopes in phase B");
   static_assert(!NOWALL || ZEXT, "the constant-path form is a specialisation of the vacuum, unrotated one");
   BoreRay br;
   phase_a_bore<FAST, ZEXT, NOWALL, WORD>(H, P, L, U, st, sampled, reached, br, M, held);
-  return phase_a_telescope<FAST, ROT>(H, P, tel_rot_of(P), L, br, st, radial_out, M);
+  return phase_a_telescope<FAST, ROT>(H, P, tel_rot_of(P), L, br, st, radial_out, M, r3sq);
 }
 
 // Phase A of the ray with global id `ray_id`: its six uniforms from ONE Philox counter block (x, y, z, w) + its word s of the
@@ -1022,8 +1032,9 @@ __device__ __forceinline__ Uniforms uniforms_of(uint32_t seed_lo, uint32_t seed_
 template <bool FAST, int ROT, bool ZEXT, bool NOWALL = false, bool WORD = true>
 __device__ __forceinline__ bool phase_a(const HotA& H, const DevParams& P, const LdsTables& L, uint32_t seed_lo,
                                         uint32_t seed_hi, uint64_t ray_id, uint32_t u3_hi, RayState& st, bool& sampled,
-                                        bool& reached, double& radial, LaneMasks& M, const SinCosCoef* held = nullptr) {
-  return phase_a_core<FAST, ROT, ZEXT, NOWALL, WORD>(H, P, L, uniforms_of(seed_lo, seed_hi, ray_id, u3_hi), st, sampled, reached, radial, M, held);
+                                        bool& reached, double& radial, LaneMasks& M, const SinCosCoef* held = nullptr,
+                                        double* r3sq = nullptr) {
+  return phase_a_core<FAST, ROT, ZEXT, NOWALL, WORD>(H, P, L, uniforms_of(seed_lo, seed_hi, ray_id, u3_hi), st, sampled, reached, radial, M, held, r3sq);
 }
 
 // z of pointExitCB in the rotated telescope frame (z0 of :2051) from the ray as phase B knows it: the point of the ray whose z
@@ -1703,21 +1714,37 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
     reload_hot(Hl);
     constexpr bool ZEXT = FAST && !ROT && GAS >= 0;
     LaneMasks M;
+    double r3sq = 0.0;
     (void)phase_a<FAST, ROT ? 1 : 0, ZEXT, PATHC>(Hl, Pb, L, A.seed_lo, A.seed_hi, id_base + (uint64_t)rel, u3_hi, st, sampled, reached, radial, M,
-                                                  HOLD_SINCOS ? &Ksc : nullptr);
+                                                  HOLD_SINCOS ? &Ksc : nullptr, ROT ? nullptr : &r3sq);
     const uint64_t valid_m = ballot64(valid);
     n_reached += (uint32_t)__popcll(valid_m & M.reached);
     const uint64_t selected = valid_m & M.ok;
     n_shell += (uint32_t)__popcll(selected);
+    // A shell above DevParams::mirror_miss_radius (+infinity when the host proved nothing: the block is skipped), the ray at
+    // z = l_mirror more than kMirrorMissEps (in mm^2) inside the paraboloid's radius r3 there, and a slope below the bound: the first
+    // mirror's quadratic is negative over the whole mirror, pick_root accepts no root, the nickel test is true (sart_api.hip:
+    // mirror_miss_bounds_of), and all phase B makes of the ray is +1 in N_HIT_NICKEL.  Counted here, not handed on.  Direct
+    // compares, masks combined in scalar registers.
+    // (Not compiled into the rotated-telescope instantiations and skipped on a scalar compare for the cone telescope: the host proves
+    // nothing for either.)
+    uint64_t sure = 0ull;
+    const uint64_t cand = (ROT || Hl.telescope_kind == SART_TK_LLNL) ? 0ull : (selected & ballot64(radial > (double)Pb.mirror_miss_radius));
+    if (cand) {   // wave-uniform
+      const double zl = Pb.l_mirror, xe = fma(zl, st.tsx, st.X0), ye = fma(zl, st.tsy, st.Y0);
+      sure = cand & ballot64(fma(xe, xe, fma(ye, ye, kMirrorMissEps)) < r3sq) &
+             ballot64(fma(st.tsx, st.tsx, st.tsy * st.tsy) < (double)Pb.mirror_miss_slope_sq);
+      n_nickel += (uint32_t)__popcll(sure);
+    }
     // Innermost shell, far enough below its first mirror (DevParams::shell0_miss_radius; -1 when the host could not prove it): phase
     // B would find no root inside the mirror and stop at the no-hit test without touching a counter.  Such a ray is counted
     // above and ends here.  Below the bound the selected shell is shell 0 (the bound lies below R1[0]): ONE compare against a
     // broadcast read of the parameter block in LDS, whose lane mask is combined with `selected` in scalar registers (the
     // ballot of a direct compare is the compare itself; a ballot of `a && b` costs a select and a second compare).
 #ifdef SART_DEBUG_KNOBS
-    const uint64_t mask = (A.flags & 0x10000000u) ? 0ull : (selected & ~ballot64(radial < Pb.shell0_miss_radius));   // experiment: nothing reaches phase B
+    const uint64_t mask = (A.flags & 0x10000000u) ? 0ull : (selected & ~ballot64(radial < Pb.shell0_miss_radius) & ~sure);   // experiment: nothing reaches phase B
 #else
-    const uint64_t mask = selected & ~ballot64(radial < Pb.shell0_miss_radius);
+    const uint64_t mask = selected & ~ballot64(radial < Pb.shell0_miss_radius) & ~sure;
 #endif
     const bool alive = __builtin_amdgcn_inverse_ballot_w64(mask);
     const uint32_t cnt = (uint32_t)__popcll(mask);
@@ -4612,6 +4639,65 @@ __global__ __launch_bounds__(kRecBlock) void trace_records_kernel(HotA H, const 
   }
 }
 
+// Diagnostic twin of the mirror-miss shortcut of trace_histogram_kernel (test entry sart_internal_mirror_miss; no hot path reads
+// it): phase A of the record kernel for the launch's rays, then the shortcut's predicate beside phase B's own first-mirror
+// arithmetic.  counts[0]: selected rays whose pick_root finds no root in the first mirror; [1]: those in a shell above the
+// innermost; [2]: rays the predicate flags; [3]: flagged rays for which pick_root accepts a root; [4]: flagged rays whose nickel
+// test is false ([3] and [4] are what the host's proofs exclude).
+__global__ __launch_bounds__(kRecBlock) void mirror_miss_count_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
+                                                                       unsigned long long* __restrict__ counts) {
+  __shared__ TablesLds S;
+  __shared__ DevBlob B;
+  {
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(blob);
+    uint64_t* dst = reinterpret_cast<uint64_t*>(&B);
+    for (int i = threadIdx.x; i < (int)(sizeof(DevBlob) / 8); i += kRecBlock) dst[i] = src[i];
+    __syncthreads();
+  }
+  const DevParams& P = B.P;
+  stage_tables<kRecBlock>(S, P, B.T);
+  const LdsTables L{S.sincos, S.rcdf_hi, B.T.flux_radius_cdf, S.rguide, S.shells, S.lut};
+  uint32_t n[5] = {0, 0, 0, 0, 0};
+  const uint64_t stride = (uint64_t)gridDim.x * kRecBlock;
+  const uint64_t n_round = (A.n_rays + stride - 1) / stride * stride;   // whole waves run every pass (ballots)
+  for (uint64_t i = (uint64_t)blockIdx.x * kRecBlock + threadIdx.x; i < n_round; i += stride) {
+    RayState st;
+    bool sampled, reached;
+    double radial;
+    LaneMasks masks;
+    double r3sq;
+    const uint64_t ray_id = A.ray_id_offset + i;
+    const uint32_t u3_hi = word_of(stream_block(ray_id >> 2, A.seed_lo, A.seed_hi), (uint32_t)ray_id & 3u);
+    const bool alive = phase_a<false, -1, false, false, false>(H, P, L, A.seed_lo, A.seed_hi, ray_id, u3_hi, st, sampled, reached, radial, masks, nullptr, &r3sq) &&
+                       i < A.n_rays;
+    const ShellDev& sh = L.shells[st.shell];
+    const double X0 = st.X0, Y0 = st.Y0, tsx = st.tsx, tsy = st.tsy;
+    const double Q0 = fma(X0, X0, Y0 * Y0), D0 = fma(X0, tsx, Y0 * tsy), A0 = fma(tsx, tsx, tsy * tsy);
+    // phase B's first mirror and nickel test (phase_b), for a ray that missed
+    double z1;
+    uint64_t hit1_m;
+    const bool hit1 = pick_root(A0 - sh.m1_k, D0 + sh.m1_hb, Q0 - sh.m1_cc, 0.0, sh.m1_zhi, z1, hit1_m);
+    const double zcb = st.zcb;
+    const double m1x = fma(zcb, tsx, X0), m1y = fma(zcb, tsy, Y0);
+    const double n1z = normal_z_general(P, sh, 1, m1x, m1y, zcb);
+    double wx = tsx, wy = tsy, wz = 1.0, sin_a1;
+    const double sin2_a1 = reflect(wx, wy, wz, 1.0 + A0, m1x, m1y, n1z, fma(m1x, m1x, fma(m1y, m1y, n1z * n1z)), sin_a1);
+    const double lz = P.l_mirror - zcb, num = sh.nickel_num;
+    const bool nick = sin2_a1 * fma(lz, lz, num * num) > num * num;
+    // the shortcut's predicate (run_phase_a of trace_histogram_kernel)
+    const double zl = P.l_mirror, xe = fma(zl, tsx, X0), ye = fma(zl, tsy, Y0);
+    const bool sure = alive & (radial > (double)P.mirror_miss_radius) & (fma(xe, xe, fma(ye, ye, kMirrorMissEps)) < r3sq) &
+                      (A0 < (double)P.mirror_miss_slope_sq);
+    n[0] += (uint32_t)(alive & !hit1);
+    n[1] += (uint32_t)(alive & !hit1 & (st.shell > 0));
+    n[2] += (uint32_t)sure;
+    n[3] += (uint32_t)(sure & hit1);
+    n[4] += (uint32_t)(sure & !nick);
+  }
+  for (int k = 0; k < 5; ++k)
+    if (n[k]) atomicAdd(&counts[k], (unsigned long long)n[k]);
+}
+
 // ---- passed rays only (include/sart.h: sart_trace_records_passed): the records of one chunk, compacted in ray order ----------
 // What generateResultPlots (raytracer.nim:2252-2283) and the scan sum (:2800) read of the record buffer: the records with
 // `passed` set, and how many records have passedTillWindow / hitNickel set.  Three small kernels behind trace_records_kernel on
@@ -5251,6 +5337,10 @@ void launch_compact_records(const sart_axion_t* rec, uint32_t n, sart_axion_t* o
 void launch_trace_records(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, sart_axion_t* out, int n_blocks,
                           hipStream_t stream, const double* uniforms_dev) {
   hipLaunchKernelGGL(trace_records_kernel, dim3(n_blocks), dim3(kRecBlock), 0, stream, H, blob, A, out, HB, uniforms_dev);
+}
+// counts: [5], zeroed by the caller
+void launch_mirror_miss_count(const HotA& H, const DevBlob* blob, const TraceArgs& A, unsigned long long* counts, int n_blocks, hipStream_t stream) {
+  hipLaunchKernelGGL(mirror_miss_count_kernel, dim3(n_blocks), dim3(kRecBlock), 0, stream, H, blob, A, counts);
 }
 // stage: [popcount(mask & 0x3FFFFFF)][A.n_rays] words, flags: [A.n_rays]
 void launch_stage_columns(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, uint64_t* stage, uint32_t* flags,
