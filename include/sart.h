@@ -327,6 +327,16 @@ int sart_set_solar_tables_device(sart_context* ctx, const double* em_rates_devic
  */
 int sart_get_solar_tables(sart_context* ctx, double* flux_radius_cdf_out, double* diff_flux_cdfs_out,
                           uint16_t* radius_guide_out, uint16_t* energy_guide_out);
+/*
+ * The radial verdict table the next histogram launch of this context uses (csrc/sart_device.h: RadialLds - for tests and
+ * debugging; any pointer may be NULL).  Returns its number of entries n <= 128, 0 if this setup has none (then nothing but
+ * *n_cells_out is written), or a negative SART_ERR_*.  breakpoints_out[n] ascending, the last +infinity; verdicts_out[n]: three
+ * bytes (just below, at, just above the breakpoint), each code << 6 | shell; cells_out[*n_cells_out] (at most 1024): per cell
+ * of the radial look-up table the index of the first breakpoint in that cell or a later one, 255 for a cell whose rays evaluate
+ * the compares.  SART_NO_RADIAL_TABLE=1 in the environment when the context is created: no table.
+ */
+int sart_get_radial_table(sart_context* ctx, double* breakpoints_out, uint32_t* verdicts_out, uint8_t* cells_out,
+                          int32_t* n_cells_out);
 /* Reflectivity grids as read by initReflectivity (:1160-1231): data[coating][angle][energy],
  * uniform grid defined by (min,max) of the axes (newBilinearSpline :1181/:1204/:1226). */
 int sart_set_reflectivity(sart_context* ctx, int32_t n_coatings, int32_t n_angles,
@@ -738,7 +748,7 @@ int sart_finalize_energy_scan_device(sart_context* ctx, const sart_trace_params_
  * sart_reduce_across_devices with n_doubles = sart_shell_block_len(...), as int64 in FIXED64 - then finalize.
  * SART_ERR_INVALID_ARGUMENT, with the context unchanged: a NULL pointer, an invalid image or spectra specification.
  * Cost: trace_histogram's generic variants plus per selected ray one LDS atomic and per ray behind the mirrors up to five (folded
- * once per workgroup), two global atomics per passed ray with spectra; the LDS image tile is 53 x 53 instead of 64 x 64.
+ * once per workgroup), two global atomics per passed ray with spectra; the LDS image tile is 53 x 53 instead of 63 x 63.
  */
 enum { SART_SHELL_N_SELECTED = 0, SART_SHELL_N_HIT_NICKEL = 1, SART_SHELL_N_PASSED_TILL_WINDOW = 2, SART_SHELL_N_PASSED = 3,
        SART_SHELL_SUM_WEIGHTS = 4, SART_SHELL_SUM_WEIGHTS_SQ = 5, SART_SHELL_SUM_WEIGHTS_HI = 6, SART_SHELL_SUM_WEIGHTS_SQ_HI = 7,
@@ -864,7 +874,7 @@ int sart_finalize_channels_device(sart_context* ctx, const sart_trace_params_t* 
  * SART_ERR_INVALID_ARGUMENT, context unchanged: the X-ray test source is active (no solar draw), a NULL pointer, an invalid image
  * or spectra specification.  SART_ERR_NOT_READY without solar tables.
  * Cost: the generic histogram variants plus three global atomics per passed ray into a 94 MB map at 1968 x 1500 (no replicas, no LDS
- * staging: millions of cells); the LDS image tile is 55 x 55 instead of 64 x 64.  Measured on BabyIAXO / XMM with image and spectra:
+ * staging: millions of cells); the LDS image tile is 55 x 55 instead of 63 x 63.  Measured on BabyIAXO / XMM with image and spectra:
  * 108 ms per 1e9 rays against 81 of the generic histogram launch (1.34 x; FIXED64: 111 against 83, 1.33 x) - profiles/r16_origin_rate.txt,
  * DESIGN.md 3.2e.
  */

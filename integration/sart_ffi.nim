@@ -109,6 +109,8 @@ proc sart_set_solar_tables_device*(ctx: ptr SartContext, emRatesDevice: pointer,
                                    nRadii, nEnergies: int32): cint {.importc, header: sartH.}
 proc sart_get_solar_tables*(ctx: ptr SartContext, fluxRadiusCdfOut, diffFluxCdfsOut: ptr cdouble,
                             radiusGuideOut, energyGuideOut: ptr uint16): cint {.importc, header: sartH.}
+proc sart_get_radial_table*(ctx: ptr SartContext, breakpointsOut: ptr cdouble, verdictsOut: ptr uint32, cellsOut: ptr uint8,
+                            nCellsOut: ptr int32): cint {.importc, header: sartH.}
 proc sart_set_reflectivity*(ctx: ptr SartContext, nCoatings, nAngles, nEnergies: int32,
                             angleMinDeg, angleMaxDeg, energyMinKev, energyMaxKev: cdouble, data: ptr cdouble): cint {.importc, header: sartH.}
 proc sart_set_detector_tables*(ctx: ptr SartContext, strongbackX, strongbackY: ptr cdouble, nStrongback: int32,

@@ -318,6 +318,7 @@ SART_SYMBOLS = {
     "sart_set_solar_tables": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _i, _i]),
     "sart_set_solar_tables_device": (C.c_int, [C.c_void_p, C.c_void_p, _dp, _dp, _i, _i]),
     "sart_get_solar_tables": (C.c_int, [C.c_void_p, _dp, _dp, C.c_void_p, C.c_void_p]),
+    "sart_get_radial_table": (C.c_int, [C.c_void_p, _dp, C.c_void_p, C.c_void_p, _P(_i)]),
     "sart_set_reflectivity": (C.c_int, [C.c_void_p, _i, _i, _i, _d, _d, _d, _d, _dp]),
     "sart_set_detector_tables": (C.c_int, [C.c_void_p, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _i]),
     "sart_trace_records": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p]),

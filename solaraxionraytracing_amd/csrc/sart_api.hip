@@ -67,6 +67,8 @@ int histogram_block_of(int variant);
 void launch_trace_records(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, sart_axion_t* out, int n_blocks,
                           hipStream_t stream, const double* uniforms_dev);
 void launch_mirror_miss_count(const HotA& H, const DevBlob* blob, const TraceArgs& A, unsigned long long* counts, int n_blocks, hipStream_t stream);
+void launch_radial_verdicts(const HotA& H, const DevBlob* blob, const double* radii, int n, uint32_t* out_table, uint32_t* out_compares,
+                            hipStream_t stream);
 int records_block();
 int compact_chunk_max();
 void launch_compact_records(const sart_axion_t* rec, uint32_t n, sart_axion_t* out, unsigned long long capacity, uint32_t* block_counts,
@@ -206,6 +208,7 @@ struct sart_context {
     bool force_generic = false;      // SART_FORCE_GENERIC: never use the specialised kernel variant
     int image_replicas = 0;          // SART_IMAGE_REPLICAS: 0 = chosen from the plate scale
     int hist_blocks_per_cu = 0;      // SART_HIST_BLOCKS_PER_CU: 0 = occupancy query
+    bool no_radial_table = false;    // SART_NO_RADIAL_TABLE: stage A1 of the solar-source histogram kernels decides by its compares, never by the radial verdict table
     int image_tile_max = 0;          // SART_IMAGE_TILE_MAX: upper bound of the LDS image tile's width (0 = what LDS holds); results do not depend on it
   } knobs;
   hipStream_t own_stream = nullptr;
@@ -230,7 +233,10 @@ struct sart_context {
   bool blob_dirty = true;
   bool spot_may_have_moved = true;   // geometry, tables or angles changed since the LDS image tile was placed
   std::vector<ShellDev> shells;
+  // [lut_n] cells of the shell selection; from kRadialCellsOffset the cells of the radial verdict table, from kRadialTableOffset
+  // the table (RadialLds; build_radial_table): one device buffer, d_lut
   std::vector<uint8_t> shell_lut;
+  int radial_n = 0;            // entries of the radial verdict table (0: this setup runs the compares)
   int radius_span = 0;
   bool path_const = false;     // no survivor of phase A entered through the bore wall (path_is_constant)
   DevBuf<ShellDev> d_shells;
@@ -492,12 +498,24 @@ int hoist_setup(sart_context* c) {
     for (int j = 1; j < s.n_shells; ++j) min_gap = std::min(min_gap, s.all_r1[j] - s.all_r1[j - 1]);
     const double r_last = s.all_r1[s.n_shells - 1];
     double step = std::min(1.0, 0.5 * min_gap);
+    if (!c->knobs.no_radial_table) {
+      // The radial verdict table (build_radial_table) wants every value the setup compares the radial distance against in a cell
+      // of its own: a step below the smallest distance between two of them (shell radii, the outer edges of their glass, the
+      // inner disc, the XMM ring).  The shell selection itself needs no more than the step above and gives the same shells.
+      std::vector<double> b;
+      for (int j = 0; j < s.n_shells; ++j) { b.push_back(s.all_r1[j]); b.push_back(s.all_r1[j] + s.all_thickness[j]); }
+      if (P.telescope_kind != SART_TK_LLNL) b.push_back(P.inner_radius);
+      if (P.telescope_kind == SART_TK_XMM) { b.push_back(P.ring_lo); b.push_back(P.ring_hi); }
+      std::sort(b.begin(), b.end());
+      for (size_t k = 1; k < b.size(); ++k)
+        if (b[k] - b[k - 1] > 1e-6) step = std::min(step, 0.9 * (b[k] - b[k - 1]));
+    }
     step = std::max(step, r_last / (kShellLutMax - 2));
     if (!(step < min_gap)) return fail(SART_ERR_UNSUPPORTED, "shell radii too dense for the shell look-up table");
     P.r1_last = r_last;
     P.lut_inv_step = 1.0 / step;
     P.lut_n = static_cast<int>(r_last / step) + 2;
-    c->shell_lut.assign(static_cast<size_t>(P.lut_n), 0);
+    c->shell_lut.assign(static_cast<size_t>(kRadialTableOffset) + sizeof(RadialLds), 0);
     for (int k = 0; k < P.lut_n; ++k) {
       // a little below k*step so that rounding of radial * inv_step can never skip a shell
       const double lo = std::max(0.0, (k - 1e-9) * step);
@@ -685,7 +703,7 @@ HotA hot_of(const DevParams& P) {
   h.spoke_cos_thr = (P.spoke_n == 16) ? P.spoke_cos_thr * (1.0 / 32768.0) : P.spoke_cos_thr;
   h.ring_lo = P.ring_lo; h.ring_hi = P.ring_hi;
   h.test_active = P.test_active; h.rotated = P.rotated; h.telescope_kind = P.telescope_kind; h.spoke_n = P.spoke_n;
-  h.n_shells = P.n_shells; h.lut_n = P.lut_n; h.radius_span = P.radius_span; h.inner_blocks = P.inner_blocks;
+  h.n_shells = P.n_shells; h.lut_n = P.lut_n; h.radial_table = 0; h.inner_blocks = P.inner_blocks;   // (radial_table: sync_blob)
   return h;
 }
 
@@ -887,6 +905,107 @@ bool path_is_constant(const DevParams& P, const HotA& h, int n_radii) {
   return reach + 1e-6 < R;
 }
 
+// ---- the radial verdict table (sart_device.h: RadialLds) ----------------------------------------------------------------------
+// Host copy of radial_verdict_compares (sart_kernels.hip), expression by expression.  `both` (may be NULL): the radius is below
+// shell0_miss_radius AND above mirror_miss_radius, which one code cannot say.
+uint32_t radial_verdict_of(const HotA& H, const DevParams& P, const std::vector<ShellDev>& shells, const uint8_t* lut, bool cand_on, double radial,
+                           bool* both = nullptr) {
+  auto cell_of = [&](double r) {   // max(min((int)(r * lut_inv_step), lut_n - 1), 0) with the device's conversion: saturating, NaN -> 0
+    const double x = r * H.lut_inv_step;
+    return !(x >= 0.0) ? 0 : (x >= static_cast<double>(H.lut_n - 1)) ? H.lut_n - 1 : static_cast<int>(x);
+  };
+  bool ok = true;
+  if (H.telescope_kind != SART_TK_LLNL) {
+    const bool inner = (H.telescope_kind == SART_TK_XMM) ? (radial <= H.inner_radius) : (radial < H.inner_radius);
+    const bool ring = (H.telescope_kind == SART_TK_XMM) & (radial < H.ring_hi) & (radial > H.ring_lo);
+    ok = !(inner | ring);
+  }
+  ok = ok & !(radial > H.r1_last);
+  const int nS = H.n_shells;
+  const int j0 = lut[cell_of(radial)];
+  const int jc = std::min(j0, nS - 1), jb = std::max(jc - 1, 0);
+  const double c_r1 = shells[jc].r1, c_ro = shells[jc].r1_outer;
+  const double b_r1 = shells[jb].r1, b_ro = shells[jb].r1_outer;
+  const bool step = (j0 < nS) & !(c_r1 > radial);
+  const int j = j0 + (step ? 1 : 0);
+  ok = ok & (j < nS);
+  const double g_r1 = step ? c_r1 : b_r1, g_ro = step ? c_ro : b_ro;
+  ok = ok & !((j > 0) & (radial > g_r1) & (radial < g_ro));
+  const uint32_t shell = static_cast<uint32_t>(std::min(j, nS - 1));
+  const bool below0 = radial < P.shell0_miss_radius, cand = cand_on & (radial > static_cast<double>(P.mirror_miss_radius));
+  if (both) *both = ok & below0 & cand;
+  const uint32_t code = !ok ? 0u : below0 ? 1u : cand ? 3u : 2u;
+  return code << 6 | shell;
+}
+
+// Fills the tail of c->shell_lut (the verdict table's cells, then the table) for the current parameters; false if this setup gets
+// none and runs the compares.  The breakpoints are every value one of the compares is made against.  The verdicts come from the
+// predicate itself, evaluated just below, at and just above each of them - `<` against `<=` and the measure-zero radii come out as
+// the compares give them - and a breakpoint that changes nothing (mirror_miss_radius inside the glass of its shell) is dropped.
+// Between two neighbours the verdict must be constant: checked on sample points.  Cells with several breakpoints: the look-up
+// table's step is already chosen below the distance of any two breakpoints the setup alone decides (hoist_setup); what still
+// shares a cell - a sure-miss radius beside another breakpoint - marks the cell, and its lanes evaluate the compares.
+bool build_radial_table(sart_context* c) {
+  std::fill(c->shell_lut.begin() + kRadialCellsOffset, c->shell_lut.end(), static_cast<uint8_t>(0));
+  c->radial_n = 0;
+  const DevParams& P = c->params;
+  if (c->knobs.no_radial_table || P.test_active || P.n_shells < 1 || P.n_shells > 64) return false;
+  const HotA H = hot_of(P);
+  const uint8_t* lut = c->shell_lut.data();
+  const bool cand_on = !P.rotated && P.telescope_kind != SART_TK_LLNL;
+  const double inf = std::numeric_limits<double>::infinity();
+  std::vector<double> cand_b;
+  for (int j = 0; j < P.n_shells; ++j) { cand_b.push_back(c->shells[j].r1); cand_b.push_back(c->shells[j].r1_outer); }
+  cand_b.push_back(H.inner_radius); cand_b.push_back(H.ring_lo); cand_b.push_back(H.ring_hi); cand_b.push_back(H.r1_last);
+  cand_b.push_back(static_cast<double>(P.mirror_miss_radius)); cand_b.push_back(P.shell0_miss_radius);
+  std::sort(cand_b.begin(), cand_b.end());
+  bool both = false, any_both = false;
+  auto V = [&](double r) { const uint32_t v = radial_verdict_of(H, P, c->shells, lut, cand_on, r, &both); any_both |= both; return v; };
+  struct Entry { double b; uint32_t lo, at, hi; };
+  std::vector<Entry> e;
+  double prev = -1.0;
+  for (double b : cand_b) {
+    if (!(b > 0.0) || !std::isfinite(b) || b == prev) continue;
+    prev = b;
+    const Entry x = {b, V(std::nextafter(b, -inf)), V(b), V(std::nextafter(b, inf))};
+    if (x.lo == x.at && x.at == x.hi) continue;
+    e.push_back(x);
+  }
+  const uint32_t far = V(std::numeric_limits<double>::max());
+  e.push_back({inf, far, far, far});
+  // constant between neighbours (and from zero to the first one)
+  for (size_t k = 0; k < e.size(); ++k) {
+    const double a = k ? e[k - 1].b : 0.0, b = std::isfinite(e[k].b) ? e[k].b : 4.0 * (a + 1.0);
+    const uint32_t want = e[k].lo;
+    if (k ? (e[k - 1].hi != want) : (V(0.0) != want || V(std::numeric_limits<double>::denorm_min()) != want)) return false;
+    for (int i = 1; i < 16; ++i)
+      if (const double r = a + (b - a) * (i / 16.0); r > a && r < b && V(r) != want) return false;
+  }
+  if (any_both || e.size() > static_cast<size_t>(kRadialMax)) return false;
+  auto cell_of = [&](double r) {
+    const double x = r * H.lut_inv_step;
+    return (x >= static_cast<double>(H.lut_n - 1)) ? H.lut_n - 1 : static_cast<int>(x);
+  };
+  uint8_t* cells = c->shell_lut.data() + kRadialCellsOffset;
+  {
+    size_t k = 0;
+    for (int cell = 0; cell < H.lut_n; ++cell) {
+      while (cell_of(e[k].b) < cell) ++k;   // (ends at the entry of +infinity, which lies in the last cell)
+      const bool several = k + 1 < e.size() && cell_of(e[k].b) == cell && cell_of(e[k + 1].b) == cell;
+      cells[cell] = static_cast<uint8_t>((several || cell == 0) ? kRadialMarked : static_cast<int>(k));
+    }
+  }
+  RadialLds t;
+  std::memset(&t, 0, sizeof t);
+  for (size_t k = 0; k < e.size(); ++k) {
+    t.b[k] = e[k].b;
+    t.w[k] = e[k].lo | e[k].at << 8 | e[k].hi << 16;
+  }
+  std::memcpy(c->shell_lut.data() + kRadialTableOffset, &t, sizeof t);
+  c->radial_n = static_cast<int>(e.size());
+  return true;
+}
+
 DevTables tables_of(sart_context* c);
 
 // (Re)uploads the parameter blob if the host mirror changed.  Ordered after all work already queued on
@@ -902,12 +1021,15 @@ int sync_blob(sart_context* c) {
     c->params.mirror_miss_radius = b.radius;
     c->params.mirror_miss_slope_sq = b.slope_sq;
   }
+  const bool radial_table = build_radial_table(c);   // (reads the two radii above)
+  if (int rc = c->d_lut.upload(c->shell_lut.data(), c->shell_lut.size())) return rc;
   DevBlob b;
   std::memset(&b, 0, sizeof b);
   b.P = c->params;
   b.T = tables_of(c);
   if (int rc = c->d_blob.upload(&b, 1)) return rc;
   c->hot = hot_of(c->params);
+  c->hot.radial_table = radial_table ? 1 : 0;
   c->hotb.diff_flux_cdfs = c->d_ecdf.p;
   c->hotb.cdf_hi32 = c->d_ecdf_hi32.p;
   c->hotb.energy_guide = c->d_eguide.p;
@@ -1164,6 +1286,7 @@ int sart_create(int device_ordinal, sart_context** out) {
     c->knobs.force_generic = flag("SART_FORCE_GENERIC");
     c->knobs.image_replicas = number("SART_IMAGE_REPLICAS");
     c->knobs.hist_blocks_per_cu = number("SART_HIST_BLOCKS_PER_CU");
+    c->knobs.no_radial_table = flag("SART_NO_RADIAL_TABLE");
     c->knobs.image_tile_max = number("SART_IMAGE_TILE_MAX");
   }
   *out = c;
@@ -1544,6 +1667,43 @@ __attribute__((visibility("default"))) int sart_internal_mirror_miss(sart_contex
     SART_HIP(hipMemcpyAsync(counts, d_counts.p, sizeof zero, hipMemcpyDeviceToHost, c->stream));
     SART_HIP(hipStreamSynchronize(c->stream));
   }
+  return 0;
+}
+
+// The radial verdict table of the next launch (include/sart.h).
+int sart_get_radial_table(sart_context* c, double* breakpoints, uint32_t* verdicts, uint8_t* cells, int32_t* n_cells) {
+  if (!c) return fail(SART_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  SART_HIP(hipSetDevice(c->device));
+  if (int rc = refresh_derived(c)) return rc;
+  if (int rc = sync_blob(c)) return rc;
+  if (n_cells) *n_cells = c->params.lut_n;
+  if (c->radial_n > 0) {
+    const uint8_t* t = c->shell_lut.data() + kRadialTableOffset;
+    if (breakpoints) std::memcpy(breakpoints, t + offsetof(RadialLds, b), static_cast<size_t>(c->radial_n) * sizeof(double));
+    if (verdicts) std::memcpy(verdicts, t + offsetof(RadialLds, w), static_cast<size_t>(c->radial_n) * sizeof(uint32_t));
+    if (cells) std::memcpy(cells, c->shell_lut.data() + kRadialCellsOffset, static_cast<size_t>(c->params.lut_n));
+  }
+  return c->radial_n;
+}
+
+// Test entry (not in sart.h): the verdict byte (code << 6 | shell) of n given radial distances by the table and by the compares,
+// both on the device (radial_verdict_kernel).  Returns SART_ERR_UNSUPPORTED if the next launch of this context would use no table.
+__attribute__((visibility("default"))) int sart_internal_radial_verdicts(sart_context* c, const double* radii, int32_t n, uint32_t* by_table,
+                                                                         uint32_t* by_compares) {
+  if (!c || !radii || !by_table || !by_compares || n < 1) return fail(SART_ERR_INVALID_ARGUMENT, "invalid argument");
+  SART_HIP(hipSetDevice(c->device));
+  if (int rc = refresh_derived(c)) return rc;
+  if (int rc = sync_blob(c)) return rc;
+  if (!c->hot.radial_table) return fail(SART_ERR_UNSUPPORTED, "this setup has no radial verdict table");
+  DevBuf<double> d_r;
+  DevBuf<uint32_t> d_out;
+  if (int rc = d_r.upload(radii, static_cast<size_t>(n))) return rc;
+  if (int rc = d_out.resize(2 * static_cast<size_t>(n))) return rc;
+  launch_radial_verdicts(c->hot, c->d_blob.p, d_r.p, n, d_out.p, d_out.p + n, c->stream);
+  SART_HIP(hipGetLastError());
+  SART_HIP(hipMemcpyAsync(by_table, d_out.p, static_cast<size_t>(n) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  SART_HIP(hipMemcpyAsync(by_compares, d_out.p + n, static_cast<size_t>(n) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  SART_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
 
@@ -2055,8 +2215,8 @@ int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_
       a.replicas = reps.p;
       a.replica_mask = static_cast<uint32_t>(R - 1);
       // No stage A0 (its ring space in LDS is free) or the constant-path variant (the path column of ring 1 is free):
-      // accumulate the centre of the spot in a per-workgroup LDS tile (64 x 64: CAST / LLNL 89 % of the hits, BabyIAXO / XMM 39 %;
-      // 45 x 45 behind the tables alone for the variants whose rings are all in use: stage A0 on and the path carried).
+      // accumulate the centre of the spot in a per-workgroup LDS tile (63 x 63: CAST / LLNL 89 % of the hits, BabyIAXO / XMM 39 %;
+      // 43 x 43 behind the tables alone for the variants whose rings are all in use: stage A0 on and the path carried).
       // The tile is centred on the spot's centroid, measured once per setup and image binning by a pilot launch of 2e5 rays
       // into a one-pixel image (only SUM_X / SUM_Y / N_PASSED are read).
       const bool ring_cells_free = c->hot.n_zones == 0 || variant == 5 || variant == 6;

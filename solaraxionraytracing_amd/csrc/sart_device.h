@@ -170,7 +170,10 @@ struct HotA {
   double r1_last, lut_inv_step;
   double spider_z, spoke_cos_thr, inner_radius, ring_lo, ring_hi;
   int32_t test_active, rotated, telescope_kind, spoke_n;
-  int32_t n_shells, lut_n, radius_span, inner_blocks;
+  // radial_table: 1 if the look-up table in LDS holds the cells of the radial verdict table (RadialLds; sart_api.hip:
+  // build_radial_table), 0 if it holds the shell selection's own cells (today's compares).  Wave-uniform switch of the solar-source
+  // histogram kernels.  (In the slot of the informational radius_span, which no kernel read: the argument block keeps its layout.)
+  int32_t n_shells, lut_n, radial_table, inner_blocks;
   // Stage A0 (early rejection on the bore-exit radius alone): the hi word w of the uniform u3 that sets the
   // radius of the point on the bore exit (r = R sqrt(u3), raytracer.nim:418) lies in zone z if
   // zone_lo[z] <= w <= zone_hi[z]; rays in a zone provably die before the mirrors.  Bit z of zone_reached:
@@ -325,16 +328,32 @@ constexpr int kFixedLimbBits = 40;                          // two-limb sums: va
 // LDS image tile of the histogram kernels: 16 waves x 128 doubles of ring space (ring 0, or ring 1's path column) + kTileExtraCells
 // doubles behind the tables: what the radius CDF leaves free in LDS as 32-bit words and the end of the 160 KB (kRingExtraCells, all
 // that the kernels whose rings are WaveRings have there), and 512 bytes per wave that ring 1 of the histogram kernels does not need
-// (HistRings: the energy draw's uniform travels as its 32-bit word): 64 x 64 <= 2048 + 2114 cells
+// (HistRings: the energy draw's uniform travels as its 32-bit word), less the radial verdict table: 63 x 63 <= 2048 + 1922 cells
+// Radial verdict table of the solar-source histogram kernels: everything phase A decides from the radial distance at the entrance
+// plane alone (inner disc, XMM ring, beyond the last shell, shell selection, glass front, the two sure-miss radii) is a piecewise
+// constant function of it.  Entry k: breakpoint b[k] and a word of three verdict bytes - just below b[k], exactly at it, just above
+// it; a byte is code << 6 | shell with code 0 not selected, 1 selected and below shell0_miss_radius, 2 selected, 3 selected and
+// above mirror_miss_radius.  The look-up table's cell of a ray gives the index of the first breakpoint whose own cell is not lower
+// (kRadialMarked: several breakpoints in that cell, or cell 0, where an unordered radial distance lands - such lanes evaluate the
+// compares).  The table takes kRadialTableCells of the cells behind the tables from the image tile.
+constexpr int kRadialMax = 128;
+constexpr int kRadialMarked = 255;
+struct RadialLds {
+  double b[kRadialMax];
+  uint32_t w[kRadialMax];
+};
+constexpr int kRadialTableCells = (int)(sizeof(RadialLds) / 8);
+// the device buffer behind DevTables::shell_lut: the shell selection's cells, the verdict table's cells, the table
+constexpr int kRadialCellsOffset = kShellLutMax, kRadialTableOffset = 2 * kShellLutMax;
 constexpr int kTileRingCells = 2048;
 constexpr int kRingExtraCells = 1090;
-constexpr int kTileExtraCells = 2114;
-static_assert(kTileExtraCells == kRingExtraCells + 16 * 512 / 8, "16 waves x 512 bytes");
+constexpr int kTileExtraCells = 1922;
+static_assert(kTileExtraCells == kRingExtraCells + 16 * 512 / 8 - kRadialTableCells, "16 waves x 512 bytes, less the radial verdict table");
 // Margin of the end-radius compare of the mirror-miss shortcut, mm^2 (DevParams::mirror_miss_radius; the host checks per shell that it
 // is more than 1e4 times what rounding can move either side by)
 constexpr double kMirrorMissEps = 1e-3;
-constexpr int kImageTileMax = 64;
-constexpr int kImageTileExtraMax = 45;   // 45 x 45 <= kTileExtraCells: the tile of the variants whose rings are all in use
+constexpr int kImageTileMax = 63;
+constexpr int kImageTileExtraMax = 43;   // 43 x 43 <= kTileExtraCells: the tile of the variants whose rings are all in use
 
 // The three breakdowns of the histogram trace, per shell, per emission channel and per cell of the solar table, are one pipeline:
 // breakdown_histogram_body (sart_kernels.hip) is the generic histogram kernel with a per-workgroup table in LDS, and

@@ -456,6 +456,10 @@ struct LdsTables {
   const uint16_t* rguide;    // guide table in front of it
   const ShellDev* shells;
   const uint8_t* lut;        // radial look-up table of the shell selection
+  // the radial verdict table (solar-source histogram kernels with HotA::radial_table set: `lut` then holds ITS cells) and the
+  // shell selection's own cells in device memory, for the lanes of a marked cell
+  const RadialLds* radial = nullptr;
+  const DevTables* tabs = nullptr;   // (the LDS copy of the blob's pointers: shell_lut is fetched from it inside the rare block)
 };
 
 // State of a ray between phase A and phase B.
@@ -669,7 +673,9 @@ struct Uniforms {
 __device__ __forceinline__ uint32_t upper32_of_uniform(double u) {
   return (uint32_t)(u * 4294967296.0);   // floor(u 2^32), exact for every u in [0, 1)
 }
-struct LaneMasks { uint64_t ok, reached; };   // phase A's verdicts as wave-wide lane masks (see phase_a_bore)
+// phase A's verdicts as wave-wide lane masks (see phase_a_bore).  keep, cand (phase_a_telescope<.., RTAB = true> only): not below
+// shell0_miss_radius / above mirror_miss_radius, for the lanes of `ok` (other lanes: any value)
+struct LaneMasks { uint64_t ok, reached, keep, cand; };
 
 // Phase A is written in two halves that meet where the magnet's pipes end and the telescope begins (:1868 | :1878): everything
 // in the first half - sampling, bore, cold-bore exit, pipe cuts - is independent of the telescope's angles, everything in the
@@ -851,9 +857,59 @@ __device__ __forceinline__ void phase_a_bore(const HotA& H, const DevParams& P, 
 // `R`: the telescope's rotation; `shell0`-style shortcuts stay with the caller.  Returns true if the ray goes on to the mirrors.
 // `r3sq` (optional): n1_r3sq of the selected shell - the squared radius of its paraboloid at z = l_mirror - for the caller's
 // mirror-miss shortcut.
-template <bool FAST, int ROT>
+//
+// ---- the verdicts that the radial distance alone decides, as one byte: code << 6 | shell (sart_device.h: RadialLds) ----
+// By the compares: phase_a_telescope's own expressions for the inner disc, the XMM ring, the last shell, the shell selection and
+// the glass front, and the two sure-miss radii of trace_histogram_kernel's stage A1 (`cand_on`: the mirror-miss shortcut is
+// compiled in and the telescope is not the cone one).  `lut`: the shell selection's cells in device memory.  This is what the host
+// evaluates around every breakpoint to fill the table (sart_api.hip: radial_verdict_of), and what the lanes of a marked cell run.
+__device__ __forceinline__ uint32_t radial_verdict_compares(const HotA& H, const DevParams& P, const ShellDev* shells, const uint8_t* lut,
+                                                            bool cand_on, double radial) {
+  bool ok = true;
+  if (H.telescope_kind != SART_TK_LLNL) {
+    const bool inner = (H.telescope_kind == SART_TK_XMM) ? (radial <= H.inner_radius) : (radial < H.inner_radius);
+    const bool ring = (H.telescope_kind == SART_TK_XMM) & (radial < H.ring_hi) & (radial > H.ring_lo);
+    ok = !(inner | ring);
+  }
+  ok = ok & !(radial > H.r1_last);
+  const int nS = H.n_shells;
+  const int j0 = (int)as_global(lut)[max(min((int)(radial * H.lut_inv_step), H.lut_n - 1), 0)];
+  const int jc = min(j0, nS - 1), jb = max(jc - 1, 0);
+  const double c_r1 = shells[jc].r1, c_ro = shells[jc].r1_outer;
+  const double b_r1 = shells[jb].r1, b_ro = shells[jb].r1_outer;
+  const bool step = (j0 < nS) & !(c_r1 > radial);
+  const int j = j0 + (step ? 1 : 0);
+  ok = ok & (j < nS);
+  const double g_r1 = step ? c_r1 : b_r1, g_ro = step ? c_ro : b_ro;
+  ok = ok & !((j > 0) & (radial > g_r1) & (radial < g_ro));
+  const uint32_t shell = (uint32_t)min(j, nS - 1);
+  const uint32_t code = !ok ? 0u : (radial < P.shell0_miss_radius) ? 1u : (cand_on & (radial > (double)P.mirror_miss_radius)) ? 3u : 2u;
+  return code << 6 | shell;
+}
+// By the table: the cell's byte, the breakpoint and its three verdicts read together, two compares, an extract.  A breakpoint in a
+// lower cell than the ray's is below the ray's radial distance, one in a higher cell above it (a product by a positive constant and
+// a truncation are monotone): only a breakpoint in the ray's own cell needs the compare, and the host allows one per cell.  (A
+// marked lane reads entry kRadialMarked behind the table - cells of the image tile, still LDS of this workgroup - and drops it.)
+__device__ __forceinline__ uint32_t radial_verdict_table(const HotA& H, const DevParams& P, const LdsTables& L, bool cand_on, double radial) {
+  const uint32_t k = L.lut[max(min((int)(radial * H.lut_inv_step), H.lut_n - 1), 0)];
+  const double b = L.radial->b[k];
+  const uint32_t w = L.radial->w[k];
+  uint32_t sh = (radial >= b) ? 8u : 0u;
+  sh = (radial > b) ? 16u : sh;
+  uint32_t v = (w >> sh) & 0xFFu;
+  if (k == (uint32_t)kRadialMarked) {   // divergent, rare: several breakpoints in one cell; cell 0 (an unordered radial distance lands there)
+    asm volatile("; rare: marked cell of the radial verdict table");
+    v = radial_verdict_compares(H, P, L.shells, L.tabs->shell_lut, cand_on, radial);
+  }
+  return v;
+}
+
+// RTAB (solar-source histogram kernels): with HotA::radial_table set the radial verdicts come from the table; M.keep and M.cand are
+// filled either way, and `r3sq` is not (the caller reads it for the selected shell where it needs it).
+template <bool FAST, int ROT, bool RTAB = false>
 __device__ __forceinline__ bool phase_a_telescope(const HotA& H, const DevParams& P, const TelRot& R, const LdsTables& L, const BoreRay& br,
                                                   RayState& st, double& radial_out, LaneMasks& M, double* r3sq = nullptr) {
+  static_assert(!RTAB || (FAST && ROT >= 0), "the table serves the solar-source specialisations (no hole loop)");
   const bool cfg_rotated = (ROT < 0) ? (H.rotated != 0) : (ROT != 0);
   const bool cfg_holes = FAST ? false : (H.telescope_kind == SART_TK_XMM && H.inner_blocks < 0);
   const double x1 = br.x1, y1 = br.y1, x3 = br.x3, y3 = br.y3, sx = br.sx, sy = br.sy;
@@ -896,6 +952,29 @@ __device__ __forceinline__ bool phase_a_telescope(const HotA& H, const DevParams
   const double Q0 = fma(X0, X0, Y0 * Y0);
   const double inv_radial = frsq(Q0);
   const double radial = Q0 * inv_radial;       // radialDist (:1905)
+
+  if constexpr (RTAB) {
+    if (H.radial_table) {   // wave-uniform
+      // the spider's spokes as below; everything else the opaque structures and the shell selection decide is one verdict byte
+      if (H.telescope_kind != SART_TK_LLNL) {
+        const double c_ent = X0 * inv_radial;
+        const double xs = fma(H.spider_z, tsx, X0), ys = fma(H.spider_z, tsy, Y0);
+        const double c_sp = xs * frsq(fma(xs, xs, ys * ys));
+        double meas_a, meas_b;
+        spoke_measure_pair(H.spoke_n, c_ent, c_sp, meas_a, meas_b);
+        const bool spoke_a = meas_a >= H.spoke_cos_thr, spoke_b = meas_b >= H.spoke_cos_thr;
+        ok = ok & !(spoke_a | spoke_b);
+        okm &= ~(ballot64(spoke_a) | ballot64(spoke_b));
+      }
+      const uint32_t v = radial_verdict_table(H, P, L, ROT == 0 && H.telescope_kind != SART_TK_LLNL, radial);
+      M.ok = okm & ballot64(v > 63u);
+      M.keep = ballot64(v > 127u);
+      M.cand = ballot64(v > 191u);
+      st.shell = (int)(v & 63u);
+      radial_out = radial;
+      return ok & (v > 63u);
+    }
+  }
 
   // ---- opaque structures (:1635-1704) ----
   if (H.telescope_kind != SART_TK_LLNL) {      // LLNL: the graphite block never blocks (:1646)
@@ -991,11 +1070,15 @@ __device__ __forceinline__ bool phase_a_telescope(const HotA& H, const DevParams
     const double c_r3sq = L.shells[jc].n1_r3sq, u_r3sq = L.shells[jc + 1].n1_r3sq;
     *r3sq = step ? u_r3sq : c_r3sq;
   }
+  if constexpr (RTAB) {   // the caller's two compares (no table for this setup)
+    M.keep = ~ballot64(radial < P.shell0_miss_radius);
+    M.cand = (ROT != 0) ? 0ull : ballot64(radial > (double)P.mirror_miss_radius);
+  }
   return ok;
 }
 
 // Both halves back to back (histogram and record kernels).
-template <bool FAST, int ROT, bool ZEXT, bool NOWALL = false, bool WORD = false>
+template <bool FAST, int ROT, bool ZEXT, bool NOWALL = false, bool WORD = false, bool RTAB = false>
 __device__ __forceinline__ bool phase_a_core(const HotA& H, const DevParams& P, const LdsTables& L, const Uniforms& U, RayState& st,
                                              bool& sampled, bool& reached, double& radial_out, LaneMasks& M, const SinCosCoef* held = nullptr,
                                              double* r3sq = nullptr) {
@@ -1003,7 +1086,7 @@ __device__ __forceinline__ bool phase_a_core(const HotA& H, const DevParams& P, 
   static_assert(!NOWALL || ZEXT, "the constant-path form is a specialisation of the vacuum, unrotated one");
   BoreRay br;
   phase_a_bore<FAST, ZEXT, NOWALL, WORD>(H, P, L, U, st, sampled, reached, br, M, held);
-  return phase_a_telescope<FAST, ROT>(H, P, tel_rot_of(P), L, br, st, radial_out, M, r3sq);
+  return phase_a_telescope<FAST, ROT, RTAB>(H, P, tel_rot_of(P), L, br, st, radial_out, M, r3sq);
 }
 
 // Phase A of the ray with global id `ray_id`: its six uniforms from ONE Philox counter block (x, y, z, w) + its word s of the
@@ -1029,12 +1112,12 @@ __device__ __forceinline__ Uniforms uniforms_of(uint32_t seed_lo, uint32_t seed_
   return U;
 }
 // (WORD = false: the record kernel, which keeps the general draws for both sources of its uniforms)
-template <bool FAST, int ROT, bool ZEXT, bool NOWALL = false, bool WORD = true>
+template <bool FAST, int ROT, bool ZEXT, bool NOWALL = false, bool WORD = true, bool RTAB = false>
 __device__ __forceinline__ bool phase_a(const HotA& H, const DevParams& P, const LdsTables& L, uint32_t seed_lo,
                                         uint32_t seed_hi, uint64_t ray_id, uint32_t u3_hi, RayState& st, bool& sampled,
                                         bool& reached, double& radial, LaneMasks& M, const SinCosCoef* held = nullptr,
                                         double* r3sq = nullptr) {
-  return phase_a_core<FAST, ROT, ZEXT, NOWALL, WORD>(H, P, L, uniforms_of(seed_lo, seed_hi, ray_id, u3_hi), st, sampled, reached, radial, M, held, r3sq);
+  return phase_a_core<FAST, ROT, ZEXT, NOWALL, WORD, RTAB>(H, P, L, uniforms_of(seed_lo, seed_hi, ray_id, u3_hi), st, sampled, reached, radial, M, held, r3sq);
 }
 
 // z of pointExitCB in the rotated telescope frame (z0 of :2051) from the ray as phase B knows it: the point of the ray whose z
@@ -1487,15 +1570,16 @@ struct __align__(16) HistRings {
   uint32_t u3hi[kQueue];
 };
 static_assert(sizeof(WaveRings) - sizeof(HistRings) == kQueue * sizeof(uint32_t) && sizeof(HistRings) % 512 == 0 &&
-                  (kTileRingCells / kQueue * (sizeof(WaveRings) - sizeof(HistRings))) / sizeof(double) == kTileExtraCells - kRingExtraCells,
+                  (kTileRingCells / kQueue * (sizeof(WaveRings) - sizeof(HistRings))) / sizeof(double) == kTileExtraCells + kRadialTableCells - kRingExtraCells,
               "what ring 1's packed cell frees is what the histogram kernels' image tile grows by");
 template <int WAVES, typename Rings = WaveRings>
 struct __align__(16) QueueLds {
   Rings w[WAVES];
 };
 
+// `radial_cells`: the look-up table gets the cells of the radial verdict table instead of the shell selection's own
 template <int BLOCK>
-__device__ __forceinline__ void stage_tables(TablesLds& S, const DevParams& P, const DevTables& T) {
+__device__ __forceinline__ void stage_tables(TablesLds& S, const DevParams& P, const DevTables& T, bool radial_cells = false) {
   for (int i = threadIdx.x; i < 2 * kSinCosEntries; i += BLOCK) S.sincos[i] = as_global(T.sincos_tab)[i];
   for (int i = threadIdx.x; i < P.n_radii + 4; i += BLOCK) {   // (cdf_hi32_kernel's definition, sart_tables.hip)
     const double c = (i < P.n_radii) ? as_global(T.flux_radius_cdf)[i] : 1.0;
@@ -1509,7 +1593,8 @@ __device__ __forceinline__ void stage_tables(TablesLds& S, const DevParams& P, c
     const int n = P.n_shells * (int)(sizeof(ShellDev) / 8);
     for (int i = threadIdx.x; i < n; i += BLOCK) dst[i] = src[i];
   }
-  for (int i = threadIdx.x; i < P.lut_n; i += BLOCK) S.lut[i] = as_global(T.shell_lut)[i];
+  const uint8_t* lut = T.shell_lut + (radial_cells ? kRadialCellsOffset : 0);
+  for (int i = threadIdx.x; i < P.lut_n; i += BLOCK) S.lut[i] = as_global(lut)[i];
   __syncthreads();
 }
 
@@ -1607,11 +1692,14 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
   // (the rings are addressed from a per-wave scalar base anyway).
   struct LdsLayout {
     TablesLds S;
+    RadialLds R;                          // (in front of the tile: a marked lane's read behind it stays inside this object)
     double tile_extra[kTileExtraCells];   // cells kTileRingCells .. of the image tile
     DevBlob B;
     TraceArgs Ab;
     QueueLds<BLOCK / 64, HistRings> Q;
   };
+  static_assert(sizeof(RadialLds) % 8 == 0 && (kRadialMarked + 1) * sizeof(double) <= sizeof(RadialLds) + kTileExtraCells * sizeof(double),
+                "entry kRadialMarked of either column lies in the table or in the tile's cells");
   __shared__ LdsLayout lds;
   TablesLds& S = lds.S;
   QueueLds<BLOCK / 64, HistRings>& Q = lds.Q;
@@ -1653,8 +1741,15 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
     for (int i = threadIdx.x; i < kTileExtraCells; i += BLOCK) lds.tile_extra[i] = 0.0;
     if (SCAN && threadIdx.x < kScanMaxMasses) scan_zero[threadIdx.x] = 0u;   // (the barrier of stage_tables orders both before their first use)
   }
-  stage_tables<BLOCK>(S, Pb, Tb);
-  const LdsTables L{S.sincos, S.rcdf_hi, Tb.flux_radius_cdf, S.rguide, S.shells, S.lut};
+  // The radial verdict table of the solar-source specialisations (HotA::radial_table: the host could build it for this setup).
+  constexpr bool RTAB = FAST;
+  if (RTAB && H.radial_table) {
+    const auto src = as_global(reinterpret_cast<const uint64_t*>(Tb.shell_lut + kRadialTableOffset));
+    uint64_t* dst = reinterpret_cast<uint64_t*>(&lds.R);
+    for (int i = threadIdx.x; i < kRadialTableCells; i += BLOCK) dst[i] = src[i];
+  }
+  stage_tables<BLOCK>(S, Pb, Tb, RTAB && H.radial_table);
+  const LdsTables L{S.sincos, S.rcdf_hi, Tb.flux_radius_cdf, S.rguide, S.shells, S.lut, &lds.R, &Tb};
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform: scalar addressing of the rings
@@ -1715,8 +1810,8 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
     constexpr bool ZEXT = FAST && !ROT && GAS >= 0;
     LaneMasks M;
     double r3sq = 0.0;
-    (void)phase_a<FAST, ROT ? 1 : 0, ZEXT, PATHC>(Hl, Pb, L, A.seed_lo, A.seed_hi, id_base + (uint64_t)rel, u3_hi, st, sampled, reached, radial, M,
-                                                  HOLD_SINCOS ? &Ksc : nullptr, ROT ? nullptr : &r3sq);
+    (void)phase_a<FAST, ROT ? 1 : 0, ZEXT, PATHC, true, RTAB>(Hl, Pb, L, A.seed_lo, A.seed_hi, id_base + (uint64_t)rel, u3_hi, st, sampled, reached, radial,
+                                                              M, HOLD_SINCOS ? &Ksc : nullptr, ROT ? nullptr : &r3sq);
     const uint64_t valid_m = ballot64(valid);
     n_reached += (uint32_t)__popcll(valid_m & M.reached);
     const uint64_t selected = valid_m & M.ok;
@@ -1729,8 +1824,12 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
     // (Not compiled into the rotated-telescope instantiations and skipped on a scalar compare for the cone telescope: the host proves
     // nothing for either.)
     uint64_t sure = 0ull;
-    const uint64_t cand = (ROT || Hl.telescope_kind == SART_TK_LLNL) ? 0ull : (selected & ballot64(radial > (double)Pb.mirror_miss_radius));
+    // (RTAB: phase A hands both radial compares on as lane masks - from the verdict table where the setup has one, in which case
+    // n1_r3sq of the selected shell is read here, where it is needed.)
+    const uint64_t cand = (ROT || Hl.telescope_kind == SART_TK_LLNL) ? 0ull
+                                                                     : (selected & (RTAB ? M.cand : ballot64(radial > (double)Pb.mirror_miss_radius)));
     if (cand) {   // wave-uniform
+      if (RTAB && Hl.radial_table) r3sq = L.shells[st.shell].n1_r3sq;
       const double zl = Pb.l_mirror, xe = fma(zl, st.tsx, st.X0), ye = fma(zl, st.tsy, st.Y0);
       sure = cand & ballot64(fma(xe, xe, fma(ye, ye, kMirrorMissEps)) < r3sq) &
              ballot64(fma(st.tsx, st.tsx, st.tsy * st.tsy) < (double)Pb.mirror_miss_slope_sq);
@@ -1742,9 +1841,9 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
     // broadcast read of the parameter block in LDS, whose lane mask is combined with `selected` in scalar registers (the
     // ballot of a direct compare is the compare itself; a ballot of `a && b` costs a select and a second compare).
 #ifdef SART_DEBUG_KNOBS
-    const uint64_t mask = (A.flags & 0x10000000u) ? 0ull : (selected & ~ballot64(radial < Pb.shell0_miss_radius) & ~sure);   // experiment: nothing reaches phase B
+    const uint64_t mask = (A.flags & 0x10000000u) ? 0ull : (selected & (RTAB ? M.keep : ~ballot64(radial < Pb.shell0_miss_radius)) & ~sure);   // experiment: nothing reaches phase B
 #else
-    const uint64_t mask = selected & ~ballot64(radial < Pb.shell0_miss_radius) & ~sure;
+    const uint64_t mask = selected & (RTAB ? M.keep : ~ballot64(radial < Pb.shell0_miss_radius)) & ~sure;
 #endif
     const bool alive = __builtin_amdgcn_inverse_ballot_w64(mask);
     const uint32_t cnt = (uint32_t)__popcll(mask);
@@ -4639,6 +4738,42 @@ __global__ __launch_bounds__(kRecBlock) void trace_records_kernel(HotA H, const 
   }
 }
 
+// Test twin of the radial verdict table (test entry sart_internal_radial_verdicts; no hot path reads it): the verdict byte of GIVEN
+// radial distances by the table (radial_verdict_table, as stage A1 of the solar-source histogram kernels looks it up) and by the
+// compares (radial_verdict_compares).  A ray's own radial distance cannot be placed to the last bit from its uniforms; here it can.
+__global__ __launch_bounds__(256) void radial_verdict_kernel(HotA H, const DevBlob* __restrict__ blob, const double* __restrict__ radii, int n,
+                                                             uint32_t* __restrict__ out_table, uint32_t* __restrict__ out_compares) {
+  struct Lds {
+    TablesLds S;
+    RadialLds R;
+    double behind[kRadialMarked + 1 - kRadialMax];   // (what a marked lane reads behind the table)
+    DevBlob B;
+  };
+  __shared__ Lds lds;
+  {
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(blob);
+    uint64_t* dst = reinterpret_cast<uint64_t*>(&lds.B);
+    for (int i = threadIdx.x; i < (int)(sizeof(DevBlob) / 8); i += 256) dst[i] = src[i];
+    for (int i = threadIdx.x; i < kRadialMarked + 1 - kRadialMax; i += 256) lds.behind[i] = 0.0;
+    __syncthreads();
+  }
+  const DevParams& P = lds.B.P;
+  {
+    const auto src = as_global(reinterpret_cast<const uint64_t*>(lds.B.T.shell_lut + kRadialTableOffset));
+    uint64_t* dst = reinterpret_cast<uint64_t*>(&lds.R);
+    for (int i = threadIdx.x; i < kRadialTableCells; i += 256) dst[i] = src[i];
+  }
+  stage_tables<256>(lds.S, P, lds.B.T, true);
+  const LdsTables L{lds.S.sincos, lds.S.rcdf_hi, lds.B.T.flux_radius_cdf, lds.S.rguide, lds.S.shells, lds.S.lut, &lds.R, &lds.B.T};
+  const bool cand_on = H.telescope_kind != SART_TK_LLNL;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    const double radial = radii[i];
+    out_table[i] = radial_verdict_table(H, P, L, cand_on, radial);
+    out_compares[i] = radial_verdict_compares(H, P, L.shells, lds.B.T.shell_lut, cand_on, radial);
+  }
+}
+
 // Diagnostic twin of the mirror-miss shortcut of trace_histogram_kernel (test entry sart_internal_mirror_miss; no hot path reads
 // it): phase A of the record kernel for the launch's rays, then the shortcut's predicate beside phase B's own first-mirror
 // arithmetic.  counts[0]: selected rays whose pick_root finds no root in the first mirror; [1]: those in a shell above the
@@ -5341,6 +5476,12 @@ void launch_trace_records(const HotA& H, const HotB& HB, const DevBlob* blob, co
 // counts: [5], zeroed by the caller
 void launch_mirror_miss_count(const HotA& H, const DevBlob* blob, const TraceArgs& A, unsigned long long* counts, int n_blocks, hipStream_t stream) {
   hipLaunchKernelGGL(mirror_miss_count_kernel, dim3(n_blocks), dim3(kRecBlock), 0, stream, H, blob, A, counts);
+}
+// out_table[n], out_compares[n]: the verdict byte of radii[i] by either form (cand_on as trace_histogram_kernel's unrotated
+// instantiations have it).  H.radial_table must be set.
+void launch_radial_verdicts(const HotA& H, const DevBlob* blob, const double* radii, int n, uint32_t* out_table, uint32_t* out_compares,
+                            hipStream_t stream) {
+  hipLaunchKernelGGL(radial_verdict_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, H, blob, radii, n, out_table, out_compares);
 }
 // stage: [popcount(mask & 0x3FFFFFF)][A.n_rays] words, flags: [A.n_rays]
 void launch_stage_columns(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, uint64_t* stage, uint32_t* flags,

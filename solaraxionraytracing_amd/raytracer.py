@@ -315,6 +315,17 @@ class RayTracer:
                                                   eg.ctypes.data_as(C.c_void_p) if guides else None))
         return (rcdf, ecdf, rg, eg) if guides else (rcdf, ecdf)
 
+    def radial_table(self):
+        """The radial verdict table of the next histogram launch: (breakpoints [n] f64, verdict words [n] u32, cells [lut_n] u8),
+        or None if this setup runs the compares (include/sart.h: sart_get_radial_table)."""
+        b, w, cells = np.empty(128), np.empty(128, dtype=np.uint32), np.empty(1024, dtype=np.uint8)
+        n_cells = C.c_int32(0)
+        n = self.lib.sart_get_radial_table(self.handle, _lib.as_dp(b), w.ctypes.data_as(C.c_void_p), cells.ctypes.data_as(C.c_void_p),
+                                           C.byref(n_cells))
+        if n < 0:
+            _lib.check(n)
+        return (b[:n].copy(), w[:n].copy(), cells[:n_cells.value].copy()) if n > 0 else None
+
     def _n_radii(self) -> int:
         if getattr(self, "_n_radii_set", None):
             return self._n_radii_set
