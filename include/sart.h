@@ -895,6 +895,68 @@ int sart_trace_histogram_origin(sart_context* ctx, const sart_trace_params_t* pa
 int sart_finalize_origin_device(sart_context* ctx, const sart_trace_params_t* params, const void* origin_fixed_device,
                                 double* out_f64_device);
 
+/* ---- aperture map of the histogram trace ----------------------------------------- */
+/*
+ * Every ray that reaches the telescope crosses its entrance plane at pointEntranceXRT, which the reference keeps per ray as
+ * pointdataXBefore / pointdataYBefore (raytracer.nim:2091-2094) and puts on a pixel grid in getPixelValue (:618-623).  These entry
+ * points are sart_trace_histogram_device plus the detected weight per cell of a grid over that plane (telescope frame, mm, the frame
+ * of the record's pointdataXBefore / pointdataYBefore): which part of the entrance aperture feeds the detector, and with how much
+ * flux - the vignetting picture of the optic (shell annuli, spider spokes, the bore's shadow on a tilted telescope, the LLNL sector),
+ * Monte-Carlo errors per cell, and - by a product on the host - the exact flux for anything that multiplies a ray's weight by a
+ * function of its entrance point (an aperture stop, a support structure, a masked sector; to first order a transverse field profile).
+ *
+ * The grid is context state, as the source channels are: sart_set_aperture_grid.  nx x ny cells over [x_min, x_max) x [y_min, y_max),
+ * binned as the image is: cell (ix, iy) = ((int)((x - x_min) nx / (x_max - x_min)), (int)((y - y_min) ny / (y_max - y_min))), inside
+ * where 0 <= both < n (a NaN falls outside).  SART_ERR_INVALID_ARGUMENT, context unchanged: nx or ny outside [1, 4096], nx ny > 2^22, a
+ * non-finite or empty range, a NULL pointer.  sart_get_aperture_grid: SART_ERR_NOT_READY if none was ever set.
+ *
+ *   accumulator_device  exactly what sart_trace_histogram_device accumulates for the same params (image, scalars, spectra, flux-only
+ *                       launches): the contract of the per-shell, per-channel and origin entries - bit for bit in SART_ACCUM_FIXED64
+ *                       against the generic kernel variants, up to the summation order in f64
+ *   aperture_device     a flat array of sart_aperture_block_len(nx, ny) 8-byte slots (f64, or raw int64 in FIXED64; ranks reduce it
+ *                       as it is - sart_reduce_across_devices, as int64 in FIXED64 - then finalize):
+ *                         1. the head, SART_APERTURE_HEAD slots: SART_APERTURE_N_PASSED, _SUM_WEIGHTS, _SUM_WEIGHTS_SQ (= SART_ACC_N_PASSED,
+ *                            _SUM_WEIGHTS, _SUM_WEIGHTS_SQ) and in raw FIXED64 the high limbs SART_APERTURE_SUM_WEIGHTS_HI / _SQ_HI:
+ *                            value = (hi 2^40 + lo) quantum, 0 <= lo < 2^40 after a launch; the other slots are reserved (0): the
+ *                            origin head's positions
+ *                         2. cells[ny][nx][SART_APERTURE_CELL], row-major as the image is: SART_APERTURE_N (passed rays that entered
+ *                            through the cell), SART_APERTURE_SUM_WEIGHTS (sum of w; FIXED64: of rint(w / quantum)),
+ *                            SART_APERTURE_SUM_WEIGHTS_SQ (sum of w^2; FIXED64: of the integer the ray adds to SART_ACC_SUM_WEIGHTS_SQ);
+ *                            slot 3 is reserved (0).  One aligned 32-byte cell per (iy, ix)
+ *                         3. one more cell, index nx ny: the passed rays that entered outside the window
+ * In FIXED64 and exactly as integers: sum of all cells, the outside cell included, = head = the accumulator's N_PASSED, SUM_WEIGHTS
+ * and SUM_WEIGHTS_SQ (every passed ray adds the same integers everywhere).
+ * Quanta: the accumulator's, frozen in the same way; params->accumulate applies to both buffers.
+ * SART_ERR_INVALID_ARGUMENT, context unchanged: a NULL pointer, an invalid image or spectra specification.  SART_ERR_NOT_READY
+ * without a setup or without a grid.  Every source is accepted, the X-ray test source included: the entrance point exists for all.
+ * Cost: the generic histogram variants plus three global atomics per passed ray into a map of 2 MB at 256 x 256 (no replicas, no LDS
+ * staging); the LDS image tile is 55 x 55 instead of 63 x 63, as for the origin map.  Measured on BabyIAXO / XMM with image and
+ * spectra: 112 ms per 1e9 rays at 256 x 256 against 79 of the generic histogram launch (1.41 x; FIXED64: 113 against 81, 1.39 x) and
+ * 109 at 1024 x 1024 (1.37 x; FIXED64: 109, 1.35 x), where the origin map stands at 109 / 111 (1.37 x).  The fewer the cells, the more
+ * of a launch's atomics meet in one cell at the memory side: 125 at 64 x 64, 232 at 16 x 16, 2741 at 2 x 2 - a coarse picture is better
+ * summed on the host from a fine one (profiles/r19_aperture_rate.txt).
+ */
+enum { SART_APERTURE_N = 0, SART_APERTURE_SUM_WEIGHTS = 1, SART_APERTURE_SUM_WEIGHTS_SQ = 2, SART_APERTURE_CELL = 4,
+       SART_APERTURE_N_PASSED = 0, SART_APERTURE_SUM_WEIGHTS_HI = 4, SART_APERTURE_SUM_WEIGHTS_SQ_HI = 5, SART_APERTURE_HEAD = 8 };
+typedef struct sart_aperture_grid_t {
+  int32_t nx, ny;
+  double x_min, x_max, y_min, y_max; /* mm, telescope frame at the entrance plane */
+} sart_aperture_grid_t;
+int sart_set_aperture_grid(sart_context* ctx, const sart_aperture_grid_t* grid);
+int sart_get_aperture_grid(sart_context* ctx, sart_aperture_grid_t* out);
+/* 8-byte slots of an aperture block: SART_APERTURE_HEAD + (nx ny + 1) SART_APERTURE_CELL (a negative side counts as 0). */
+size_t sart_aperture_block_len(int32_t nx, int32_t ny);
+/* DEVICE memory; asynchronous on the context's stream. */
+int sart_trace_histogram_aperture_device(sart_context* ctx, const sart_trace_params_t* params, double* accumulator_device,
+                                         double* aperture_device);
+/* Blocking form with HOST outputs (each may be NULL), finalized in FIXED64 mode.  Starts from zero: params->accumulate is not read. */
+int sart_trace_histogram_aperture(sart_context* ctx, const sart_trace_params_t* params, double* image_out_host, sart_summary_t* summary_out,
+                                  double* spectra_out_host, double* aperture_out_host);
+/* Raw FIXED64 block -> doubles with the context's frozen quanta (device pointers; in place allowed); asynchronous.  The checks and the
+ * NaN rule of sart_finalize_origin_device, over the nx ny + 1 cells of the context's grid. */
+int sart_finalize_aperture_device(sart_context* ctx, const sart_trace_params_t* params, const void* aperture_fixed_device,
+                                  double* out_f64_device);
+
 /* ---- multi-GPU ---------------------------------------------------------- */
 /*
  * Sum the fused accumulators of n contexts (one per GPU of this process) into the one of contexts[root]:

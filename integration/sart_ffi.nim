@@ -214,6 +214,23 @@ proc sart_trace_histogram_origin*(ctx: ptr SartContext, p: ptr SartTraceParams, 
                                   spectraOutHost: ptr cdouble, originOutHost: ptr cdouble): cint {.importc, header: sartH.}
 proc sart_finalize_origin_device*(ctx: ptr SartContext, p: ptr SartTraceParams, originFixedDevice: pointer,
                                   outF64Device: ptr cdouble): cint {.importc, header: sartH.}
+## aperture map of the histogram trace: the detected weight per cell of a grid over the telescope's entrance plane (pointEntranceXRT,
+## the record's pointdataXBefore / pointdataYBefore).  The block: a head of 8 slots as the origin block's, then cells [ny][nx][4]
+## (N, sum w, sum w^2, reserved), then one more cell for the passed rays that entered outside the window
+const SartApertureHead* = 8
+const SartApertureCell* = 4
+type SartApertureGrid* {.importc: "sart_aperture_grid_t", header: sartH, bycopy.} = object
+  nx*, ny*: int32
+  x_min*, x_max*, y_min*, y_max*: cdouble
+proc sart_set_aperture_grid*(ctx: ptr SartContext, grid: ptr SartApertureGrid): cint {.importc, header: sartH.}
+proc sart_get_aperture_grid*(ctx: ptr SartContext, gridOut: ptr SartApertureGrid): cint {.importc, header: sartH.}
+proc sart_aperture_block_len*(nx, ny: int32): csize_t {.importc, header: sartH.}
+proc sart_trace_histogram_aperture_device*(ctx: ptr SartContext, p: ptr SartTraceParams, accumulatorDevice: ptr cdouble,
+                                           apertureDevice: ptr cdouble): cint {.importc, header: sartH.}
+proc sart_trace_histogram_aperture*(ctx: ptr SartContext, p: ptr SartTraceParams, imageOutHost: ptr cdouble, summaryOut: ptr SartSummary,
+                                    spectraOutHost: ptr cdouble, apertureOutHost: ptr cdouble): cint {.importc, header: sartH.}
+proc sart_finalize_aperture_device*(ctx: ptr SartContext, p: ptr SartTraceParams, apertureFixedDevice: pointer,
+                                    outF64Device: ptr cdouble): cint {.importc, header: sartH.}
 proc sart_reduce_across_devices*(contexts: ptr ptr SartContext, accumulatorsDevice: ptr ptr cdouble, n: int32, nDoubles: csize_t,
                                  root: int32): cint {.importc, header: sartH.}
 proc sart_enable_kernel_timing*(ctx: ptr SartContext, enable: cint): cint {.importc, header: sartH.}

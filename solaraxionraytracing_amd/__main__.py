@@ -10,6 +10,7 @@
         [--emissionChannels {terms,couplings}]                           (not in the reference: see below)
         [--events PATH.npz [--eventColumns a,b,c]]                       (not in the reference: see below)
         [--originMap]                                                    (not in the reference: see below)
+        [--apertureMap [--apertureBins N] [--apertureWindow x0,x1,y0,y1]]  (not in the reference: see below)
 
 Same switches, same two modes (full run = calculateFluxFractions, :2755-2776; angular scan, :2778-2815).  What differs:
 `--rays` replaces the compile-time constant NumberOfPointsSun (:251, default 1e6), plots are never made (the numbers
@@ -38,7 +39,13 @@ n_rays, n_passed, n_passed_till_window, n_hit_nickel.  The rays are those of the
 detected weight per cell (solar radius, energy) of the emission table the passed rays were drawn in, from the one trace, and writes
 `origin_map_{year}.npz` (counts, weights, weights_sq [n_radii][n_energies], radii, energies, n_rays and the traced rates) and
 `flux_by_solar_radius_{year}.csv`.  `python -m solaraxionraytracing_amd.reweight origin_map_{year}.npz --solarModel FILE.csv` then
-gives the flux for another solar model on the same grid without a new trace (origin.py)."""
+gives the flux for another solar model on the same grid without a new trace (origin.py).
+--apertureMap (full-run mode only; allowed with --xrayTest; not beside --shellBreakdown, --emissionChannels or --originMap: one
+breakdown per run) also keeps the detected weight per cell of a grid over the telescope's entrance plane (pointEntranceXRT, the
+record's pointdataXBefore / pointdataYBefore, :2091-2094), from the one trace: --apertureBins N (default 256) cells a side over
+--apertureWindow x0,x1,y0,y1 in mm (default: the square of +-1.02 x the largest R1 of the setup's shells about the optical axis).
+Writes `aperture_map_{year}.npz` (counts, weights, weights_sq [ny][nx], outside, x_edges, y_edges, n_rays, head) and
+`aperture_image_{year}.csv` (x, y, N, flux, sigma) and prints the share of the flux that entered outside the window (aperture.py)."""
 from __future__ import annotations
 
 import argparse
@@ -47,7 +54,7 @@ import sys
 
 import numpy as np
 
-from . import _lib, config as cfgmod, origin
+from . import _lib, aperture, config as cfgmod, origin
 from .raytracer import (RayTracer, angle_image_names, containment_radii, initFullSetup, performAngularScan, performAxionMassScan,
                         performEnergyScan, write_channel_csvs, write_image_csv, write_shell_csvs)
 
@@ -89,6 +96,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="extension (full-run mode): the detected flux per (solar radius, energy) cell of the emission table, "
                          "origin_map_{year}.npz and flux_by_solar_radius_{year}.csv; reweightable to another solar model "
                          "(python -m solaraxionraytracing_amd.reweight)")
+    ap.add_argument("--apertureMap", action="store_true",
+                    help="extension (full-run mode): the detected flux per cell of a grid over the telescope's entrance plane, "
+                         "aperture_map_{year}.npz and aperture_image_{year}.csv")
+    ap.add_argument("--apertureBins", type=int, default=256, metavar="N", help="cells a side of --apertureMap (default: %(default)s)")
+    ap.add_argument("--apertureWindow", default="", metavar="x0,x1,y0,y1",
+                    help="window of --apertureMap in mm (default: +-1.02 x the largest R1 of the setup's shells)")
     ap.add_argument("--events", default="", metavar="PATH.npz",
                     help="extension (full-run mode): the passed rays as columns, in ray order, and the four counts, as a numpy .npz")
     ap.add_argument("--eventColumns", default=",".join(EVENT_COLUMNS), help="comma-separated columns of --events (default: %(default)s)")
@@ -132,6 +145,20 @@ def check_scan_args(ap: argparse.ArgumentParser, args) -> None:
             ap.error("--originMap needs the solar source: it cannot be combined with --xrayTest")
         if getattr(args, "shellBreakdown", False) or getattr(args, "emissionChannels", None):
             ap.error("--originMap cannot be combined with --shellBreakdown or --emissionChannels (one breakdown per run)")
+    if getattr(args, "apertureMap", False):
+        if energy_scan_requested(args) or args.massScanMax > args.massScanMin or args.angularScanMin != args.angularScanMax:
+            ap.error("--apertureMap belongs to the full run: it cannot be combined with a mass, angular or energy scan")
+        if getattr(args, "shellBreakdown", False) or getattr(args, "emissionChannels", None) or getattr(args, "originMap", False):
+            ap.error("--apertureMap cannot be combined with --shellBreakdown, --emissionChannels or --originMap (one breakdown per run)")
+        if not 1 <= args.apertureBins <= min(_lib.APERTURE_MAX_SIDE, int(_lib.APERTURE_MAX_CELLS ** 0.5)):
+            ap.error("--apertureMap: --apertureBins must lie in [1, %d]" % min(_lib.APERTURE_MAX_SIDE, int(_lib.APERTURE_MAX_CELLS ** 0.5)))
+        if args.apertureWindow:
+            try:
+                x0, x1, y0, y1 = aperture_window(args)
+            except ValueError:
+                ap.error("--apertureMap: --apertureWindow takes four numbers x0,x1,y0,y1")
+            if not (np.all(np.isfinite([x0, x1, y0, y1])) and x1 > x0 and y1 > y0):
+                ap.error("--apertureMap: --apertureWindow needs finite x0 < x1 and y0 < y1")
     if not energy_scan_requested(args):
         return
     if args.massScanMax > args.massScanMin or args.angularScanMin != args.angularScanMax:
@@ -151,6 +178,15 @@ def check_channels_config(ap: argparse.ArgumentParser, args) -> None:
         csv = cfgmod.solar_model_csv_of(path)
         if csv:
             ap.error("--emissionChannels cannot be combined with a solar-model CSV (%s): its components are not known" % csv)
+
+
+def aperture_window(args, full=None):
+    """(x0, x1, y0, y1) of --apertureWindow; without it the square of +-1.02 x the largest R1 of ``full``'s shells."""
+    if args.apertureWindow:
+        x0, x1, y0, y1 = (float(v) for v in args.apertureWindow.split(","))
+        return x0, x1, y0, y1
+    half = 1.02 * max(full.setup.all_r1[:full.setup.n_shells])
+    return -half, half, -half, half
 
 
 def event_columns(args) -> list:
@@ -241,6 +277,9 @@ def main(argv=None) -> int:
                 img, s, spec, chans = rt.trace_channels(n, seed=args.seed, flags=flags)
             elif args.originMap:
                 img, s, spec, omap = rt.trace_origin(n, seed=args.seed, flags=flags)
+            elif args.apertureMap:
+                rt.set_aperture_grid(args.apertureBins, args.apertureBins, *aperture_window(args, full))
+                img, s, spec, amap = rt.trace_aperture(n, seed=args.seed, flags=flags)
             else:
                 img, s, spec = rt.trace_spectra(n, seed=args.seed, flags=flags)
             write_result(os.path.join(args.outpath, "axion_image_%s.csv" % year), img, s, spec, full.setup.chip_x_max)
@@ -257,6 +296,13 @@ def main(argv=None) -> int:
                                     energies=full.energies, n_rays=np.float64(s["N_RAYS"]), rates=full.em_rates)
                 print("wrote", path)
                 print("wrote", origin.write_radial_csv(os.path.join(args.outpath, "flux_by_solar_radius_%s.csv" % year), omap, full.radii))
+            if args.apertureMap:
+                print("wrote", aperture.save_map(os.path.join(args.outpath, "aperture_map_%s.npz" % year), amap, s["N_RAYS"]))
+                print("wrote", aperture.write_csv(os.path.join(args.outpath, "aperture_image_%s.csv" % year), amap))
+                print("--apertureMap: %d x %d cells over x [%.6g, %.6g] y [%.6g, %.6g] mm; outside the window: %d passed axions, share of "
+                      "the flux %.6g" % (args.apertureBins, args.apertureBins, amap["x_edges"][0], amap["x_edges"][-1], amap["y_edges"][0],
+                                         amap["y_edges"][-1], int(amap["outside"]["N"]),
+                                         aperture.reweight(amap, np.ones_like(amap["weights"]))["uncovered"]))
             if args.events:
                 cols, counts = rt.trace_columns(n, event_columns(args), seed=args.seed, flags=flags)
                 np.savez(args.events, **cols, **counts)

@@ -72,6 +72,14 @@ ORIGIN_CELL = 4
 ORIGIN = dict(N=0, SUM_WEIGHTS=1, SUM_WEIGHTS_SQ=2)
 ORIGIN_HEAD_SLOTS = dict(N_PASSED=0, SUM_WEIGHTS=1, SUM_WEIGHTS_SQ=2)
 ORIGIN_HEAD_HI = dict(SUM_WEIGHTS=4, SUM_WEIGHTS_SQ=5)
+# aperture map (include/sart.h: SART_APERTURE_*): a head of APERTURE_HEAD slots, then cells[ny][nx][APERTURE_CELL], then the outside cell
+APERTURE_HEAD = 8
+APERTURE_CELL = 4
+APERTURE = dict(N=0, SUM_WEIGHTS=1, SUM_WEIGHTS_SQ=2)
+APERTURE_HEAD_SLOTS = dict(N_PASSED=0, SUM_WEIGHTS=1, SUM_WEIGHTS_SQ=2)
+APERTURE_HEAD_HI = dict(SUM_WEIGHTS=4, SUM_WEIGHTS_SQ=5)
+APERTURE_MAX_SIDE = 4096
+APERTURE_MAX_CELLS = 1 << 22
 
 
 def energy_scan_len(n_energies: int) -> int:
@@ -140,6 +148,25 @@ def split_origin(block, n_radii: int, n_energies: int) -> dict:
     cells = block[ORIGIN_HEAD:].reshape(int(n_radii), int(n_energies), ORIGIN_CELL)
     return dict(head={k: float(block[i]) for k, i in ORIGIN_HEAD_SLOTS.items()}, counts=cells[:, :, ORIGIN["N"]].copy(),
                 weights=cells[:, :, ORIGIN["SUM_WEIGHTS"]].copy(), weights_sq=cells[:, :, ORIGIN["SUM_WEIGHTS_SQ"]].copy())
+
+
+def aperture_block_len(nx: int, ny: int) -> int:
+    """sart_aperture_block_len: 8-byte slots of an aperture block (the head, nx ny cells, the outside cell)."""
+    return APERTURE_HEAD + (max(int(nx), 0) * max(int(ny), 0) + 1) * APERTURE_CELL
+
+
+def split_aperture(block, nx: int, ny: int) -> dict:
+    """``head`` (dict, keys of APERTURE_HEAD_SLOTS), the maps ``counts``, ``weights``, ``weights_sq`` [ny][nx] (row-major as the image)
+    and ``outside`` (dict N, SUM_WEIGHTS, SUM_WEIGHTS_SQ: the passed rays that entered outside the window) from a finalized aperture
+    block."""
+    import numpy as np
+    block = np.asarray(block, dtype=np.float64)
+    assert block.size == aperture_block_len(nx, ny)
+    cells = block[APERTURE_HEAD:].reshape(int(ny) * int(nx) + 1, APERTURE_CELL)
+    grid = cells[:-1].reshape(int(ny), int(nx), APERTURE_CELL)
+    return dict(head={k: float(block[i]) for k, i in APERTURE_HEAD_SLOTS.items()}, counts=grid[:, :, APERTURE["N"]].copy(),
+                weights=grid[:, :, APERTURE["SUM_WEIGHTS"]].copy(), weights_sq=grid[:, :, APERTURE["SUM_WEIGHTS_SQ"]].copy(),
+                outside={k: float(cells[-1, i]) for k, i in APERTURE.items()})
 
 
 def split_energy_scan(acc, n_energies: int):
@@ -256,6 +283,12 @@ class TraceParams(C.Structure):
     ]
 
 
+class ApertureGrid(C.Structure):
+    """sart_aperture_grid_t: nx x ny cells over [x_min, x_max) x [y_min, y_max) of the entrance plane (mm, telescope frame)."""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("x_min", C.c_double), ("x_max", C.c_double), ("y_min", C.c_double),
+                ("y_max", C.c_double)]
+
+
 class Summary(C.Structure):
     _fields_ = [("v", _d * SART_ACC_COUNT)]
 
@@ -366,6 +399,12 @@ SART_SYMBOLS = {
     "sart_trace_histogram_origin_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p, C.c_void_p]),
     "sart_trace_histogram_origin": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _P(Summary), _dp, _dp]),
     "sart_finalize_origin_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p, C.c_void_p]),
+    "sart_set_aperture_grid": (C.c_int, [C.c_void_p, _P(ApertureGrid)]),
+    "sart_get_aperture_grid": (C.c_int, [C.c_void_p, _P(ApertureGrid)]),
+    "sart_aperture_block_len": (C.c_size_t, [_i, _i]),
+    "sart_trace_histogram_aperture_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p, C.c_void_p]),
+    "sart_trace_histogram_aperture": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _P(Summary), _dp, _dp]),
+    "sart_finalize_aperture_device": (C.c_int, [C.c_void_p, _P(TraceParams), C.c_void_p, C.c_void_p]),
     "sart_reduce_across_devices": (C.c_int, [_P(C.c_void_p), _P(C.c_void_p), _i, C.c_size_t, _i]),
     "sart_enable_kernel_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "sart_get_kernel_timing": (C.c_int, [C.c_void_p, _dp, _P(C.c_int64)]),

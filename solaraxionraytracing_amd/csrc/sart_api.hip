@@ -63,6 +63,9 @@ int origin_histogram_blocks_per_cu(bool rotated);
 void launch_origin_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, double* acc, const OriginArgs& OG,
                              int n_blocks, hipStream_t stream, bool rotated, bool fixed);
 void launch_finalize_origin(const void* in, double* out, size_t n_cells, double q_w, double q_w2, void* check_dev, hipStream_t stream);
+int aperture_histogram_blocks_per_cu(bool rotated);
+void launch_aperture_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, double* acc, const ApertureArgs& AP,
+                               int n_blocks, hipStream_t stream, bool rotated, bool fixed);
 int histogram_block_of(int variant);
 void launch_trace_records(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, sart_axion_t* out, int n_blocks,
                           hipStream_t stream, const double* uniforms_dev);
@@ -321,6 +324,12 @@ struct sart_context {
   // solar-origin map (sart_trace_histogram_origin*): per-workgroup head sums, the blocking form's scratch block and its f64 image
   DevBuf<double> d_origin_partials, d_oblock, d_oblock_fin;
   int blocks_per_cu_origin[2] = {0, 0};
+  // aperture map (sart_trace_histogram_aperture*): the grid over the entrance plane (sart_set_aperture_grid), per-workgroup head sums,
+  // the blocking form's scratch block and its f64 image
+  bool have_aperture = false;
+  sart_aperture_grid_t aperture_grid = {};
+  DevBuf<double> d_aperture_partials, d_ablock, d_ablock_fin;
+  int blocks_per_cu_aperture[2] = {0, 0};
 
   // timing
   bool timing = false;
@@ -2123,7 +2132,11 @@ size_t channel_block_len_of(const sart_context* c, const sart_trace_params_t* p)
 
 size_t origin_block_len_of(const sart_context* c, const sart_trace_params_t*) { return sart_origin_block_len(c->n_radii, c->n_energies); }
 
-// What the host path knows of a breakdown of the histogram trace (kShells, kChannels, kOrigin below): its kernel keeps a table in the last
+size_t aperture_block_len_of(const sart_context* c, const sart_trace_params_t*) {
+  return sart_aperture_block_len(c->aperture_grid.nx, c->aperture_grid.ny);
+}
+
+// What the host path knows of a breakdown of the histogram trace (kShells, kChannels, kOrigin, kAperture below): its kernel keeps a table in the last
 // cells of the LDS tile space and stores it once per workgroup, the fold adds those partials into the caller's block.
 struct Breakdown {
   int tile_max, tile_extra_max;                // widest LDS image tile beside the table: ring 0 free (no stage A0) / all rings in use
@@ -2146,8 +2159,8 @@ struct BreakdownBlock {   // which breakdown a launch fills, if any, and the cal
 };
 
 // sart_trace_histogram_device, and with a breakdown `bd` sart_trace_histogram_shells_device / sart_trace_histogram_channels_device /
-// sart_trace_histogram_origin_device: the same host path (quanta, replicas, LDS tile, partials) around trace_histogram_kernel,
-// shell_histogram_kernel, channel_histogram_kernel or origin_histogram_kernel.
+// sart_trace_histogram_origin_device / sart_trace_histogram_aperture_device: the same host path (quanta, replicas, LDS tile, partials)
+// around trace_histogram_kernel, shell_histogram_kernel, channel_histogram_kernel, origin_histogram_kernel or aperture_histogram_kernel.
 int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_dev, BreakdownBlock bd = {}) {
   SART_HIP(hipSetDevice(c->device));
   if (int rc = refresh_derived(c)) return rc;
@@ -2346,6 +2359,14 @@ int origin_check(sart_context* c, const sart_trace_params_t* p) {
   return 0;
 }
 
+// params that an aperture launch and its finalize accept (the context stays as it is otherwise): every setup that a shell launch
+// accepts, the X-ray test source included
+int aperture_check(sart_context* c, const sart_trace_params_t* p) {
+  if (int rc = shells_check(c, p)) return rc;
+  if (!c->have_aperture) return fail(SART_ERR_NOT_READY, "no aperture grid (sart_set_aperture_grid)");
+  return 0;
+}
+
 void launch_shells(sart_context* c, const TraceArgs& a, double* acc_dev, double* block_dev, int n_blocks, bool rotated, bool fixed) {
   ShellArgs sh;
   std::memset(&sh, 0, sizeof sh);
@@ -2379,6 +2400,21 @@ void launch_origin(sart_context* c, const TraceArgs& a, double* acc_dev, double*
   launch_origin_histogram(c->hot, c->hotb, c->d_blob.p, a, acc_dev, og, n_blocks, c->stream, rotated, fixed);
 }
 
+void launch_aperture(sart_context* c, const TraceArgs& a, double* acc_dev, double* block_dev, int n_blocks, bool rotated, bool fixed) {
+  const sart_aperture_grid_t& g = c->aperture_grid;
+  ApertureArgs ap;
+  std::memset(&ap, 0, sizeof ap);
+  ap.block = block_dev;
+  ap.partials = c->d_aperture_partials.p;
+  ap.nx = g.nx;
+  ap.ny = g.ny;
+  ap.x_min = g.x_min;
+  ap.y_min = g.y_min;
+  ap.inv_step_x = static_cast<double>(g.nx) / (g.x_max - g.x_min);   // (as make_args forms image_inv_step_x)
+  ap.inv_step_y = static_cast<double>(g.ny) / (g.y_max - g.y_min);
+  launch_aperture_histogram(c->hot, c->hotb, c->d_blob.p, a, acc_dev, ap, n_blocks, c->stream, rotated, fixed);
+}
+
 const Breakdown kShells = {kShellImageTileMax, kShellImageTileExtraMax, static_cast<size_t>(kMaxShells) * kShellPartialSlots,
                            &sart_context::d_shell_partials, &sart_context::blocks_per_cu_shells, shell_histogram_blocks_per_cu,
                            shell_block_len_of, launch_shells, shells_check, &sart_context::d_sblock, &sart_context::d_sblock_fin,
@@ -2393,7 +2429,13 @@ const Breakdown kOrigin = {kOriginImageTileMax, kOriginImageTileExtraMax, static
                            origin_block_len_of, launch_origin, origin_check, &sart_context::d_oblock, &sart_context::d_oblock_fin,
                            sart_finalize_origin_device};
 
-// The blocking form of a breakdown (sart_trace_histogram_shells / sart_trace_histogram_channels / sart_trace_histogram_origin): launch into the context's scratch
+const Breakdown kAperture = {kApertureImageTileMax, kApertureImageTileExtraMax, static_cast<size_t>(kAperturePartialSlots),
+                             &sart_context::d_aperture_partials, &sart_context::blocks_per_cu_aperture, aperture_histogram_blocks_per_cu,
+                             aperture_block_len_of, launch_aperture, aperture_check, &sart_context::d_ablock, &sart_context::d_ablock_fin,
+                             sart_finalize_aperture_device};
+
+// The blocking form of a breakdown (sart_trace_histogram_shells / sart_trace_histogram_channels / sart_trace_histogram_origin /
+// sart_trace_histogram_aperture): launch into the context's scratch
 // accumulator and block, finalize both in FIXED64, copy out what the caller asked for.
 int trace_histogram_breakdown(sart_context* c, const sart_trace_params_t* p, const Breakdown& kind, double* image_out,
                               sart_summary_t* summary, double* spectra_out, double* block_out) {
@@ -2616,6 +2658,55 @@ int sart_finalize_origin_device(sart_context* c, const sart_trace_params_t* p, c
 int sart_trace_histogram_origin(sart_context* c, const sart_trace_params_t* p, double* image_out, sart_summary_t* summary,
                                 double* spectra_out, double* origin_out) {
   return trace_histogram_breakdown(c, p, kOrigin, image_out, summary, spectra_out, origin_out);
+}
+
+// ---- aperture map (include/sart.h) -----------------------------------------------------------
+size_t sart_aperture_block_len(int32_t nx, int32_t ny) {
+  const size_t x = nx > 0 ? static_cast<size_t>(nx) : 0u, y = ny > 0 ? static_cast<size_t>(ny) : 0u;
+  return static_cast<size_t>(SART_APERTURE_HEAD) + (x * y + 1u) * static_cast<size_t>(SART_APERTURE_CELL);
+}
+
+int sart_set_aperture_grid(sart_context* c, const sart_aperture_grid_t* g) {
+  if (!c || !g) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (g->nx < 1 || g->nx > kApertureMaxSide || g->ny < 1 || g->ny > kApertureMaxSide)
+    return fail(SART_ERR_INVALID_ARGUMENT, "aperture grid: nx and ny must lie in [1, 4096]");
+  if (static_cast<int64_t>(g->nx) * g->ny > kApertureMaxCells) return fail(SART_ERR_INVALID_ARGUMENT, "aperture grid: more than 2^22 cells");
+  if (!std::isfinite(g->x_min) || !std::isfinite(g->x_max) || !std::isfinite(g->y_min) || !std::isfinite(g->y_max) ||
+      !(g->x_max > g->x_min) || !(g->y_max > g->y_min) || !std::isfinite(g->x_max - g->x_min) || !std::isfinite(g->y_max - g->y_min))
+    return fail(SART_ERR_INVALID_ARGUMENT, "aperture grid: a non-finite or empty range");
+  c->aperture_grid = *g;
+  c->have_aperture = true;
+  return 0;
+}
+
+int sart_get_aperture_grid(sart_context* c, sart_aperture_grid_t* out) {
+  if (!c || !out) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (!c->have_aperture) return fail(SART_ERR_NOT_READY, "no aperture grid (sart_set_aperture_grid)");
+  *out = c->aperture_grid;
+  return 0;
+}
+
+int sart_trace_histogram_aperture_device(sart_context* c, const sart_trace_params_t* p, double* acc_dev, double* aperture_dev) {
+  if (!c || !p || !acc_dev || !aperture_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (int rc = aperture_check(c, p)) return rc;
+  return histogram_launch(c, p, acc_dev, {&kAperture, aperture_dev});
+}
+
+int sart_finalize_aperture_device(sart_context* c, const sart_trace_params_t* p, const void* raw_dev, double* out_dev) {
+  if (!c || !p || !raw_dev || !out_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (int rc = aperture_check(c, p)) return rc;
+  if (!c->quanta_frozen) return fail(SART_ERR_NOT_READY, "no FIXED64 launch has fixed the quanta yet");
+  SART_HIP(hipSetDevice(c->device));
+  if (int rc = status_ensure(c)) return rc;
+  launch_finalize_origin(raw_dev, out_dev, static_cast<size_t>(c->aperture_grid.nx) * static_cast<size_t>(c->aperture_grid.ny) + 1u,
+                         std::ldexp(1.0, c->weight_exp), std::ldexp(1.0, c->weight_sq_exp), c->d_status.p, c->stream);
+  SART_HIP(hipGetLastError());
+  return status_enqueue_copy(c);
+}
+
+int sart_trace_histogram_aperture(sart_context* c, const sart_trace_params_t* p, double* image_out, sart_summary_t* summary,
+                                  double* spectra_out, double* aperture_out) {
+  return trace_histogram_breakdown(c, p, kAperture, image_out, summary, spectra_out, aperture_out);
 }
 
 int sart_trace_histogram(sart_context* c, const sart_trace_params_t* p, double* image_out, sart_summary_t* summary) {

@@ -355,11 +355,11 @@ constexpr double kMirrorMissEps = 1e-3;
 constexpr int kImageTileMax = 63;
 constexpr int kImageTileExtraMax = 43;   // 43 x 43 <= kTileExtraCells: the tile of the variants whose rings are all in use
 
-// The three breakdowns of the histogram trace, per shell, per emission channel and per cell of the solar table, are one pipeline:
-// breakdown_histogram_body (sart_kernels.hip) is the generic histogram kernel with a per-workgroup table in LDS, and
-// shell_histogram_kernel, channel_histogram_kernel and origin_histogram_kernel are its users (ShellBreakdown / ChannelBreakdown /
-// OriginBreakdown: the argument struct, the table, its cells).  What follows is what each of them keeps in that table and hands to
-// its fold.
+// The four breakdowns of the histogram trace, per shell, per emission channel, per cell of the solar table and per cell of the
+// entrance plane, are one pipeline: breakdown_histogram_body (sart_kernels.hip) is the generic histogram kernel with a per-workgroup
+// table in LDS, and shell_histogram_kernel, channel_histogram_kernel, origin_histogram_kernel and aperture_histogram_kernel are its
+// users (ShellBreakdown / ChannelBreakdown / OriginBreakdown / ApertureBreakdown: the argument struct, the table, its cells).  What
+// follows is what each of them keeps in that table and hands to its fold.
 //
 // Per-shell breakdown of the histogram trace (include/sart.h: sart_trace_histogram_shells_device).  shell_histogram_kernel keeps,
 // per workgroup and shell, four u32 counters and two sums in LDS - in the last kShellTableCells cells behind the tables, where the
@@ -424,5 +424,24 @@ struct OriginArgs {
   double _pad;
 };
 static_assert(sizeof(OriginArgs) == 32, "the kernel re-reads OriginArgs with scalar loads");
+
+// Aperture map of the histogram trace (include/sart.h: sart_trace_histogram_aperture_device).  aperture_histogram_kernel adds every
+// passed ray to the cell of a grid over the entrance plane that its entrance point (X0, Y0: pointEntranceXRT) falls in, or to the one
+// cell behind the grid where it falls outside the window - the origin map's three global atomics into one 32-byte cell - and keeps the
+// origin kernel's head table: the same per-wave rows, the same partials, the same image tile maxima, fold_origin_kernel.
+constexpr int kAperturePartialSlots = kOriginPartialSlots;
+constexpr int kApertureTableCells = kOriginTableCells;
+constexpr int kApertureImageTileMax = kOriginImageTileMax;
+constexpr int kApertureImageTileExtraMax = kOriginImageTileExtraMax;
+constexpr int kApertureMaxSide = 4096;        // nx, ny in [1, kApertureMaxSide]
+constexpr int kApertureMaxCells = 1 << 22;    // nx ny <= kApertureMaxCells: a cell index is 32-bit, a byte offset below 2^28
+struct ApertureArgs {
+  double* block;          // the caller's block: SART_APERTURE_HEAD slots, then cells[ny][nx][SART_APERTURE_CELL], then the outside cell
+  double* partials;       // [n_blocks][kAperturePartialSlots] per-workgroup sums (plain stores)
+  int32_t nx, ny;         // the grid's shape
+  double x_min, inv_step_x, y_min, inv_step_y;   // cell of a point: ((X0 - x_min) inv_step_x, (Y0 - y_min) inv_step_y), inv_step = n / (max - min)
+  double _pad;
+};
+static_assert(sizeof(ApertureArgs) == 64, "the kernel re-reads ApertureArgs with scalar loads");
 
 }  // namespace sart

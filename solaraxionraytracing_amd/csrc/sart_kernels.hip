@@ -2305,13 +2305,37 @@ static_assert(offsetof(OriginKernArgs, A) == offsetof(HistKernArgs, A) && offset
 static_assert(SART_ORIGIN_CELL == 4 && SART_ORIGIN_HEAD % SART_ORIGIN_CELL == 0, "a ray's three atomics fall into one aligned 32-byte cell");
 
 // ------------------------------------------------------------------------------------------------
-// the one pipeline of the three breakdowns: breakdown_histogram_body
+// aperture map of the histogram trace (include/sart.h: sart_trace_histogram_aperture_device)
+// ------------------------------------------------------------------------------------------------
+// The fourth user of the pipeline: the origin map's three atomics per passed ray, into the cell of a grid over the entrance plane that
+// the ray's entrance point (X0, Y0 of ring 1: pointEntranceXRT, raytracer.nim:2091-2094) falls in - or into the one cell behind the
+// grid, "outside the window".  The cell index is formed at the head of the phase-B pass, so that one 32-bit register and not the two
+// doubles lives across phase B.  The head, its per-wave table, the partials and the fold are the origin map's.
+struct ApertureKernArgs {
+  HotA H;
+  const DevBlob* blob;
+  TraceArgs A;
+  double* acc;
+  HotB HB;
+  ApertureArgs AP;
+};
+static_assert(offsetof(ApertureKernArgs, A) == offsetof(HistKernArgs, A) && offsetof(ApertureKernArgs, HB) == offsetof(HistKernArgs, HB) &&
+                  offsetof(ApertureKernArgs, AP) == offsetof(HistKernArgs, SC),
+              "the aperture kernel shares the argument offsets of the histogram kernel");
+static_assert(SART_APERTURE_CELL == SART_ORIGIN_CELL && SART_APERTURE_HEAD == SART_ORIGIN_HEAD && SART_APERTURE_N == SART_ORIGIN_N &&
+                  SART_APERTURE_SUM_WEIGHTS == SART_ORIGIN_SUM_WEIGHTS && SART_APERTURE_SUM_WEIGHTS_SQ == SART_ORIGIN_SUM_WEIGHTS_SQ &&
+                  SART_APERTURE_N_PASSED == SART_ORIGIN_N_PASSED && SART_APERTURE_SUM_WEIGHTS_HI == SART_ORIGIN_SUM_WEIGHTS_HI &&
+                  SART_APERTURE_SUM_WEIGHTS_SQ_HI == SART_ORIGIN_SUM_WEIGHTS_SQ_HI,
+              "the aperture block is folded and finalized by the origin block's kernels");
+
+// ------------------------------------------------------------------------------------------------
+// the one pipeline of the four breakdowns: breakdown_histogram_body
 // ------------------------------------------------------------------------------------------------
 // What a breakdown is to the body: its kind, its argument struct and where the kernel arguments hold it, its per-workgroup table in
 // LDS (in the last kTableCells cells behind the tables, the image tile's extra cells in front of it) and the slots it stores of it
-// per workgroup.  What the breakdown does to a ray stands in the body itself, under `if constexpr (kShells / kChannels / kOrigin)`:
+// per workgroup.  What the breakdown does to a ray stands in the body itself, under `if constexpr (kShells / kChannels / kOrigin / kAperture)`:
 // one ray can be followed through one function.
-enum class BreakdownKind { Shells, Channels, Origin };
+enum class BreakdownKind { Shells, Channels, Origin, Aperture };
 struct ShellBreakdown {
   static constexpr BreakdownKind kKind = BreakdownKind::Shells;
   using Args = ShellArgs;
@@ -2344,14 +2368,23 @@ struct OriginBreakdown {
     Sum head[kOriginTableCells / kOriginPartialSlots][kOriginPartialSlots];   // per wave: N_PASSED, sum of w, sum of w^2, unused
   };
 };
+struct ApertureBreakdown {
+  static constexpr BreakdownKind kKind = BreakdownKind::Aperture;
+  using Args = ApertureArgs;
+  static constexpr size_t kArgsOffset = offsetof(ApertureKernArgs, AP);
+  static constexpr int kTableCells = kApertureTableCells;
+  template <class Sum>
+  using Table = OriginBreakdown::Table<Sum>;   // one head row per wave, as the origin map's
+};
 
 template <int BLOCK, bool ROT, bool FIXED, class BD>
 __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* __restrict__ blob, TraceArgs A, double* __restrict__ acc,
                                                          typename BD::Args BDarg) {
   using Sum = std::conditional_t<FIXED, long long, double>;   // per-lane sums: quanta (FIXED) or f64
   constexpr bool kShells = BD::kKind == BreakdownKind::Shells, kChannels = BD::kKind == BreakdownKind::Channels,
-                 kOrigin = BD::kKind == BreakdownKind::Origin;
-  static_assert(!kOrigin || BLOCK / 64 == kOriginTableCells / kOriginPartialSlots, "one row of the origin table per wave");
+                 kOrigin = BD::kKind == BreakdownKind::Origin, kAperture = BD::kKind == BreakdownKind::Aperture;
+  constexpr bool kHead = kOrigin || kAperture;   // the table is the head's rows, one per wave
+  static_assert(!kHead || BLOCK / 64 == kOriginTableCells / kOriginPartialSlots, "one row of the origin table per wave");
   struct LdsLayout {
     TablesLds S;
     double tile_extra[kRingExtraCells - BD::kTableCells];   // cells kTileRingCells .. of the image tile
@@ -2392,7 +2425,7 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
     } else if constexpr (kChannels) {
       for (int i = threadIdx.x; i < kMaxChannels * 3 * kChanLanes; i += BLOCK) (&lds.tab.sum[0][0][0])[i] = 0;
       if (threadIdx.x < kMaxChannels * kChanLanes) (&lds.tab.cnt[0][0])[threadIdx.x] = 0u;
-    }   // (origin: every wave writes its whole row in the epilogue)
+    }   // (origin, aperture: every wave writes its whole row in the epilogue)
   }
   stage_tables<BLOCK>(S, Pb, Tb);   // (its barrier orders the zeroing above before the first use)
   const LdsTables L{S.sincos, S.rcdf_hi, Tb.flux_radius_cdf, S.rguide, S.shells, S.lut};
@@ -2466,6 +2499,7 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
     const bool valid = (uint32_t)lane < n_valid;
     const uint32_t slot = (h1 + (uint32_t)lane) % kQueue;
     RayOut out;
+    [[maybe_unused]] uint32_t ap_cell = 0u;   // aperture: the entrance point's cell, nx ny where it lies outside the window
     {
       st.X0 = Q.w[wave].X0[slot]; st.Y0 = Q.w[wave].Y0[slot];
       st.tsx = Q.w[wave].tsx[slot]; st.tsy = Q.w[wave].tsy[slot];
@@ -2481,6 +2515,16 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
       const int packed = Q.w[wave].idx[slot];
       st.r_idx = packed & 0xFFFF;
       st.shell = packed >> 16;
+      if constexpr (kAperture) {
+        // binned as the image is (prepareHeatmap's rule): inside <=> 0 <= f < n on both axes, so a NaN falls outside.  Formed here,
+        // from the ring's words, so that one 32-bit register lives across phase B.  nx ny <= kApertureMaxCells (host).
+        typename BD::Args APl;
+        reload_kernarg(APl, BD::kArgsOffset);
+        const double fx = (st.X0 - APl.x_min) * APl.inv_step_x;
+        const double fy = (st.Y0 - APl.y_min) * APl.inv_step_y;
+        const bool in_window = (fx >= 0.0) & (fx < (double)APl.nx) & (fy >= 0.0) & (fy < (double)APl.ny);
+        ap_cell = in_window ? (uint32_t)(int)fy * (uint32_t)APl.nx + (uint32_t)(int)fx : (uint32_t)APl.nx * (uint32_t)APl.ny;
+      }
       const DevBlob& Bo = lds_opaque(B);
       HotB HB;
       reload_kernarg(HB, offsetof(HistKernArgs, HB));
@@ -2645,6 +2689,20 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
           unsafeAtomicAdd(oc + SART_ORIGIN_SUM_WEIGHTS_SQ, out.weight * out.weight);
         }
       }
+      // the aperture map: the cell of the ray's entrance point (or the outside cell) takes the same 1, w and w^2, in the same way
+      if constexpr (kAperture) {
+        reload_kernarg(BDl, BD::kArgsOffset);
+        double* const ac = BDl.block + SART_APERTURE_HEAD + (size_t)ap_cell * SART_APERTURE_CELL;
+        if constexpr (FIXED) {
+          atomic_add_slot_i64(ac + SART_APERTURE_N, 1);
+          atomic_add_slot_i64(ac + SART_APERTURE_SUM_WEIGHTS, w_fx);
+          atomic_add_slot_i64(ac + SART_APERTURE_SUM_WEIGHTS_SQ, w2_fx);
+        } else {
+          unsafeAtomicAdd(ac + SART_APERTURE_N, 1.0);
+          unsafeAtomicAdd(ac + SART_APERTURE_SUM_WEIGHTS, out.weight);
+          unsafeAtomicAdd(ac + SART_APERTURE_SUM_WEIGHTS_SQ, out.weight * out.weight);
+        }
+      }
       // the channels: c_t = w f_t, ONE product; the same c_t to the row, the ray's energy bin and its pixel (or the row's OUTSIDE)
       if constexpr (kChannels) {
         const uint32_t cl = (uint32_t)lane & (uint32_t)(kChanLanes - 1);
@@ -2797,7 +2855,7 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
     r[SART_ACC_N_SHELL_SELECTED] = (Sum)n_shell;
     r[SART_ACC_N_OUTSIDE_IMAGE] = (Sum)n_out;
     if constexpr (FIXED) r[SART_ACC_SUM_WEIGHTS_OUTSIDE] = swo;
-    if constexpr (kOrigin) {   // the head's row of this wave: the very sums the scalars take
+    if constexpr (kHead) {   // the head's row of this wave: the very sums the scalars take
       lds.tab.head[wave][0] = (Sum)n_passed;
       lds.tab.head[wave][1] = sw;
       lds.tab.head[wave][2] = sw2;
@@ -2811,7 +2869,7 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
     reinterpret_cast<Sum*>(A.partials)[(size_t)blockIdx.x * SART_ACC_COUNT + threadIdx.x] = t;
   }
   // the breakdown table of this workgroup (every wave has left the loop: the barriers above)
-  if constexpr (kOrigin) {
+  if constexpr (kHead) {
     if (threadIdx.x < kOriginPartialSlots) {
       Sum t = 0;
       for (int w = 0; w < BLOCK / 64; ++w) t += lds.tab.head[w][threadIdx.x];
@@ -2837,7 +2895,7 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
   }
 }
 
-// The three kernels: their names, template parameters and parameter lists are what the host launches and the code objects' tests know.
+// The four kernels: their names, template parameters and parameter lists are what the host launches and the code objects' tests know.
 template <int BLOCK, bool ROT, bool FIXED>
 __global__ __launch_bounds__(BLOCK) void shell_histogram_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
                                                                 double* __restrict__ acc, HotB HBarg, ShellArgs SHarg) {
@@ -2852,6 +2910,11 @@ template <int BLOCK, bool ROT, bool FIXED>
 __global__ __launch_bounds__(BLOCK) void origin_histogram_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
                                                                  double* __restrict__ acc, HotB HBarg, OriginArgs OGarg) {
   breakdown_histogram_body<BLOCK, ROT, FIXED, OriginBreakdown>(H, blob, A, acc, OGarg);
+}
+template <int BLOCK, bool ROT, bool FIXED>
+__global__ __launch_bounds__(BLOCK) void aperture_histogram_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
+                                                                   double* __restrict__ acc, HotB HBarg, ApertureArgs AParg) {
+  breakdown_histogram_body<BLOCK, ROT, FIXED, ApertureBreakdown>(H, blob, A, acc, AParg);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -5345,6 +5408,10 @@ static const BreakdownKernels<OriginArgs> kOriginKernels = {
     {origin_histogram_kernel<1024, true, false>, origin_histogram_kernel<1024, false, false>,
      origin_histogram_kernel<1024, false, true>, origin_histogram_kernel<1024, true, true>},
     {fold_origin_kernel<true>, fold_origin_kernel<false>}};
+static const BreakdownKernels<ApertureArgs> kApertureKernels = {
+    {aperture_histogram_kernel<1024, true, false>, aperture_histogram_kernel<1024, false, false>,
+     aperture_histogram_kernel<1024, false, true>, aperture_histogram_kernel<1024, true, true>},
+    {fold_origin_kernel<true>, fold_origin_kernel<false>}};   // (the head is the origin block's)
 
 template <class Args>
 static int breakdown_blocks_per_cu(const BreakdownKernels<Args>& K, bool rotated) {
@@ -5387,6 +5454,11 @@ int origin_histogram_blocks_per_cu(bool rotated) { return breakdown_blocks_per_c
 void launch_origin_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, double* acc, const OriginArgs& OG,
                              int n_blocks, hipStream_t stream, bool rotated, bool fixed) {
   launch_breakdown_histogram(kOriginKernels, H, HB, blob, A, acc, OG, 1, n_blocks, stream, rotated, fixed);   // (one row: the head)
+}
+int aperture_histogram_blocks_per_cu(bool rotated) { return breakdown_blocks_per_cu(kApertureKernels, rotated); }
+void launch_aperture_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, double* acc, const ApertureArgs& AP,
+                               int n_blocks, hipStream_t stream, bool rotated, bool fixed) {
+  launch_breakdown_histogram(kApertureKernels, H, HB, blob, A, acc, AP, 1, n_blocks, stream, rotated, fixed);   // (one row: the head)
 }
 void launch_finalize_origin(const void* in, double* out, size_t n_cells, double q_w, double q_w2, void* check_dev, hipStream_t stream) {
   FinalizeOriginArgs F{(long long)n_cells, q_w, q_w2};

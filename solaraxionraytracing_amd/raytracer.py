@@ -675,6 +675,59 @@ class RayTracer:
         _lib.check(self.lib.sart_finalize_origin_device(self.handle, C.byref(params), C.c_void_p(raw_ptr),
                                                         C.c_void_p(out_ptr if out_ptr is not None else raw_ptr)))
 
+    # -- aperture map (include/sart.h "aperture map of the histogram trace") --------------------
+    def set_aperture_grid(self, nx: int, ny: int, x_min: float, x_max: float, y_min: float, y_max: float):
+        """The grid of the aperture map (sart_set_aperture_grid): nx x ny cells over [x_min, x_max) x [y_min, y_max) of the entrance
+        plane, mm in the telescope frame (the frame of pointdataXBefore / pointdataYBefore).  Context state, as the source channels."""
+        g = _lib.ApertureGrid(int(nx), int(ny), float(x_min), float(x_max), float(y_min), float(y_max))
+        _lib.check(self.lib.sart_set_aperture_grid(self.handle, C.byref(g)))
+
+    def aperture_grid(self) -> dict:
+        """The context's grid (sart_get_aperture_grid) as a dict nx, ny, x_min, x_max, y_min, y_max."""
+        g = _lib.ApertureGrid()
+        _lib.check(self.lib.sart_get_aperture_grid(self.handle, C.byref(g)))
+        return {k: getattr(g, k) for k, _ in _lib.ApertureGrid._fields_}
+
+    def aperture_block_len(self) -> int:
+        """sart_aperture_block_len for this context's grid."""
+        g = self.aperture_grid()
+        return int(self.lib.sart_aperture_block_len(g["nx"], g["ny"]))
+
+    aperture_params = shells_params
+
+    def trace_aperture(self, n_rays: int, seed: int = 299792458, ray_id_offset: int = 0, flags: int | None = None, image_n: int = 256,
+                       spectra: bool = True, n_radial_bins: int = 10_000, radial_max: float = 10.0):
+        """trace_histogram (trace_spectra with ``spectra``) plus the aperture map (sart_trace_histogram_aperture): the detected weight
+        per cell of the context's grid over the entrance plane (set_aperture_grid).  Returns (image, summary, spectra dict or None,
+        aperture dict: ``head``, the maps ``counts``, ``weights``, ``weights_sq`` [ny][nx], ``outside`` and the grid's ``x_edges`` /
+        ``y_edges``); see solaraxionraytracing_amd.aperture for what the maps answer."""
+        p = self.aperture_params(n_rays, seed, ray_id_offset, flags, image_n, spectra, n_radial_bins, radial_max)
+        g = self.aperture_grid()
+        n_e = self.full.energies.size
+        img = np.empty((image_n, image_n))
+        summ = Summary()
+        spec = np.empty(2 * n_radial_bins + 3 * (n_e + 1)) if spectra else None
+        block = np.empty(_lib.aperture_block_len(g["nx"], g["ny"]))
+        _lib.check(self.lib.sart_trace_histogram_aperture(self.handle, C.byref(p), _lib.as_dp(img) if image_n else None, C.byref(summ),
+                                                          _lib.as_dp(spec) if spectra else None, _lib.as_dp(block)))
+        amap = split_aperture(block, g["nx"], g["ny"])
+        amap["x_edges"] = np.linspace(g["x_min"], g["x_max"], g["nx"] + 1)
+        amap["y_edges"] = np.linspace(g["y_min"], g["y_max"], g["ny"] + 1)
+        return (img, {k: summ.v[i] for k, i in _lib.ACC.items()},
+                split_spectra(spec, n_radial_bins, n_e + 1, radial_max) if spectra else None, amap)
+
+    def trace_aperture_device(self, params: TraceParams, accumulator_ptr: int, aperture_ptr: int):
+        """Asynchronous form: adds into a device accumulator and a device block of aperture_block_len() slots (raw int64 in fixed64
+        mode); ``params.accumulate`` as in trace_origin_device."""
+        _lib.check(self.lib.sart_trace_histogram_aperture_device(self.handle, C.byref(params), C.c_void_p(accumulator_ptr),
+                                                                 C.c_void_p(aperture_ptr)))
+
+    def finalize_aperture_device(self, params: TraceParams, raw_ptr: int, out_ptr: int | None = None):
+        """Raw FIXED64 aperture block (device) -> doubles (device; in place by default).  Asynchronous; what the conversion finds wrong
+        is raised by the next ``synchronize()``."""
+        _lib.check(self.lib.sart_finalize_aperture_device(self.handle, C.byref(params), C.c_void_p(raw_ptr),
+                                                          C.c_void_p(out_ptr if out_ptr is not None else raw_ptr)))
+
     # -- fused axion-mass scan (gas stage; include/sart.h "fused axion-mass scan") -------------
     def trace_mass_scan(self, masses_ev, n_rays: int, seed: int = 299792458, ray_id_offset: int = 0, flags: int | None = None):
         """Every ray of [ray_id_offset, ray_id_offset + n_rays) traced ONCE and weighed for every axion mass.  Returns
@@ -859,6 +912,8 @@ channel_block_len = _lib.channel_block_len
 split_channels = _lib.split_channels
 origin_block_len = _lib.origin_block_len
 split_origin = _lib.split_origin
+aperture_block_len = _lib.aperture_block_len
+split_aperture = _lib.split_aperture
 
 # Which coupling every term of the emission table carries (csrc/sart_emission.hip: the g_ae^2, g_agamma^2 and g_anuclei^2 factors of
 # its eight terms, in the order of _lib.EM_TERMS), and the reference values the library's table is made with (readOpacityFile.nim:640-643).
