@@ -1785,8 +1785,8 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   };
-  auto prefix_of = [](uint64_t mask) {   // number of set mask bits below this lane
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+  auto prefix_from = [](uint64_t mask, uint32_t base) {   // base + number of set mask bits below this lane (v_mbcnt adds to its operand)
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, base));
   };
 
   // The seven sine / cosine coefficients of phase A (sincos_coef()'s values) in vector registers for the whole kernel, where the
@@ -1849,7 +1849,7 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
     const uint32_t cnt = (uint32_t)__popcll(mask);
     if (alive) {
       asm volatile("; hot: ring 1 write");
-      const uint32_t slot = (t1 + prefix_of(mask)) % kQueue;
+      const uint32_t slot = prefix_from(mask, t1) % kQueue;
       Q.w[wave].X0[slot] = st.X0; Q.w[wave].Y0[slot] = st.Y0;
       Q.w[wave].tsx[slot] = st.tsx; Q.w[wave].tsy[slot] = st.tsy;
       if (!PATHC) Q.w[wave].path[slot] = st.path_cb;
@@ -2079,7 +2079,10 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
         asm volatile("; hot x0.25: one block of the shared word stream per four passes");
         stream = stream_block(((first_chunk + (uint64_t)chunk) << 6) + (uint64_t)lane, A.seed_lo, A.seed_hi);
       }
-      const uint32_t w = word_of(stream, pass);                      // high word of u3 (:418) of this pass' ray
+      // high word of u3 (:418) of this pass' ray: the block's next word, with the block moved down by one word behind it.  (Picked by
+      // `pass` - word_of() - the wave-uniform index becomes a chain of seven scalar branches in every pass.)
+      const uint32_t w = stream.x;
+      stream.x = stream.y; stream.y = stream.z; stream.z = stream.w;
       const uint32_t rel = ((chunk << 8) + pass) + lane4;
       if (early_reject) {
         // ---- stage A0: the word against the zones (lane masks and scalar arithmetic only) ----
@@ -2088,18 +2091,21 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
         const uint32_t zone_reached = kZonesInVgprs ? (uint32_t)__builtin_amdgcn_readfirstlane((int)zone_reached_v) : Z.zone_reached;
         // lane masks of direct compares (v_cmp writes them) and scalar arithmetic on the masks; the final mask becomes the
         // EXEC mask of the ring write as it is (inverse ballot), with no per-lane 0 / 1 in between
-        uint64_t dead_m = 0, reached_m = 0;
+        uint64_t dead_m = 0, in_first = 0;
 #pragma unroll
         for (int z = 0; z < kMaxZones; ++z) {   // unused zones are empty: lo > hi
           const uint64_t in = kZonesInVgprs ? (ballot64(w >= zone_lo_v[z]) & ballot64(w <= zone_hi_v[z]))
                                             : (ballot64(w >= Z.lo[z]) & ballot64(w <= Z.hi[z]));
           dead_m |= in;
-          reached_m |= ((zone_reached >> z) & 1u) ? in : 0ull;      // wave-uniform select
+          if (z == 0) in_first = in;
         }
+        // Only the first zone can be one whose rays do not count as having reached the telescope (sart_api.hip: build_zones puts
+        // the zone of kind (a) in front, every zone behind it is of kind (b)): ONE wave-uniform select, not one per zone.
+        const uint64_t reached_m = dead_m & ~((zone_reached & 1u) ? 0ull : in_first);
         // all four ids of every lane lie inside the launch for every chunk but the first and the last (wave-uniform test)
-        const uint32_t chunk_lo = chunk << 8;
+        // (only chunk 0 can begin below rel_begin and only chunk n_chunks - 1 can end above rel_end: ONE unsigned compare finds both)
         uint64_t valid_m = ~0ull;
-        if ((chunk_lo < rel_begin) | (chunk_lo + 256u > rel_end)) valid_m = ballot64(rel >= rel_begin) & ballot64(rel < rel_end);
+        if (chunk - 1u >= n_chunks - 2u) valid_m = ballot64(rel >= rel_begin) & ballot64(rel < rel_end);
         n_reached += (uint32_t)__popcll(valid_m & reached_m);
 #ifdef SART_DEBUG_KNOBS
         const uint64_t mask = (A.flags & 0x20000000u) ? 0ull : (valid_m & ~dead_m);   // experiment: nothing reaches stage A1
@@ -2108,7 +2114,7 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
 #endif
         if (__builtin_amdgcn_inverse_ballot_w64(mask)) {
           asm volatile("; hot: ring 0 write");
-          const uint32_t slot = (t0 + prefix_of(mask)) % kQueue;
+          const uint32_t slot = prefix_from(mask, t0) % kQueue;
           Q.w[wave].ray[slot] = rel;
           Q.w[wave].u3hi[slot] = w;
         }
@@ -2124,8 +2130,15 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
     SART_STAGE_MARK("LOOP");
     if (early_reject) {
       // ---- stage A1 on a full wave of A0 survivors (or on the remainder once the input is exhausted) ----
+      // (the drain's conditions in blocks of their own, which a wave with input left jumps over: written as one expression they are
+      // ten scalar instructions in every iteration)
       const uint32_t n0 = t0 - h0;
-      if ((n0 >= 64u) | (!have_new & (n0 > 0u))) {   // bitwise on purpose: `||` would become a per-lane select of 0 / 1
+      bool a1_due = n0 >= 64u;
+      if (chunk >= n_chunks) {   // (compared again, on the scalar unit: `have_new` carried here is a lane mask rebuilt with two vector instructions)
+        asm volatile("; the drain");   // (keeps the block a block: no select form)
+        a1_due = n0 > 0u;
+      }
+      if (a1_due) {
         const uint32_t m = min(n0, 64u);
         const bool v = (uint32_t)lane < m;
         const uint32_t slot = (h0 + (uint32_t)lane) % kQueue;
@@ -2142,14 +2155,22 @@ __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const De
     // ---- stage B on a full wave of A1 survivors (or on the remainder at the very end) ----
     SART_STAGE_MARK("LOOP");
     const uint32_t n1 = t1 - h1;
-    const bool draining = !have_new & (t0 == h0);
-    if ((n1 >= 64u) | (draining & (n1 > 0u))) {
+    bool b_due = n1 >= 64u, draining = false;
+    if (chunk >= n_chunks) {
+      asm volatile("; the drain");   // (keeps the block a block: no select form)
+      draining = t0 == h0;
+      b_due |= draining & (n1 > 0u);
+    }
+    if (b_due) {
       SART_STAMP(ts_b);
       run_phase_b(min(n1, 64u));
       ring_sync();
       SART_SPAN(cyc_b, ts_b);
     }
-    if (draining & (t1 == h1)) break;
+    if (draining) {
+      asm volatile("; the drain");   // (keeps the block a block: no select form)
+      if (t1 == h1) break;
+    }
   }
 
   SART_STAGE_MARK("EPILOGUE");
