@@ -590,6 +590,64 @@ int sart_trace_mass_scan(sart_context* ctx, const sart_trace_params_t* params, c
 int sart_finalize_mass_scan_device(sart_context* ctx, const sart_trace_params_t* params, const double* masses_ev,
                                    int32_t n_masses, const void* scan_fixed_device, double* out_f64_device);
 
+/* ---- fused axion-mass scan with energy bands ------------------------------ */
+/*
+ * Near resonance the conversion probability is a narrow function of energy, so the SHAPE of the detected spectrum changes from
+ * mass to mass: what a gas-phase analysis fits is the expected signal per energy bin and per mass.  These entry points are the
+ * fused mass scan above - every ray traced once, weighed for n_masses masses - that also splits each mass's sum of w and sum of
+ * w^2 by the energy band of the ray.
+ *
+ * Bands are uniform in energy-INDEX space (a ray's energy is an index of the context's energy table; no float compare): a passed
+ * ray with energy index e belongs to band (e - e0) / width if e0 <= e < e0 + n_bands width, and to the OUTSIDE cell, index
+ * n_bands, otherwise (the X-ray test source's index n_energies follows the same rule).  n_bands in [1, 31], width >= 1, e0 >= 0;
+ * anything else: SART_ERR_INVALID_ARGUMENT, context unchanged.
+ *
+ * scan_acc_device: exactly the rows sart_trace_mass_scan_device writes for the same arguments - same layout, same values, bit for
+ * bit in SART_ACCUM_FIXED64.
+ * spectra_device: (n_masses + 1) blocks of (n_bands + 1) cells of SART_MSPEC_CELL 8-byte slots (f64, or int64 when raw FIXED64):
+ *   block k < n_masses, cell b   SART_MSPEC_SUM_WEIGHTS, _SUM_WEIGHTS_SQ of masses_ev[k] and band b (raw FIXED64: + the high limbs
+ *                                SART_MSPEC_SUM_WEIGHTS_HI / _SQ_HI, value = (hi 2^40 + lo) quantum, 0 <= lo < 2^40 after a launch;
+ *                                the quanta are those of mass k in the plain scan; the HI slots read 0 in f64)
+ *   block n_masses, cell b       SART_MSPEC_N_ON_DETECTOR: the rays of band b on the chip whose mass-independent weight factor is
+ *                                non-zero - SART_SCAN_N_ON_DETECTOR split by band; the other slots are 0
+ * Conservation (FIXED64: exactly, as integers): for every k the cells of block k, the outside cell included, add up to row k of
+ * the scan rows (sum of w and sum of w^2, both limbs combined); the band counts add up to SART_SCAN_N_ON_DETECTOR.
+ * Contract: for mass k and any band, SUM_WEIGHTS equals the sum over the band's indices of energy_weights[e] of a
+ * sart_trace_histogram_device spectra launch (accumulate = 0) after sart_set_axion_mass(masses_ev[k]) on the same ray ids: bit for
+ * bit in FIXED64 (the energy-weight spectrum shares q_w with SUM_WEIGHTS), up to the summation order in f64.
+ * params->accumulate, the groups of 32 masses per launch, the refusal outside the gas stage and the multi-GPU rule (ranks add both
+ * raw buffers as int64) are those of the plain scan.  FIXED64: a band cell of a workgroup can receive every ray the workgroup
+ * traces in one launch, so a launch is refused (SART_ERR_INVALID_ARGUMENT) when that number exceeds 2^(headroom_bits - 1) or 2^23
+ * (the room the quantum of SUM_WEIGHTS_SQ leaves): with the default headroom, never for n_rays <= 2^31 per call on a full grid.
+ * Cost (profiles/r20_mass_scan_spectra_rate.txt: BabyIAXO / XMM, gas stage, 32 masses, 3e8 rays per scan, one MI355X): with 31 bands
+ * the scan takes the plain scan's time within the spread of the repeats (6.6 against 6.4 ms in f64, 6.7 against 6.7 ms in FIXED64)
+ * and 1 / 115 of the host loop of 32 single-mass spectra launches (766 ms).  FEWER bands cost MORE: the lanes of a wave whose rays
+ * share a band add to one LDS cell, which the LDS unit takes one after the other - 8 bands 10.3 / 7.7 ms, 1 band 22.1 / 15.4 ms
+ * (f64 / FIXED64; still 35 to 50 times faster than the host loop).  Ask for a fine set of bands and sum it on the host.
+ */
+typedef struct sart_energy_bands_t { int32_t e0, width, n_bands; } sart_energy_bands_t;
+enum { SART_MSPEC_SUM_WEIGHTS = 0, SART_MSPEC_SUM_WEIGHTS_SQ = 1, SART_MSPEC_SUM_WEIGHTS_HI = 2, SART_MSPEC_SUM_WEIGHTS_SQ_HI = 3,
+       SART_MSPEC_CELL = 4 };
+enum { SART_MSPEC_N_ON_DETECTOR = 0 };
+/* 8-byte slots of the spectra buffer: (n_masses + 1) (n_bands + 1) SART_MSPEC_CELL.  (Exported, like sart_energy_scan_len.) */
+size_t sart_mass_scan_spectra_len(int32_t n_masses, int32_t n_bands);
+/* Both buffers are DEVICE memory (sart_mass_scan_len(n_masses) and sart_mass_scan_spectra_len(n_masses, bands->n_bands) 8-byte
+ * slots); asynchronous on the context's stream. */
+int sart_trace_mass_scan_spectra_device(sart_context* ctx, const sart_trace_params_t* params, const double* masses_ev,
+                                        int32_t n_masses, const sart_energy_bands_t* bands, double* scan_acc_device,
+                                        double* spectra_device);
+/* Blocking form with HOST outputs of the same lengths (finalized in FIXED64 mode). */
+int sart_trace_mass_scan_spectra(sart_context* ctx, const sart_trace_params_t* params, const double* masses_ev, int32_t n_masses,
+                                 const sart_energy_bands_t* bands, double* scan_out_host, double* spectra_out_host);
+/* Raw FIXED64 buffers -> doubles: out_f64_device receives the scan rows (sart_mass_scan_len doubles) and, behind them, the spectra
+ * (sart_mass_scan_spectra_len doubles); it overlaps neither input.  Asynchronous; the next sart_synchronize returns
+ * SART_ERR_ACCUMULATOR if a slot is negative or >= 2^62, if either conservation law above fails, or for what
+ * sart_finalize_mass_scan_device reports about the rows (per mass: the resolution rule; a mass whose SUM_WEIGHTS_SQ is not
+ * resolved reads NaN there and in every cell of its block). */
+int sart_finalize_mass_scan_spectra_device(sart_context* ctx, const sart_trace_params_t* params, const double* masses_ev,
+                                           int32_t n_masses, const sart_energy_bands_t* bands, const void* scan_fixed_device,
+                                           const void* spectra_fixed_device, double* out_f64_device);
+
 /* ---- fused angular scan (BASELINE configs[3]) ----------------------------- */
 /*
  * performAngularScan (raytracer.nim:2778-2802) re-runs calculateFluxFractions per telescope angle: it copies the setup, sets

@@ -91,6 +91,15 @@ int sart_host_angular_scan(sart_context* ctx, const double* angles_deg, int32_t 
 int sart_host_axion_mass_scan(sart_context* ctx, const double* masses_ev, int32_t n_masses, uint64_t n_rays, uint64_t seed,
                               uint64_t ray_id_offset, uint32_t flags, double* fluxes_out, double* flux_sq_out,
                               double* n_passed_out);
+/* The same scan with its signal split by energy band (sart_trace_mass_scan_spectra, include/sart.h; gas stage only:
+ * SART_ERR_INVALID_ARGUMENT otherwise): e0, width, n_bands describe the bands in energy-index space.  fluxes_out, flux_sq_out,
+ * n_passed_out as above (the latter two may be NULL); band_flux_out[i (n_bands + 1) + b] = sum of the weights of mass i in band b,
+ * b = n_bands being everything outside the window, band_flux_sq_out (may be NULL) the sums of their squares;
+ * band_counts_out[b] (may be NULL; n_bands + 1 values) the rays of band b on the detector. */
+int sart_host_axion_mass_scan_spectra(sart_context* ctx, const double* masses_ev, int32_t n_masses, uint64_t n_rays, uint64_t seed,
+                                      uint64_t ray_id_offset, uint32_t flags, int32_t e0, int32_t width, int32_t n_bands,
+                                      double* fluxes_out, double* flux_sq_out, double* n_passed_out, double* band_flux_out,
+                                      double* band_flux_sq_out, double* band_counts_out);
 /* The scan of rounds 1-3 under its old name, with its old meaning: a host loop in performAngularScan's shape - mass i on its OWN
  * block of fresh rays, ids [ray_id_offset + i n_rays_per_mass, ...) - through flux-only launches.  (Round 4 had routed this name
  * through the fused kernel: same signature, correlated scan points, other numbers for the same seed.  The fused scan is

@@ -69,6 +69,8 @@ type
   ## sart_fixed_quanta_t: what one count of a raw SART_ACCUM_FIXED64 accumulator is worth
   SartFixedQuanta* {.importc: "sart_fixed_quanta_t", header: sartH, bycopy.} = object
     weight*, weight_sq*, position*, reflect*: cdouble
+  SartEnergyBands* {.importc: "sart_energy_bands_t", header: sartH, bycopy.} = object   ## bands of the banded mass scan, in energy-index space
+    e0*, width*, n_bands*: int32
 
 const   # accumulation modes (include/sart.h)
   AccumF64* = 0
@@ -151,6 +153,18 @@ proc sart_trace_mass_scan*(ctx: ptr SartContext, p: ptr SartTraceParams, massesE
                            scanOutHost: ptr cdouble): cint {.importc, header: sartH.}
 proc sart_finalize_mass_scan_device*(ctx: ptr SartContext, p: ptr SartTraceParams, massesEv: ptr cdouble, nMasses: int32,
                                      scanFixedDevice: pointer, outF64Device: ptr cdouble): cint {.importc, header: sartH.}
+## banded mass scan: the scan rows above and, per mass and energy band, sum w / sum w^2: (nMasses + 1) blocks of (nBands + 1) cells of 4
+## slots (cell nBands: everything outside the window; block nMasses: the per-band on-detector counts in slot 0)
+proc sart_mass_scan_spectra_len*(nMasses: int32, nBands: int32): csize_t {.importc, header: sartH.}
+proc sart_trace_mass_scan_spectra_device*(ctx: ptr SartContext, p: ptr SartTraceParams, massesEv: ptr cdouble, nMasses: int32,
+                                          bands: ptr SartEnergyBands, scanAccDevice: ptr cdouble,
+                                          spectraDevice: ptr cdouble): cint {.importc, header: sartH.}
+proc sart_trace_mass_scan_spectra*(ctx: ptr SartContext, p: ptr SartTraceParams, massesEv: ptr cdouble, nMasses: int32,
+                                   bands: ptr SartEnergyBands, scanOutHost: ptr cdouble,
+                                   spectraOutHost: ptr cdouble): cint {.importc, header: sartH.}
+proc sart_finalize_mass_scan_spectra_device*(ctx: ptr SartContext, p: ptr SartTraceParams, massesEv: ptr cdouble, nMasses: int32,
+                                             bands: ptr SartEnergyBands, scanFixedDevice: pointer, spectraFixedDevice: pointer,
+                                             outF64Device: ptr cdouble): cint {.importc, header: sartH.}
 ## fused angular scan: every ray sampled and cut once, turned through nAngles telescope angles; (nAngles + 1) rows of SartAScanRow slots
 proc sart_trace_angular_scan_device*(ctx: ptr SartContext, p: ptr SartTraceParams, turnedYDeg: ptr cdouble, nAngles: int32,
                                      scanAccDevice: ptr cdouble): cint {.importc, header: sartH.}
@@ -242,6 +256,7 @@ static:
   doAssert sizeof(Axion) == 208            # the record layout the library writes (raytracer.nim:192-221; SURVEY 8a a1)
   doAssert sizeof(SartSetup) == 2504
   doAssert sizeof(SartTraceParams) == 88
+  doAssert sizeof(SartEnergyBands) == 12
   doAssert sizeof(SartSummary) == 8 * SartAccCount
 
 template sartCheck*(rc: cint) =

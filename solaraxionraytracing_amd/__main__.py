@@ -5,6 +5,7 @@
         [--fusedAngularScan] [--angularImages]
         [--noPlots] [--config FILE | --configPath DIR]  [--rays N] [--seed S] [--outpath DIR]
         [--massScanMin M0 --massScanMax M1 --numMassScanPoints K]     (not in the reference: see below)
+        [--massScanBands N [--massScanBandMin keV --massScanBandMax keV]]  (with the mass scan: see below)
         [--energyScanMin E0 --energyScanMax E1 --numEnergyScanPoints K]  (not in the reference: see below)
         [--shellBreakdown]                                               (not in the reference: see below)
         [--emissionChannels {terms,couplings}]                           (not in the reference: see below)
@@ -19,6 +20,11 @@ behind them are written as CSV), and without a config file the setup is that of 
 A third mode the reference does not have (it has one constant mAxion, :255): --massScanMin / --massScanMax / --numMassScanPoints
 run the fused axion-mass scan (every ray traced once, weighed for every mass; `stageSetup = "gas"` in the config, else the flux does
 not depend on the mass) and write `axion_mass_scan.csv`.
+With --massScanBands N (gas stage) the same trace also splits every mass's signal into N energy bands (1 .. 31; uniform in the index
+of the energy table, over the whole table or over [--massScanBandMin, --massScanBandMax] keV, which must lie on cell edges) and
+writes `axion_mass_scan_spectra.csv`: one row per mass and band - band edges, flux, its error sqrt(sum of w^2), the axions of the
+band on the detector - and per mass one last row (band N, edges nan) for everything outside the bands, so that a mass's rows add up
+to its flux in `axion_mass_scan.csv`.
 A fourth: --energyScanMin / --energyScanMax / --numEnergyScanPoints (keV) run the fused energy scan of the X-ray test source
 (`--xrayTest` or the config's [TestXraySource]; every ray traced once, weighed at every energy) and write `energy_scan.csv`: the
 detection efficiency per energy and, for a parallel beam, the effective area (the quantity of the reference's
@@ -55,7 +61,7 @@ import sys
 import numpy as np
 
 from . import _lib, aperture, config as cfgmod, origin
-from .raytracer import (RayTracer, angle_image_names, containment_radii, initFullSetup, performAngularScan, performAxionMassScan,
+from .raytracer import (RayTracer, energy_bands, angle_image_names, containment_radii, initFullSetup, performAngularScan, performAxionMassScan,
                         performEnergyScan, write_channel_csvs, write_image_csv, write_shell_csvs)
 
 WINDOW_YEAR = {_lib.DK_INGRID2017: "2017", _lib.DK_INGRID2018: "2018", _lib.DK_INGRIDIAXO: "IAXO"}   # WindowYearKind, :1468-1484
@@ -84,6 +90,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--massScanMin", type=float, default=0.0, help="eV (extension: fused axion-mass scan)")
     ap.add_argument("--massScanMax", type=float, default=0.0, help="eV")
     ap.add_argument("--numMassScanPoints", type=int, default=32)
+    ap.add_argument("--massScanBands", type=int, default=0, metavar="N",
+                    help="extension (mass scan, gas stage): also the signal per energy band and mass, axion_mass_scan_spectra.csv; "
+                         "N bands (1 .. 31) over the whole energy table, or over [--massScanBandMin, --massScanBandMax]")
+    ap.add_argument("--massScanBandMin", type=float, default=None, metavar="keV", help="lower edge of the bands (a cell edge of the energy table)")
+    ap.add_argument("--massScanBandMax", type=float, default=None, metavar="keV", help="upper edge of the bands")
     ap.add_argument("--energyScanMin", type=float, default=0.0, help="keV (extension: fused energy scan of the X-ray test source)")
     ap.add_argument("--energyScanMax", type=float, default=0.0, help="keV")
     ap.add_argument("--numEnergyScanPoints", type=int, default=32)
@@ -159,6 +170,18 @@ def check_scan_args(ap: argparse.ArgumentParser, args) -> None:
                 ap.error("--apertureMap: --apertureWindow takes four numbers x0,x1,y0,y1")
             if not (np.all(np.isfinite([x0, x1, y0, y1])) and x1 > x0 and y1 > y0):
                 ap.error("--apertureMap: --apertureWindow needs finite x0 < x1 and y0 < y1")
+    if getattr(args, "massScanBands", 0) or getattr(args, "massScanBandMin", None) is not None or getattr(args, "massScanBandMax", None) is not None:
+        if not args.massScanMax > args.massScanMin:
+            ap.error("--massScanBands belongs to the mass scan: it needs --massScanMin < --massScanMax")
+        if energy_scan_requested(args) or args.angularScanMin != args.angularScanMax:
+            ap.error("--massScanBands cannot be combined with an angular or energy scan")
+        if not 1 <= args.massScanBands <= _lib.MSPEC_MAX_BANDS:
+            ap.error("--massScanBands must lie in [1, %d]" % _lib.MSPEC_MAX_BANDS)
+        if (args.massScanBandMin is None) != (args.massScanBandMax is None):
+            ap.error("--massScanBands: give both --massScanBandMin and --massScanBandMax, or neither")
+        if args.massScanBandMin is not None and not (np.isfinite([args.massScanBandMin, args.massScanBandMax]).all()
+                                                     and args.massScanBandMin < args.massScanBandMax):
+            ap.error("--massScanBands needs finite --massScanBandMin < --massScanBandMax (keV)")
     if not energy_scan_requested(args):
         return
     if args.massScanMax > args.massScanMin or args.angularScanMin != args.angularScanMax:
@@ -187,6 +210,26 @@ def aperture_window(args, full=None):
         return x0, x1, y0, y1
     half = 1.02 * max(full.setup.all_r1[:full.setup.n_shells])
     return -half, half, -half, half
+
+
+def mass_scan_bands(ap: argparse.ArgumentParser, args, full):
+    """((e0, width, n_bands), edges in keV) of --massScanBands: the requested window, or the whole energy table in N bands of the
+    largest whole width that fits (the indices left over at the top land in the outside cell).  Exits 2 for a request the
+    table's index grid cannot represent, and outside the gas stage."""
+    if full.setup.stage != _lib.SK_GAS:
+        ap.error("--massScanBands needs the gas stage (the vacuum conversion probability does not depend on the axion mass)")
+    en = np.asarray(full.energies, dtype=np.float64)
+    try:
+        if args.massScanBandMin is not None:
+            return energy_bands(en, args.massScanBandMin, args.massScanBandMax, args.massScanBands)
+        step = (en[-1] - en[0]) / (en.size - 1)
+        width = en.size // args.massScanBands
+        if width < 1:
+            raise ValueError("--massScanBands: the energy table has fewer points (%d) than bands" % en.size)
+        lo = en[0] - 0.5 * step
+        return energy_bands(en, lo, lo + step * width * args.massScanBands, args.massScanBands)
+    except ValueError as e:
+        ap.error(str(e))
 
 
 def event_columns(args) -> list:
@@ -237,6 +280,8 @@ def main(argv=None) -> int:
             ap.error("--originMap needs the solar source: the config's X-ray test source is active")
         if full.em_rates is None:
             ap.error("--originMap needs the emission table on the host (this setup makes it on the device: %s)" % full.meta.get("emission"))
+    if args.massScanBands:
+        bands, band_edges = mass_scan_bands(ap, args, full)
     n = int(args.rays)
     os.makedirs(args.outpath, exist_ok=True)
     print("Flags:", [name for name, bit in (("cfIgnoreDetWindow", _lib.CF_IGNORE_DET_WINDOW), ("cfIgnoreGasAbs", _lib.CF_IGNORE_GAS_ABS),
@@ -259,7 +304,24 @@ def main(argv=None) -> int:
             print("wrote", out)
         elif args.massScanMax > args.massScanMin:
             masses = np.linspace(args.massScanMin, args.massScanMax, args.numMassScanPoints)
-            fluxes, errs, n_pass = performAxionMassScan(rt, masses, n, seed=args.seed, flags=flags, errors=True)
+            if args.massScanBands:
+                res = performAxionMassScan(rt, masses, n, seed=args.seed, flags=flags, bands=bands)
+                fluxes, errs, n_pass = res["flux"], res["sigma"], res["n_passed"]
+                out = os.path.join(args.outpath, "axion_mass_scan_spectra.csv")
+                lo_edges = np.append(band_edges[:-1], np.nan)      # the last row of a mass: everything outside the window
+                hi_edges = np.append(band_edges[1:], np.nan)
+                with open(out, "w") as f:
+                    f.write("m_a [eV],band,E min [keV],E max [keV],flux,flux error,axions on detector\n")
+                    for k, m in enumerate(masses):
+                        for b in range(bands[2] + 1):
+                            f.write("%r,%d,%r,%r,%r,%r,%d\n" % (float(m), b, float(lo_edges[b]), float(hi_edges[b]), float(res["band_flux"][k, b]),
+                                                               float(res["band_sigma"][k, b]), int(res["band_counts"][b])))
+                print("mass scan spectra: %d bands of %d energy indices from index %d (%.6g - %.6g keV), %d of %d axions on the detector "
+                      "outside them" % (bands[2], bands[1], bands[0], band_edges[0], band_edges[-1], int(res["band_counts"][-1]),
+                                        int(res["band_counts"].sum())))
+                print("wrote", out)
+            else:
+                fluxes, errs, n_pass = performAxionMassScan(rt, masses, n, seed=args.seed, flags=flags, errors=True)
             out = os.path.join(args.outpath, "axion_mass_scan.csv")
             with open(out, "w") as f:
                 f.write("m_a [eV],flux,flux error,passed axions,relative flux\n")

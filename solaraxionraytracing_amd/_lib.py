@@ -42,6 +42,13 @@ SCAN_ROW = 8
 SCAN = dict(SUM_WEIGHTS=0, SUM_WEIGHTS_SQ=1, N_PASSED=2)
 SCAN_HI = dict(SUM_WEIGHTS=4, SUM_WEIGHTS_SQ=5)
 SCAN_SHARED = dict(N_RAYS=0, N_REACHED_TELESCOPE=1, N_SHELL_SELECTED=2, N_HIT_NICKEL=3, N_ON_DETECTOR=4)
+# banded mass scan (include/sart.h: SART_MSPEC_*): (n_masses + 1) blocks of (n_bands + 1) cells of MSPEC_CELL slots; the last cell of a
+# block is the outside cell, the last block holds the per-band counts of MSPEC_COUNTS
+MSPEC_CELL = 4
+MSPEC = dict(SUM_WEIGHTS=0, SUM_WEIGHTS_SQ=1)
+MSPEC_HI = dict(SUM_WEIGHTS=2, SUM_WEIGHTS_SQ=3)
+MSPEC_COUNTS = dict(N_ON_DETECTOR=0)
+MSPEC_MAX_BANDS = 31      # csrc/sart_device.h: kScanBandsMax (the 32 cells of a mass less the outside cell)
 # fused angular scan (include/sart.h: SART_ASCAN_*): (n_angles + 1) rows of ASCAN_ROW slots; the last row holds the counters of ASCAN_SHARED
 ASCAN_ROW = 8
 ASCAN = dict(SUM_WEIGHTS=0, SUM_WEIGHTS_SQ=1, N_PASSED=2, N_SHELL_SELECTED=3, N_HIT_NICKEL=6, N_PASSED_TILL_WINDOW=7)
@@ -80,6 +87,11 @@ APERTURE_HEAD_SLOTS = dict(N_PASSED=0, SUM_WEIGHTS=1, SUM_WEIGHTS_SQ=2)
 APERTURE_HEAD_HI = dict(SUM_WEIGHTS=4, SUM_WEIGHTS_SQ=5)
 APERTURE_MAX_SIDE = 4096
 APERTURE_MAX_CELLS = 1 << 22
+
+
+def mass_scan_spectra_len(n_masses: int, n_bands: int) -> int:
+    """sart_mass_scan_spectra_len: 8-byte slots of the spectra buffer of a banded mass scan."""
+    return (int(n_masses) + 1) * (int(n_bands) + 1) * MSPEC_CELL
 
 
 def energy_scan_len(n_energies: int) -> int:
@@ -293,6 +305,11 @@ class Summary(C.Structure):
     _fields_ = [("v", _d * SART_ACC_COUNT)]
 
 
+class EnergyBands(C.Structure):
+    """sart_energy_bands_t"""
+    _fields_ = [("e0", _i), ("width", _i), ("n_bands", _i)]
+
+
 class FixedQuanta(C.Structure):
     """sart_fixed_quanta_t"""
     _fields_ = [("weight", _d), ("weight_sq", _d), ("position", _d), ("reflect", _d)]
@@ -379,6 +396,11 @@ SART_SYMBOLS = {
     "sart_finalize_angular_scan_device": (C.c_int, [C.c_void_p, _P(TraceParams), _i, C.c_void_p, C.c_void_p]),
     "sart_trace_angular_scan_images_device": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, C.c_void_p, C.c_void_p]),
     "sart_trace_angular_scan_images": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, _dp, _dp]),
+    "sart_mass_scan_spectra_len": (C.c_size_t, [_i, _i]),
+    "sart_trace_mass_scan_spectra_device": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, _P(EnergyBands), C.c_void_p, C.c_void_p]),
+    "sart_trace_mass_scan_spectra": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, _P(EnergyBands), _dp, _dp]),
+    "sart_finalize_mass_scan_spectra_device": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, _P(EnergyBands), C.c_void_p, C.c_void_p,
+                                                         C.c_void_p]),
     "sart_energy_scan_len": (C.c_size_t, [_i]),
     "sart_trace_energy_scan_device": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, C.c_void_p]),
     "sart_trace_energy_scan": (C.c_int, [C.c_void_p, _P(TraceParams), _dp, _i, _dp]),
@@ -434,6 +456,8 @@ SART_HOST_SYMBOLS = {
     "sart_host_detector_tables": (C.c_int, [_dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _dp, _dp]),
     "sart_host_perform_axion_mass_scan": (C.c_int, [C.c_void_p, _dp, _i, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, _dp]),
     "sart_host_axion_mass_scan": (C.c_int, [C.c_void_p, _dp, _i, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _dp, _dp]),
+    "sart_host_axion_mass_scan_spectra": (C.c_int, [C.c_void_p, _dp, _i, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, _i, _i, _i,
+                                                    _dp, _dp, _dp, _dp, _dp, _dp]),
     "sart_host_angular_scan": (C.c_int, [C.c_void_p, _dp, _i, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _dp, _dp, _dp]),
     "sart_host_h5_reflectivity_info": (C.c_int, [C.c_char_p, _P(_i), _P(_i), _P(_i), _dp, _dp, _dp, _dp]),
     "sart_host_h5_read_reflectivity": (C.c_int, [C.c_char_p, _dp]),

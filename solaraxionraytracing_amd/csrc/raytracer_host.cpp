@@ -517,6 +517,39 @@ int sart_host_axion_mass_scan(sart_context* ctx, const double* masses_ev, int32_
   return 0;
 }
 
+int sart_host_axion_mass_scan_spectra(sart_context* ctx, const double* masses_ev, int32_t n_masses, uint64_t n_rays, uint64_t seed,
+                                      uint64_t ray_id_offset, uint32_t flags, int32_t e0, int32_t width, int32_t n_bands,
+                                      double* fluxes_out, double* flux_sq_out, double* n_passed_out, double* band_flux_out,
+                                      double* band_flux_sq_out, double* band_counts_out) {
+  if (!ctx || !masses_ev || n_masses < 1 || !fluxes_out || !band_flux_out || n_bands < 1 || n_bands > 31)
+    return fail(SART_ERR_INVALID_ARGUMENT, "sart_host_axion_mass_scan_spectra: bad argument");
+  sart_trace_params_t p;
+  std::memset(&p, 0, sizeof p);
+  p.n_rays = n_rays;
+  p.seed = seed;
+  p.ray_id_offset = ray_id_offset;
+  p.flags = flags;
+  const sart_energy_bands_t bands = {e0, width, n_bands};
+  std::vector<double> rows(sart_mass_scan_len(n_masses)), spec(sart_mass_scan_spectra_len(n_masses, n_bands));
+  if (int rc = sart_trace_mass_scan_spectra(ctx, &p, masses_ev, n_masses, &bands, rows.data(), spec.data())) { g_err = sart_last_error(); return rc; }
+  const size_t n_cells = static_cast<size_t>(n_bands) + 1;
+  for (int32_t i = 0; i < n_masses; ++i) {
+    const double* r = rows.data() + static_cast<size_t>(i) * SART_SCAN_ROW;
+    fluxes_out[i] = r[SART_SCAN_SUM_WEIGHTS];
+    if (flux_sq_out) flux_sq_out[i] = r[SART_SCAN_SUM_WEIGHTS_SQ];
+    if (n_passed_out) n_passed_out[i] = r[SART_SCAN_N_PASSED];
+    for (size_t b = 0; b < n_cells; ++b) {
+      const double* cell = spec.data() + (static_cast<size_t>(i) * n_cells + b) * SART_MSPEC_CELL;
+      band_flux_out[static_cast<size_t>(i) * n_cells + b] = cell[SART_MSPEC_SUM_WEIGHTS];
+      if (band_flux_sq_out) band_flux_sq_out[static_cast<size_t>(i) * n_cells + b] = cell[SART_MSPEC_SUM_WEIGHTS_SQ];
+    }
+  }
+  if (band_counts_out)
+    for (size_t b = 0; b < n_cells; ++b)
+      band_counts_out[b] = spec[(static_cast<size_t>(n_masses) * n_cells + b) * SART_MSPEC_CELL + SART_MSPEC_N_ON_DETECTOR];
+  return 0;
+}
+
 int sart_host_perform_axion_mass_scan(sart_context* ctx, const double* masses_ev, int32_t n_masses, uint64_t n_rays_per_mass,
                                       uint64_t seed, uint64_t ray_id_offset, uint32_t flags, double* fluxes_out) {
   // The meaning of rounds 1-3, back under the name of rounds 1-3 (round 4 had silently routed it through the fused scan): a host

@@ -38,6 +38,11 @@ bool launch_trace_mass_scan(const HotA& H, const HotB& HB, const DevBlob* blob, 
                             double* shared_row, int n_blocks, hipStream_t stream, int variant, bool fixed);
 void launch_finalize_scan(const void* in, double* out, int n_masses, const double* q_w, const double* q_w2, int shared_row,
                           void* check_dev, hipStream_t stream, uint32_t counter_slots);
+bool launch_trace_mass_scan_spectra(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, const ScanArgs& SC, double* rows,
+                                    double* shared_row, double* block0, double* counts, int n_blocks, hipStream_t stream, int variant, bool fixed);
+int mass_scan_spectra_blocks_per_cu(int variant);
+void launch_finalize_scan_bands(const void* rows, const void* shared_row, const void* in, double* out, const void* counts_in, double* counts_out,
+                                int n_masses, int n_cells, const double* q_w, const double* q_w2, void* check_dev, hipStream_t stream);
 void launch_trace_angular_scan(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, const AScanArgs& AN, double* rows,
                                double* shared_row, int n_blocks, hipStream_t stream, bool fast, bool fixed);
 int angular_scan_blocks_per_cu(bool fast);
@@ -297,6 +302,8 @@ struct sart_context {
   bool status_pending = false;
   // fused mass scan: per-workgroup per-mass partial sums, scratch accumulators of the blocking call
   DevBuf<double> d_scan_partials, d_scan, d_scan_fin;
+  DevBuf<double> d_mspec, d_mspec_fin;   // banded mass scan: the blocking form's buffers
+  int blocks_per_cu_mspec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   DevBuf<double> d_ascan_partials;   // fused angular scan: per-workgroup per-angle partial sums
   DevBuf<double> d_aimg_partials;    // ... with images: per-angle per-workgroup scalars
   DevBuf<double> d_aimg;             // ... scratch blocks of the blocking form
@@ -2827,11 +2834,43 @@ int scan_check(sart_context* c, const sart_trace_params_t* p, const double* mass
 // |m_gamma^2 - m_a^2| exactly as hoist_setup / sart_set_axion_mass compute it for the single-mass kernels
 double dm2_abs_of(const sart_context* c, double m_axion) { return std::fabs(c->params.gas_m_gamma_sq - m_axion * m_axion); }
 
-}  // namespace
+// The bands of a banded scan as the kernel takes them (ScanArgs::band_*).
+struct BandSpec {
+  int32_t e0;
+  uint32_t mul, window;
+  int32_t n_bands;
+};
+int bands_check(const sart_energy_bands_t* b) {
+  if (!b) return fail(SART_ERR_INVALID_ARGUMENT, "bands is NULL");
+  if (b->n_bands < 1 || b->n_bands > kScanBandsMax) return fail(SART_ERR_INVALID_ARGUMENT, "n_bands must be in [1, 31]");
+  if (b->width < 1) return fail(SART_ERR_INVALID_ARGUMENT, "the band width must be >= 1 energy index");
+  if (b->e0 < 0) return fail(SART_ERR_INVALID_ARGUMENT, "e0 must be >= 0");
+  return 0;
+}
+// A width beyond the index range bands like the range itself (every index from e0 on lies in band 0), so the kernel's numbers stay
+// small; the multiply-shift is held to the division for every index the context's tables can give.
+int bands_prepare(const sart_context* c, const sart_energy_bands_t* b, BandSpec& out) {
+  const uint32_t n_idx = static_cast<uint32_t>(c->n_energies) + 1u;   // indices 0 .. n_energies (the last: the X-ray test source)
+  const uint32_t w = std::min<uint32_t>(static_cast<uint32_t>(b->width), n_idx);
+  out.e0 = b->e0;
+  out.n_bands = b->n_bands;
+  out.window = static_cast<uint32_t>(b->n_bands) * w;
+  out.mul = static_cast<uint32_t>(((uint64_t(1) << 31) + w - 1u) / w);
+  for (uint32_t d = 0; d < std::min(out.window, n_idx); ++d)
+    if (static_cast<uint32_t>((uint64_t(2u * d + 1u) * out.mul) >> 32) != d / w)
+      return fail(SART_ERR_UNSUPPORTED, "banded mass scan: the energy table is too long for this band width");
+  return 0;
+}
 
-int sart_trace_mass_scan_device(sart_context* c, const sart_trace_params_t* p, const double* masses, int32_t n_masses, double* scan_dev) {
+// The fused mass scan; with `bands` the banded form, which also fills `spectra_dev`.
+int trace_mass_scan_impl(sart_context* c, const sart_trace_params_t* p, const double* masses, int32_t n_masses, const sart_energy_bands_t* bands,
+                         double* scan_dev, double* spectra_dev) {
   if (int rc = scan_check(c, p, masses, n_masses)) return rc;
   if (!scan_dev) return fail(SART_ERR_INVALID_ARGUMENT, "scan accumulator is NULL");
+  if (bands) {
+    if (int rc = bands_check(bands)) return rc;
+    if (!spectra_dev) return fail(SART_ERR_INVALID_ARGUMENT, "spectra accumulator is NULL");
+  }
   SART_HIP(hipSetDevice(c->device));
   if (int rc = refresh_derived(c)) return rc;
   if (int rc = sync_blob(c)) return rc;
@@ -2847,30 +2886,56 @@ int sart_trace_mass_scan_device(sart_context* c, const sart_trace_params_t* p, c
   if (int rc = make_args(c, &q, a)) return rc;
   a.fx_scale_w = a.fx_scale_w2 = 0.0;
   const bool fixed = c->accum_mode == SART_ACCUM_FIXED64;
-  if (!p->accumulate) SART_HIP(hipMemsetAsync(scan_dev, 0, sart_mass_scan_len(n_masses) * sizeof(double), c->stream));
-  if (p->n_rays == 0) return 0;
+  BandSpec bs = {0, 0u, 0u, 0};
+  if (bands)
+    if (int rc = bands_prepare(c, bands, bs)) return rc;
   const int variant = hist_variant_of(c);
   if (variant != 1 && variant != 2 && variant != 3 && variant != 6) return fail(SART_ERR_INTERNAL, "no scan kernel for this variant");
-  if (c->blocks_per_cu_hist[variant] == 0) {
-    c->blocks_per_cu_hist[variant] = std::max(1, histogram_blocks_per_cu(variant));
-    if (c->knobs.hist_blocks_per_cu > 0) c->blocks_per_cu_hist[variant] = c->knobs.hist_blocks_per_cu;
+  int& blocks_per_cu = bands ? c->blocks_per_cu_mspec[variant] : c->blocks_per_cu_hist[variant];
+  if (blocks_per_cu == 0) {
+    blocks_per_cu = std::max(1, bands ? mass_scan_spectra_blocks_per_cu(variant) : histogram_blocks_per_cu(variant));
+    if (c->knobs.hist_blocks_per_cu > 0) blocks_per_cu = c->knobs.hist_blocks_per_cu;
   }
-  // ray indices inside one launch are 32-bit: pieces of at most 2^31 rays; every piece runs once per group of masses
+  // ray indices inside one launch are 32-bit: pieces of at most 2^31 rays (banded: 2^30, see below); every piece runs once per group of masses
+  const uint64_t piece = bands ? (1ull << 30) : (1ull << 31);
+  if (bands && fixed) {
+    // A band cell of a workgroup can receive every ray the workgroup traces in one launch (sart_kernels.hip: BANDS): chunks of 256
+    // ids go round the grid's waves, 16 waves per workgroup.  Sum of w: < 2^(63 - headroom) quanta per ray; sum of w^2: < 2^39.
+    const uint64_t room = std::min<uint64_t>(1ull << 23, 1ull << (c->headroom_bits - 1));
+    for (uint64_t done = 0; done < p->n_rays;) {
+      const uint64_t n = std::min<uint64_t>(p->n_rays - done, piece);
+      const uint64_t n_chunks = (((p->ray_id_offset + done) & 255u) + n + 255u) >> 8;
+      const uint64_t waves = static_cast<uint64_t>(grid_for(n, c->n_cu, blocks_per_cu, histogram_block_of(variant))) * 16u;
+      if ((n_chunks + waves - 1) / waves * 16u * 256u > room)
+        return fail(SART_ERR_INVALID_ARGUMENT, "FIXED64 banded mass scan: one workgroup would trace more rays in a launch than a band cell has "
+                                               "room for at this headroom (2^(headroom_bits - 1), at most 2^23): use a larger headroom or "
+                                               "split the rays over accumulating calls");
+      done += n;
+    }
+  }
+  if (!p->accumulate) {
+    SART_HIP(hipMemsetAsync(scan_dev, 0, sart_mass_scan_len(n_masses) * sizeof(double), c->stream));
+    if (bands) SART_HIP(hipMemsetAsync(spectra_dev, 0, sart_mass_scan_spectra_len(n_masses, bands->n_bands) * sizeof(double), c->stream));
+  }
+  if (p->n_rays == 0) return 0;
+  const size_t n_cells = bands ? static_cast<size_t>(bands->n_bands) + 1u : 0u;
   for (uint64_t done = 0; done < p->n_rays;) {
-    const uint64_t n = std::min<uint64_t>(p->n_rays - done, 1ull << 31);
+    const uint64_t n = std::min<uint64_t>(p->n_rays - done, piece);
     a.n_rays = n;
     a.ray_id_offset = p->ray_id_offset + done;
-    const int n_blocks = grid_for(n, c->n_cu, c->blocks_per_cu_hist[variant], histogram_block_of(variant));
+    const int n_blocks = grid_for(n, c->n_cu, blocks_per_cu, histogram_block_of(variant));
     if (c->d_partials.n < static_cast<size_t>(n_blocks) * SART_ACC_COUNT) {
       SART_HIP(hipStreamSynchronize(c->stream));
       const size_t rows = std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4);
       if (int rc = c->d_partials.resize(rows * SART_ACC_COUNT)) return rc;
     }
-    const size_t scan_partials = static_cast<size_t>(n_blocks) * kScanMaxMasses * kScanPartialSlots;
-    if (c->d_scan_partials.n < scan_partials) {
+    // (banded: a workgroup's cells behind the plain rows; plain stores cover every slot the folds read - no memset - and the scratch
+    // is the context's, on the context's stream)
+    const size_t per_block = static_cast<size_t>(kScanMaxMasses * kScanPartialSlots) + (bands ? static_cast<size_t>(kScanBandSlots) : 0u);
+    if (c->d_scan_partials.n < static_cast<size_t>(n_blocks) * per_block) {
       SART_HIP(hipStreamSynchronize(c->stream));
       const size_t rows = std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4);
-      if (int rc = c->d_scan_partials.resize(rows * kScanMaxMasses * kScanPartialSlots)) return rc;
+      if (int rc = c->d_scan_partials.resize(rows * per_block)) return rc;
     }
     a.partials = c->d_partials.p;
     for (int32_t k0 = 0; k0 < n_masses; k0 += kScanMaxMasses) {
@@ -2878,6 +2943,12 @@ int sart_trace_mass_scan_device(sart_context* c, const sart_trace_params_t* p, c
       std::memset(&sc, 0, sizeof sc);
       sc.n_masses = std::min<int32_t>(kScanMaxMasses, n_masses - k0);
       sc.partials = c->d_scan_partials.p;
+      if (bands) {
+        sc.n_bands = bs.n_bands;
+        sc.m[0].aux[0] = static_cast<uint32_t>(bs.e0);
+        sc.m[0].aux[1] = bs.mul;
+        sc.m[1].aux[0] = bs.window;
+      }
       for (int k = 0; k < sc.n_masses; ++k) {
         ScanMass& m = sc.m[k];
         m.dm2_abs = dm2_abs_of(c, masses[k0 + k]);
@@ -2893,14 +2964,34 @@ int sart_trace_mass_scan_device(sart_context* c, const sart_trace_params_t* p, c
       double* const shared = (k0 == 0) ? scan_dev + static_cast<size_t>(n_masses) * SART_SCAN_ROW : nullptr;   // counters: once per piece
       {
         TimedLaunch tl(c);
-        if (!launch_trace_mass_scan(c->hot, c->hotb, c->d_blob.p, a, sc, rows, shared, n_blocks, c->stream, variant, fixed))
-          return fail(SART_ERR_INTERNAL, "no scan kernel for this variant");
+        const bool ok = bands ? launch_trace_mass_scan_spectra(c->hot, c->hotb, c->d_blob.p, a, sc, rows, shared,
+                                                               spectra_dev + static_cast<size_t>(k0) * n_cells * SART_MSPEC_CELL,
+                                                               shared ? spectra_dev + static_cast<size_t>(n_masses) * n_cells * SART_MSPEC_CELL : nullptr,
+                                                               n_blocks, c->stream, variant, fixed)
+                              : launch_trace_mass_scan(c->hot, c->hotb, c->d_blob.p, a, sc, rows, shared, n_blocks, c->stream, variant, fixed);
+        if (!ok) return fail(SART_ERR_INTERNAL, "no scan kernel for this variant");
       }
       SART_HIP(hipGetLastError());
     }
     done += n;
   }
   return 0;
+}
+
+}  // namespace
+
+size_t sart_mass_scan_spectra_len(int32_t n_masses, int32_t n_bands) {
+  return (static_cast<size_t>(n_masses) + 1u) * (static_cast<size_t>(n_bands) + 1u) * static_cast<size_t>(SART_MSPEC_CELL);
+}
+
+int sart_trace_mass_scan_device(sart_context* c, const sart_trace_params_t* p, const double* masses, int32_t n_masses, double* scan_dev) {
+  return trace_mass_scan_impl(c, p, masses, n_masses, nullptr, scan_dev, nullptr);
+}
+
+int sart_trace_mass_scan_spectra_device(sart_context* c, const sart_trace_params_t* p, const double* masses, int32_t n_masses,
+                                        const sart_energy_bands_t* bands, double* scan_dev, double* spectra_dev) {
+  if (!bands) return fail(SART_ERR_INVALID_ARGUMENT, "bands is NULL");
+  return trace_mass_scan_impl(c, p, masses, n_masses, bands, scan_dev, spectra_dev);
 }
 
 int sart_finalize_mass_scan_device(sart_context* c, const sart_trace_params_t* p, const double* masses, int32_t n_masses,
@@ -2944,6 +3035,65 @@ int sart_trace_mass_scan(sart_context* c, const sart_trace_params_t* p, const do
     src = c->d_scan_fin.p;
   }
   SART_HIP(hipMemcpyAsync(out_host, src, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  SART_HIP(hipStreamSynchronize(c->stream));
+  return status_take(c);
+}
+
+int sart_finalize_mass_scan_spectra_device(sart_context* c, const sart_trace_params_t* p, const double* masses, int32_t n_masses,
+                                           const sart_energy_bands_t* bands, const void* scan_raw_dev, const void* spectra_raw_dev, double* out_dev) {
+  if (int rc = scan_check(c, p, masses, n_masses)) return rc;
+  if (int rc = bands_check(bands)) return rc;
+  if (!scan_raw_dev || !spectra_raw_dev || !out_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (static_cast<const void*>(out_dev) == scan_raw_dev || static_cast<const void*>(out_dev) == spectra_raw_dev)
+    return fail(SART_ERR_INVALID_ARGUMENT, "the output needs an array of its own (the spectra are held to the raw scan rows)");
+  SART_HIP(hipSetDevice(c->device));
+  if (int rc = refresh_derived(c)) return rc;
+  if (int rc = sync_blob(c)) return rc;
+  if (int rc = status_ensure(c)) return rc;
+  const size_t n_cells = static_cast<size_t>(bands->n_bands) + 1u;
+  const long long* const rows = static_cast<const long long*>(scan_raw_dev);
+  const long long* const spec = static_cast<const long long*>(spectra_raw_dev);
+  double* const spec_out = out_dev + sart_mass_scan_len(n_masses);
+  for (int32_t k0 = 0; k0 < n_masses; k0 += kScanMaxMasses) {
+    const int n = std::min<int32_t>(kScanMaxMasses, n_masses - k0);
+    double q_w[kScanMaxMasses], q_w2[kScanMaxMasses];
+    for (int k = 0; k < n; ++k) {
+      QuantaExp qe;
+      if (int rc = quanta_exp_of(c, weight_bound_of(c, p->flags, dm2_abs_of(c, masses[k0 + k])), qe)) return rc;
+      q_w[k] = std::ldexp(1.0, qe.w);
+      q_w2[k] = std::ldexp(1.0, qe.w2);
+    }
+    const bool last = k0 + n == n_masses;   // the counts block sits behind the last group
+    const size_t at = static_cast<size_t>(k0) * n_cells * SART_MSPEC_CELL, counts_at = static_cast<size_t>(n_masses) * n_cells * SART_MSPEC_CELL;
+    launch_finalize_scan_bands(rows + static_cast<size_t>(k0) * SART_SCAN_ROW, rows + static_cast<size_t>(n_masses) * SART_SCAN_ROW, spec + at,
+                               spec_out + at, last ? spec + counts_at : nullptr, last ? spec_out + counts_at : nullptr, n,
+                               static_cast<int>(n_cells), q_w, q_w2, c->d_status.p, c->stream);
+    SART_HIP(hipGetLastError());
+  }
+  return sart_finalize_mass_scan_device(c, p, masses, n_masses, scan_raw_dev, out_dev);   // the rows, their checks, the status copy
+}
+
+int sart_trace_mass_scan_spectra(sart_context* c, const sart_trace_params_t* p, const double* masses, int32_t n_masses,
+                                 const sart_energy_bands_t* bands, double* scan_out_host, double* spectra_out_host) {
+  if (int rc = scan_check(c, p, masses, n_masses)) return rc;
+  if (int rc = bands_check(bands)) return rc;
+  if (!scan_out_host || !spectra_out_host) return fail(SART_ERR_INVALID_ARGUMENT, "output is NULL");
+  SART_HIP(hipSetDevice(c->device));
+  const size_t len = sart_mass_scan_len(n_masses), slen = sart_mass_scan_spectra_len(n_masses, bands->n_bands);
+  if (int rc = c->d_scan.resize(len)) return rc;
+  if (int rc = c->d_mspec.resize(slen)) return rc;
+  sart_trace_params_t q = *p;
+  q.accumulate = 0;   // the blocking form has no accumulator the caller could add into
+  if (int rc = sart_trace_mass_scan_spectra_device(c, &q, masses, n_masses, bands, c->d_scan.p, c->d_mspec.p)) return rc;
+  const double *src = c->d_scan.p, *ssrc = c->d_mspec.p;
+  if (c->accum_mode == SART_ACCUM_FIXED64) {
+    if (int rc = c->d_mspec_fin.resize(len + slen)) return rc;
+    if (int rc = sart_finalize_mass_scan_spectra_device(c, p, masses, n_masses, bands, c->d_scan.p, c->d_mspec.p, c->d_mspec_fin.p)) return rc;
+    src = c->d_mspec_fin.p;
+    ssrc = c->d_mspec_fin.p + len;
+  }
+  SART_HIP(hipMemcpyAsync(scan_out_host, src, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  SART_HIP(hipMemcpyAsync(spectra_out_host, ssrc, slen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   SART_HIP(hipStreamSynchronize(c->stream));
   return status_take(c);
 }

@@ -262,15 +262,27 @@ constexpr int kScanLanes = 32;
 struct ScanMass {
   double dm2_abs;                 // |m_gamma^2 - m_a^2| in eV^2 (host: the same IEEE subtraction the single-mass kernel performs)
   double fx_scale_w, fx_scale_w2; // SART_ACCUM_FIXED64: 1 / quantum of the weights and of the squared weights of THIS mass
-  double _pad;
+  // Two spare words per entry.  The banded scan (include/sart.h: sart_trace_mass_scan_spectra) keeps its band table in those of the
+  // first two entries - the argument block keeps its size, and with it the code of every kernel that shares it: m[0].aux = {band_e0,
+  // band_mul}, m[1].aux = {band_window, 0}.  The cell index of the accumulators means "energy band" there: band = (e - band_e0) / width
+  // for (uint32_t)(e - band_e0) < band_window = n_bands width, else the outside cell n_bands; the division is
+  // __umulhi(2 d + 1, band_mul) with band_mul = ceil(2^31 / width), which the host checks against d / width for every d an energy
+  // index of the context can give (sart_api.hip: bands_prepare).  Zero in every other launch.
+  uint32_t aux[2];
 };
 struct ScanArgs {
-  int32_t n_masses, _pad;         // masses of this launch (<= kScanMaxMasses); 0 in every launch that is not a scan
-  double* partials;               // [n_blocks][kScanMaxMasses][4] per-workgroup {sum w, sum w^2, rays whose weight vanishes for this mass only, 0}
+  int32_t n_masses;               // masses of this launch (<= kScanMaxMasses); 0 in every launch that is not a scan
+  int32_t n_bands;                // banded scan: its bands (1 .. kScanBandsMax); 0 in every other launch
+  // [n_blocks][kScanMaxMasses][4] per-workgroup {sum w, sum w^2, rays whose weight vanishes for this mass only, 0}; banded scan: behind
+  // them [n_blocks][kScanMaxMasses + 1][2 kScanLanes], a workgroup's cells per mass, then its per-band counts
+  double* partials;
   ScanMass m[kScanMaxMasses];
 };
-static_assert(sizeof(ScanMass) == 32 && sizeof(ScanArgs) == 16 + 32 * kScanMaxMasses, "the kernel re-reads ScanArgs with scalar loads at these offsets");
+static_assert(sizeof(ScanMass) == 32 && offsetof(ScanMass, aux) == 24 && sizeof(ScanArgs) == 16 + 32 * kScanMaxMasses,
+              "the kernel re-reads ScanArgs with scalar loads at these offsets");
 constexpr int kScanPartialSlots = 4;
+constexpr int kScanBandSlots = (kScanMaxMasses + 1) * 2 * kScanLanes;   // banded scan: partial slots of one workgroup behind the plain ones
+constexpr int kScanBandsMax = kScanLanes - 1;   // bands of a banded scan: the 32 cells of a mass less the outside cell
 
 // Fused angular scan (include/sart.h: sart_trace_angular_scan): the telescope's angles enter a ray at the transformation into the
 // telescope's frame (raytracer.nim:1878-1899) and nowhere before it, so trace_angular_scan_kernel samples a ray and takes it through

@@ -751,6 +751,40 @@ class RayTracer:
         _lib.check(self.lib.sart_finalize_mass_scan_device(self.handle, C.byref(params), _lib.as_dp(masses), masses.size,
                                                            C.c_void_p(raw_ptr), C.c_void_p(out_ptr if out_ptr is not None else raw_ptr)))
 
+    # -- fused axion-mass scan with energy bands (include/sart.h "fused axion-mass scan with energy bands") ----
+    def trace_mass_scan_spectra(self, masses_ev, bands, n_rays: int, seed: int = 299792458, ray_id_offset: int = 0,
+                                flags: int | None = None):
+        """trace_mass_scan with every mass's sums split by energy band.  ``bands`` = (e0, width, n_bands) in energy-index space
+        (energy_bands() makes them from keV).  Returns (per-mass dict, shared-counter dict, spectra dict: ``SUM_WEIGHTS`` and
+        ``SUM_WEIGHTS_SQ`` [n_masses][n_bands + 1] - the last cell is everything outside the window - and ``N_ON_DETECTOR``
+        [n_bands + 1])."""
+        masses = np.ascontiguousarray(masses_ev, dtype=np.float64)
+        b = _lib.EnergyBands(*[int(v) for v in bands])
+        p = self.trace_params(n_rays, seed, ray_id_offset, flags)
+        out = np.empty(mass_scan_len(masses.size))
+        spec = np.empty(_lib.mass_scan_spectra_len(masses.size, max(b.n_bands, 0)))
+        _lib.check(self.lib.sart_trace_mass_scan_spectra(self.handle, C.byref(p), _lib.as_dp(masses), masses.size, C.byref(b),
+                                                         _lib.as_dp(out), _lib.as_dp(spec)))
+        return split_mass_scan(out, masses.size) + (split_mass_scan_spectra(spec, masses.size, b.n_bands),)
+
+    def trace_mass_scan_spectra_device(self, params: TraceParams, masses_ev, bands, scan_acc_ptr: int, spectra_ptr: int):
+        """Asynchronous form: adds into a device scan accumulator of mass_scan_len(n) slots and a device spectra buffer of
+        mass_scan_spectra_len(n, n_bands) slots (raw int64 in fixed64 mode)."""
+        masses = np.ascontiguousarray(masses_ev, dtype=np.float64)
+        b = _lib.EnergyBands(*[int(v) for v in bands])
+        _lib.check(self.lib.sart_trace_mass_scan_spectra_device(self.handle, C.byref(params), _lib.as_dp(masses), masses.size, C.byref(b),
+                                                                C.c_void_p(scan_acc_ptr), C.c_void_p(spectra_ptr)))
+
+    def finalize_mass_scan_spectra_device(self, params: TraceParams, masses_ev, bands, scan_raw_ptr: int, spectra_raw_ptr: int,
+                                          out_ptr: int):
+        """Raw FIXED64 scan rows and spectra (device) -> doubles in ``out_ptr`` (device; mass_scan_len(n) doubles, then
+        mass_scan_spectra_len(n, n_bands); not in place).  Asynchronous; what the conversion finds wrong (a wrapped slot, cells that
+        do not add up to their row, unresolved weights) is raised by the next ``synchronize()``."""
+        masses = np.ascontiguousarray(masses_ev, dtype=np.float64)
+        b = _lib.EnergyBands(*[int(v) for v in bands])
+        _lib.check(self.lib.sart_finalize_mass_scan_spectra_device(self.handle, C.byref(params), _lib.as_dp(masses), masses.size, C.byref(b),
+                                                                   C.c_void_p(scan_raw_ptr), C.c_void_p(spectra_raw_ptr), C.c_void_p(out_ptr)))
+
     # -- fused energy scan (X-ray test source; include/sart.h "fused energy scan") --------------
     def trace_energy_scan(self, energies_kev, n_rays: int, seed: int = 299792458, ray_id_offset: int = 0, flags: int | None = None):
         """Every ray of [ray_id_offset, ray_id_offset + n_rays) traced ONCE and weighed at every X-ray energy (keV) of the test
@@ -1044,6 +1078,53 @@ def split_mass_scan(acc: np.ndarray, n_masses: int):
     return per_mass, shared
 
 
+def split_mass_scan_spectra(spec: np.ndarray, n_masses: int, n_bands: int) -> dict:
+    """Dict of ``SUM_WEIGHTS`` / ``SUM_WEIGHTS_SQ`` [n_masses][n_bands + 1] and ``N_ON_DETECTOR`` [n_bands + 1] from a finalized
+    spectra buffer of a banded mass scan (the last cell of each row: everything outside the window)."""
+    cells = np.asarray(spec, dtype=np.float64).reshape(n_masses + 1, n_bands + 1, _lib.MSPEC_CELL)
+    out = {k: cells[:n_masses, :, i].copy() for k, i in _lib.MSPEC.items()}
+    out["N_ON_DETECTOR"] = cells[n_masses, :, _lib.MSPEC_COUNTS["N_ON_DETECTOR"]].copy()
+    return out
+
+
+def band_of_energy_index(e_idx, bands) -> np.ndarray:
+    """The cell of a banded mass scan that energy index ``e_idx`` (array) belongs to: (e - e0) // width inside the window
+    [e0, e0 + n_bands width), n_bands (the outside cell) otherwise - the rule of include/sart.h, in numpy."""
+    e0, width, n_bands = (int(v) for v in bands)
+    e = np.asarray(e_idx, dtype=np.int64)
+    inside = (e >= e0) & (e < e0 + n_bands * width)
+    return np.where(inside, (e - e0) // width, n_bands).astype(np.int64)
+
+
+def energy_bands(energies, e_min_kev: float, e_max_kev: float, n_bands: int):
+    """Bands of a banded mass scan from a request in keV.  ``energies``: the context's energy table (FullSetup.energies), a uniform
+    grid of points with step dE; index e stands for the cell [energies[e] - dE / 2, energies[e] + dE / 2).  Returns
+    ((e0, width, n_bands), edges in keV [n_bands + 1]).  ValueError for a request the index grid cannot represent: e_min_kev must
+    be a cell edge, (e_max_kev - e_min_kev) / n_bands a whole number >= 1 of cells, the window inside the table, n_bands in
+    [1, 31]."""
+    en = np.asarray(energies, dtype=np.float64)
+    if en.ndim != 1 or en.size < 2:
+        raise ValueError("energy_bands: the energy table needs at least two points")
+    step = (en[-1] - en[0]) / (en.size - 1)
+    if not step > 0 or np.abs(np.diff(en) - step).max() > 1e-9 * step:
+        raise ValueError("energy_bands: the energy table is not a uniform grid")
+    if not 1 <= int(n_bands) <= _lib.MSPEC_MAX_BANDS or int(n_bands) != n_bands:
+        raise ValueError("energy_bands: n_bands must be a whole number in [1, %d]" % _lib.MSPEC_MAX_BANDS)
+    n_bands = int(n_bands)
+    if not (np.isfinite(e_min_kev) and np.isfinite(e_max_kev) and e_max_kev > e_min_kev):
+        raise ValueError("energy_bands: needs finite e_min_kev < e_max_kev")
+    lo = en[0] - 0.5 * step                    # lower edge of cell 0
+    f0 = (e_min_kev - lo) / step
+    fw = (e_max_kev - e_min_kev) / (step * n_bands)
+    e0, width = int(round(f0)), int(round(fw))
+    if abs(f0 - e0) > 1e-6 or abs(fw - width) > 1e-6:
+        raise ValueError("energy_bands: [%r, %r] keV in %d bands is not a whole number of energy cells (cell edges at %r + k x %r keV)"
+                         % (float(e_min_kev), float(e_max_kev), n_bands, float(lo), float(step)))
+    if e0 < 0 or width < 1 or e0 + n_bands * width > en.size:
+        raise ValueError("energy_bands: the window leaves the energy table ([%r, %r] keV)" % (float(lo), float(lo + step * en.size)))
+    return (e0, width, n_bands), lo + step * (e0 + width * np.arange(n_bands + 1))
+
+
 def angular_scan_len(n_angles: int) -> int:
     """sart_angular_scan_len: 8-byte slots of an angular-scan accumulator."""
     return (int(n_angles) + 1) * _lib.ASCAN_ROW
@@ -1093,14 +1174,25 @@ def calculateFluxFractions(tracer: RayTracer, n_rays: int = 1_000_000, seed: int
 
 
 def performAxionMassScan(tracer: RayTracer, masses_ev, n_rays_per_mass: int = 1_000_000, seed: int = 299792458,
-                         flags: int | None = None, ray_id_offset: int = 0, errors: bool = False):
+                         flags: int | None = None, ray_id_offset: int = 0, errors: bool = False, bands=None):
     """m_a scan (BASELINE configs[4]) through the C++ host driver: flux (sum of weights) per axion mass.  Gas stage: the
     fused scan kernel - every ray of [ray_id_offset, ray_id_offset + n_rays_per_mass) is traced once and weighed for every
-    mass (common random numbers).  ``errors``: also return sqrt(sum of squared weights) and the passed-ray counts."""
+    mass (common random numbers).  ``errors``: also return sqrt(sum of squared weights) and the passed-ray counts.
+    ``bands`` = (e0, width, n_bands) (energy_bands()): the banded scan (gas stage only) - returns a dict with ``flux``, ``sigma``,
+    ``n_passed`` per mass, the per-mass spectra ``band_flux`` and ``band_sigma`` = sqrt(sum of squared weights)
+    [n_masses][n_bands + 1] (last cell: outside the window) and ``band_counts`` [n_bands + 1], the rays per band on the detector."""
     host = _lib.load_host()
     masses = np.ascontiguousarray(masses_ev, dtype=np.float64)
     fluxes, sq, n_pass = np.empty_like(masses), np.empty_like(masses), np.empty_like(masses)
     fl = tracer.full.flags if flags is None else flags
+    if bands is not None:
+        e0, width, n_bands = (int(v) for v in bands)
+        cells = max(n_bands, 0) + 1
+        bf, bsq, bn = np.empty((masses.size, cells)), np.empty((masses.size, cells)), np.empty(cells)
+        _lib.check(host.sart_host_axion_mass_scan_spectra(tracer.handle, _lib.as_dp(masses), masses.size, n_rays_per_mass, seed,
+                                                          ray_id_offset, fl, e0, width, n_bands, _lib.as_dp(fluxes), _lib.as_dp(sq),
+                                                          _lib.as_dp(n_pass), _lib.as_dp(bf), _lib.as_dp(bsq), _lib.as_dp(bn)), host=True)
+        return dict(flux=fluxes, sigma=np.sqrt(sq), n_passed=n_pass, band_flux=bf, band_sigma=np.sqrt(bsq), band_counts=bn)
     _lib.check(host.sart_host_axion_mass_scan(tracer.handle, _lib.as_dp(masses), masses.size, n_rays_per_mass, seed,
                                               ray_id_offset, fl, _lib.as_dp(fluxes), _lib.as_dp(sq), _lib.as_dp(n_pass)), host=True)
     return (fluxes, np.sqrt(sq), n_pass) if errors else fluxes

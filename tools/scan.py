@@ -39,6 +39,10 @@ def main():
     ap.add_argument("--numAngularScanPoints", type=int, default=16)
     ap.add_argument("--points", type=int, default=32, help="mass scan points")
     ap.add_argument("--massMin", type=float, default=0.0)
+    ap.add_argument("--bands", type=int, default=0, metavar="N",
+                    help="mass (fused): also every mass's signal in N energy bands (1 .. 31) over the whole energy table "
+                         "(sart_trace_mass_scan_spectra), written beside --out as <out>.spectra.csv; both raw buffers are reduced over the "
+                         "ranks (int64 when fixed64)")
     ap.add_argument("--massMax", type=float, default=0.02, help="eV; the literal-units gas stage has m_gamma = 0.008235 eV")
     ap.add_argument("--rays", type=float, default=1e7, help="rays per scan point")
     ap.add_argument("--chip", type=float, default=100.0, help="chip size in mm for the angular scan (SURVEY App. C)")
@@ -105,7 +109,12 @@ def main():
         flags = 0
         xs = np.linspace(args.massMin, args.massMax, args.points)
     fused = args.mode == "mass" and not args.host_loop
+    if args.bands and not fused:
+        raise SystemExit("--bands goes with the fused mass scan")
+    if args.bands and not 1 <= args.bands <= L.MSPEC_MAX_BANDS:
+        raise SystemExit("--bands must lie in [1, %d]" % L.MSPEC_MAX_BANDS)
     errs = None
+    band_spec = None
     if args.mode == "angular" and args.fused and args.shard == "rays":
         # Fused angular scan, rays sharded: rank r turns ray ids [lo_r, hi_r) through ALL angles into a device scan accumulator;
         # ONE reduce of 8 (points + 1) slots over the ranks (int64 when fixed64).
@@ -172,16 +181,39 @@ def main():
             rt.set_stream(stream.cuda_stream)
             rt.set_accumulation_mode(args.accumulation)
             p = rt.trace_params(hi - lo, ray_id_offset=lo, flags=flags, accumulate=True)
-            rt.trace_mass_scan_device(p, xs, acc.data_ptr())
+            if args.bands:   # the whole table in N bands of the largest whole width (what is left at the top: the outside cell)
+                en = np.asarray(full.energies, dtype=np.float64)
+                step = (en[-1] - en[0]) / (en.size - 1)
+                e_lo = en[0] - 0.5 * step
+                band_spec, band_edges = sa.energy_bands(en, e_lo, e_lo + step * (en.size // args.bands) * args.bands, args.bands)
+                spec = torch.zeros(L.mass_scan_spectra_len(len(xs), args.bands), dtype=torch.float64, device=acc.device)
+                rt.trace_mass_scan_spectra_device(p, xs, band_spec, acc.data_ptr(), spec.data_ptr())
+            else:
+                rt.trace_mass_scan_device(p, xs, acc.data_ptr())
             red = acc if use_cuda else acc.cpu()
             D.reduce_accumulator(red, dst=0, fixed64=fixed64)
+            if args.bands:
+                red_s = spec if use_cuda else spec.cpu()
+                D.reduce_accumulator(red_s, dst=0, fixed64=fixed64)   # int64 sums of the raw cells in fixed64
             if fixed64:      # raw integers -> doubles (the quanta are a function of the inputs: the same on every rank)
                 if not use_cuda:
                     acc.copy_(red)
-                rt.finalize_mass_scan_device(p, xs, acc.data_ptr())
-                rt.synchronize()   # raises if the integers did not resolve the weights / a slot wrapped
+                if args.bands:
+                    if not use_cuda:
+                        spec.copy_(red_s)
+                    fin = torch.zeros(acc.numel() + spec.numel(), dtype=torch.float64, device=acc.device)
+                    rt.finalize_mass_scan_spectra_device(p, xs, band_spec, acc.data_ptr(), spec.data_ptr(), fin.data_ptr())
+                    rt.synchronize()   # raises if a slot wrapped, the cells do not add up to their rows, or the weights are unresolved
+                    acc, red_s = fin[:acc.numel()], fin[acc.numel():]
+                else:
+                    rt.finalize_mass_scan_device(p, xs, acc.data_ptr())
+                    rt.synchronize()   # raises if the integers did not resolve the weights / a slot wrapped
                 red = acc
+            else:
+                rt.synchronize()
             red = red.cpu()
+            if args.bands:
+                bands_out = sa.split_mass_scan_spectra(red_s.cpu().numpy(), len(xs), args.bands)
         per_mass, shared = sa.split_mass_scan(red.numpy(), len(xs))
         curve = per_mass["SUM_WEIGHTS"]
         errs = np.sqrt(per_mass["SUM_WEIGHTS_SQ"])
@@ -262,6 +294,16 @@ def main():
                     f.write("%.8g,%.17g,%.8f,%s\n" % (a, c, r, "%.6g" % errs[i] if errs is not None else ""))
                 print("mass scan: m_a", np.round(xs, 5).tolist())
                 print("relative flux", np.round(rel, 4).tolist())
+        if band_spec is not None:
+            path = os.path.splitext(args.out)[0] + ".spectra.csv"
+            with open(path, "w") as f:   # per mass: the bands, then one row (edges nan) for everything outside them
+                f.write("m_a [eV],band,E min [keV],E max [keV],flux,flux error,axions on detector\n")
+                e_min, e_max = np.append(band_edges[:-1], np.nan), np.append(band_edges[1:], np.nan)
+                for k, a in enumerate(xs):
+                    for b in range(args.bands + 1):
+                        f.write("%.8g,%d,%.10g,%.10g,%.17g,%.6g,%d\n" % (a, b, e_min[b], e_max[b], bands_out["SUM_WEIGHTS"][k, b],
+                                                                        np.sqrt(bands_out["SUM_WEIGHTS_SQ"][k, b]), int(bands_out["N_ON_DETECTOR"][b])))
+            print("wrote", path)
         print("wrote", args.out)
     if world > 1:
         torch.distributed.barrier()
