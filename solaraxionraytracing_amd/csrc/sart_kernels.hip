@@ -474,7 +474,9 @@ struct RayState {
   int shell;         // hit layer
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
+// The wave's sum of v in T's own arithmetic: double, long long, or unsigned long long where the values may have wrapped (modulo 2^64)
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
@@ -487,11 +489,7 @@ __device__ __forceinline__ long long to_fixed(double x, double scale) {
   constexpr double kMagic = 6755399441055744.0;   // 1.5 * 2^52
   return __double_as_longlong(fma(x, scale, kMagic)) - __double_as_longlong(kMagic);
 }
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
+__device__ __forceinline__ long long wave_sum_i64(long long v) { return wave_sum(v); }
 // 8-byte slots of the accumulators hold doubles (SART_ACCUM_F64) or int64 bit patterns (SART_ACCUM_FIXED64)
 __device__ __forceinline__ void atomic_add_slot_i64(double* slot, long long v) {
   atomicAdd(reinterpret_cast<unsigned long long*>(slot), (unsigned long long)v);   // global_atomic_add_x2, no return
@@ -3400,79 +3398,152 @@ __global__ __launch_bounds__(BLOCK) void ascan_images_kernel(HotA H, const DevBl
 }
 
 
+// What the finalize kernels report about a raw SART_ACCUM_FIXED64 accumulator (OR-ed into a word of the context that the next
+// sart_synchronize reads): integers that no longer mean what they should.
+constexpr uint32_t kFixedStatusWrapped = 1u;       // a slot is negative or >= 2^62: wrapped, or about to (weights and counts are >= 0)
+constexpr uint32_t kFixedStatusUnresolved = 2u;    // the accumulated weights average below 2^12 quanta per passed ray
+constexpr uint32_t kFixedStatusNotConserved = 4u;  // pixels (+ outside) / radial / energy weight bins do not add up to SUM_WEIGHTS: a slot wrapped
+
+// ---- The limb arithmetic of every fold and finalize ("One fold tree, one limb arithmetic") ----
+// A two-limb sum is value = hi * 2^40 + lo (include/sart.h), lo in the slot SART_*_SUM_*, hi in its *_HI slot.  FIXED = false is the
+// f64 form of the same step: no limbs, hi stays 0.
+constexpr long long kLimbMask = (1ll << kFixedLimbBits) - 1;
+template <bool FIXED>
+using FoldSum = std::conditional_t<FIXED, long long, double>;
+// (lo, hi) += p, split before it is added: the workgroup partials are < 2^62 each, so nothing can wrap.  Arithmetic shift + mask:
+// p = (p >> 40) * 2^40 + (p & mask) for negative p as well; an unsigned T (finalize_scan_bands_kernel) takes p modulo 2^64.
+template <bool FIXED, class T>
+__host__ __device__ __forceinline__ void limb_add(T& lo, T& hi, T p) {
+  if constexpr (FIXED) { lo += p & (T)kLimbMask; hi += p >> kFixedLimbBits; } else lo += p;
+}
+// lo into [0, 2^40), the rest into hi
+template <class T>
+__host__ __device__ __forceinline__ void limbs_normalise(T& lo, T& hi) {
+  const T l = lo;
+  lo = 0;
+  limb_add<true>(lo, hi, l);
+}
+template <class T>
+__host__ __device__ __forceinline__ bool limbs_equal(T alo, T ahi, T blo, T bhi) {
+  limbs_normalise(alo, ahi);
+  limbs_normalise(blo, bhi);
+  return alo == blo && ahi == bhi;
+}
+// hi * 2^40 and lo are exact doubles (below 2^53 each): one rounding in the sum
+__device__ __forceinline__ double limbs_to_double(long long lo, long long hi) {
+  const double two40 = (double)(1ll << kFixedLimbBits);
+  return (double)hi * two40 + (double)lo;
+}
+// The two stores a fold ends with.  A plain counter:
+template <bool FIXED, class Sum>
+__device__ __forceinline__ void fold_add_counter(Sum* dst, Sum lo, Sum hi) {
+  if constexpr (FIXED) *dst += (hi << kFixedLimbBits) + lo; else *dst += lo;
+}
+// ... and a two-limb sum, whose low limb is left in [0, 2^40) (lo + *lo_dst < 2^40 + 2^14 * 2^40)
+template <bool FIXED, class Sum>
+__device__ __forceinline__ void fold_add_pair(Sum* lo_dst, Sum* hi_dst, Sum lo, Sum hi) {
+  if constexpr (FIXED) {
+    hi += *hi_dst;
+    lo += *lo_dst;
+    limbs_normalise(lo, hi);
+    *lo_dst = lo;
+    *hi_dst = hi;
+  } else {
+    *lo_dst += lo;
+  }
+}
+// slot s of `row`: a two-limb sum with its high limb in slot sh, or (sh < 0) a plain counter
+template <bool FIXED, class Sum>
+__device__ __forceinline__ void fold_store(Sum* row, int s, int sh, Sum lo, Sum hi) {
+  if (sh >= 0) fold_add_pair<FIXED>(row + s, row + sh, lo, hi); else fold_add_counter<FIXED>(row + s, lo, hi);
+}
+// The resolution rules of the finalizes.  false: the squared weights average below 2^6 quanta per passed ray - the integers do not
+// resolve them (their quantum 2^-39 of the squared weight bound is as fine as an int64 per workgroup allows); SUM_WEIGHTS_SQ - an error
+// estimate, nothing else depends on it - then reads NaN in the f64 output instead of a number that looks like one.  The weights: below
+// 2^12 quanta per passed ray.
+// Both means are judged only once kFixedMinRaysForMeans rays have passed: the check is there to catch a weight BOUND that is off by
+// orders of magnitude (an outlier in a table), and the average of a handful of rays says nothing about that - one faint ray alone
+// in an accumulator (a launch of a single low-energy CAST ray, weight 1e-8 of the bound) is exact to half a quantum like every
+// other and no reason to fail the call (found by the round-6 stream: ray 0 of seed 5 is such a ray).
+constexpr double kFixedMinRaysForMeans = 256.0;
+__device__ __forceinline__ bool squares_resolved(double n_passed, double sw2) {
+  return !(n_passed >= kFixedMinRaysForMeans) || sw2 >= 64.0 * n_passed;
+}
+__device__ __forceinline__ bool weights_resolved(double n_passed, double sw) {
+  return !(n_passed >= kFixedMinRaysForMeans) || sw >= 4096.0 * n_passed;
+}
+// Block-level sums of the finalizes.  Every thread of a wave calls these: *dst (LDS or global) += the wave's sum of v ...
+__device__ __forceinline__ void wave_add_i64(long long v, long long* dst) {
+  v = wave_sum_i64(v);
+  if ((threadIdx.x & 63) == 0 && v != 0) atomicAdd(reinterpret_cast<unsigned long long*>(dst), (unsigned long long)v);
+}
+// ... and the limb pair (*lo_dst, *hi_dst) += the wave's sum of the pairs (lo, hi), normalised (a thread's few slots: no overflow)
+__device__ __forceinline__ void wave_add_limbs(long long lo, long long hi, long long* lo_dst, long long* hi_dst) {
+  lo = wave_sum_i64(lo);
+  hi = wave_sum_i64(hi);
+  if ((threadIdx.x & 63) != 0) return;
+  limbs_normalise(lo, hi);
+  if (lo != 0) atomicAdd(reinterpret_cast<unsigned long long*>(lo_dst), (unsigned long long)lo);
+  if (hi != 0) atomicAdd(reinterpret_cast<unsigned long long*>(hi_dst), (unsigned long long)hi);
+}
+
+// ---- The fold tree ----
+// A fold block is GROUPS x SLOTS threads; thread (g, slot) with `has` (its slot has partials) sums load(g), load(g + GROUPS), ... in
+// that order, and the slot's first thread (g == 0) then adds the GROUPS group sums in order: the summation tree is fixed for a given
+// grid.  Returns that total in (lo, hi) to the threads with g == 0 and `has`, zeros to the others.  EVERY thread of the block must
+// call it (a barrier inside; the scan folds call it twice, pairs then counter rows, and so pass two).  `red`: the caller's LDS, one
+// plane per limb.  FIXED says whether the partials are split at 2^40, not what Sum is: false is a plain sum - the f64 partials, and
+// also the int64 counter rows of the scans in FIXED64, which need no limbs.
+template <bool FIXED, int GROUPS, int SLOTS, class Sum, class Load>
+__device__ __forceinline__ void fold_groups(Sum (&red)[FIXED ? 2 : 1][GROUPS][SLOTS], int g, int slot, int n_blocks, bool has, Load load,
+                                            Sum& lo, Sum& hi) {
+  lo = 0; hi = 0;
+  if (has) {
+    for (int b = g; b < n_blocks; b += GROUPS) limb_add<FIXED>(lo, hi, (Sum)load(b));
+    red[0][g][slot] = lo;
+    if constexpr (FIXED) red[1][g][slot] = hi;
+  }
+  __syncthreads();
+  lo = 0; hi = 0;
+  if (has && g == 0)
+    for (int i = 0; i < GROUPS; ++i) {
+      lo += red[0][i][slot];
+      if constexpr (FIXED) hi += red[1][i][slot];
+    }
+}
+
 // Fused angular scan: rows of the scan accumulator (include/sart.h: SART_ASCAN_*) += the per-workgroup sums of one launch.
-// 1024 threads = 128 (angle, partial slot) pairs x 8 groups of workgroups, the summation tree of fold_scan_kernel.  `shared_row`
-// (first group of angles of a scan only, else nullptr): the angle-independent counters.
+// 1024 threads = 256 (angle, partial slot) pairs x 4 groups of workgroups (fold_groups).  `shared_row` (first group of angles of a
+// scan only, else nullptr): the angle-independent counters.
 template <bool FIXED>
 __global__ __launch_bounds__(1024) void fold_ascan_kernel(double* __restrict__ rows_, double* __restrict__ shared_row_, const double* __restrict__ partials_,
                                                          int n_blocks, int n_angles, double n_rays) {
-  using Sum = std::conditional_t<FIXED, long long, double>;
-  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
+  using Sum = FoldSum<FIXED>;
   constexpr int kPairs = kAScanMaxAngles * kAScanPartialSlots, kGroups = 1024 / kPairs;
   static_assert(kPairs * kGroups == 1024 && kGroups >= 1, "one thread per (angle, partial slot, group of workgroups)");
   Sum* const rows = reinterpret_cast<Sum*>(rows_);
   Sum* const shared_row = reinterpret_cast<Sum*>(shared_row_);
   const Sum* const part = reinterpret_cast<const Sum*>(partials_);
-  __shared__ Sum red_lo[kGroups][kPairs], red_hi[kGroups][kPairs];
+  __shared__ Sum red[FIXED ? 2 : 1][kGroups][kPairs];
   const int pair = threadIdx.x % kPairs, g = threadIdx.x / kPairs;
   const int k = pair / kAScanPartialSlots, j = pair % kAScanPartialSlots;
-  Sum lo = 0, hi = 0;
-  if (k < n_angles && j < 7) {
-    for (int b = g; b < n_blocks; b += kGroups) {
-      const Sum p = part[((size_t)b * kAScanMaxAngles + k) * kAScanPartialSlots + j];
-      if constexpr (FIXED) { lo += p & kMask; hi += p >> kFixedLimbBits; } else lo += p;
-    }
-  }
-  red_lo[g][pair] = lo;
-  red_hi[g][pair] = hi;
-  __syncthreads();
+  Sum lo, hi;
+  fold_groups<FIXED, kGroups, kPairs>(red, g, pair, n_blocks, k < n_angles && j < 7,
+                                      [&](int b) { return part[((size_t)b * kAScanMaxAngles + k) * kAScanPartialSlots + j]; }, lo, hi);
   if (g != 0) return;
-  lo = 0; hi = 0;
-  for (int i = 0; i < kGroups; ++i) { lo += red_lo[i][pair]; hi += red_hi[i][pair]; }
+  // partial slots 0 / 1 are the sums, 2 .. 5 the angle's counters, 6 (angle 0) the rays that reached the telescope
   if (k < n_angles && j < 6) {
-    Sum* const row = rows + (size_t)k * SART_ASCAN_ROW;
-    if (j < 2) {
-      const int s = j == 0 ? SART_ASCAN_SUM_WEIGHTS : SART_ASCAN_SUM_WEIGHTS_SQ, sh = j == 0 ? SART_ASCAN_SUM_WEIGHTS_HI : SART_ASCAN_SUM_WEIGHTS_SQ_HI;
-      if constexpr (FIXED) {
-        lo += row[s];
-        row[s] = lo & kMask;
-        row[sh] += hi + (lo >> kFixedLimbBits);
-      } else {
-        row[s] += lo;
-      }
-    } else {
-      const int dst = j == 2 ? SART_ASCAN_N_PASSED : j == 3 ? SART_ASCAN_N_HIT_NICKEL : j == 4 ? SART_ASCAN_N_PASSED_TILL_WINDOW : SART_ASCAN_N_SHELL_SELECTED;
-      if constexpr (FIXED) row[dst] += (hi << kFixedLimbBits) + lo; else row[dst] += lo;
-    }
+    const int s = j == 0 ? SART_ASCAN_SUM_WEIGHTS : j == 1 ? SART_ASCAN_SUM_WEIGHTS_SQ : j == 2 ? SART_ASCAN_N_PASSED
+                  : j == 3 ? SART_ASCAN_N_HIT_NICKEL : j == 4 ? SART_ASCAN_N_PASSED_TILL_WINDOW : SART_ASCAN_N_SHELL_SELECTED;
+    fold_store<FIXED>(rows + (size_t)k * SART_ASCAN_ROW, s, j == 0 ? SART_ASCAN_SUM_WEIGHTS_HI : j == 1 ? SART_ASCAN_SUM_WEIGHTS_SQ_HI : -1, lo, hi);
   }
-  if (shared_row && k == 0 && j == 6) {
-    if constexpr (FIXED) shared_row[SART_ASCAN_N_REACHED_TELESCOPE] += (hi << kFixedLimbBits) + lo; else shared_row[SART_ASCAN_N_REACHED_TELESCOPE] += lo;
-  }
+  if (shared_row && k == 0 && j == 6) fold_add_counter<FIXED>(&shared_row[SART_ASCAN_N_REACHED_TELESCOPE], lo, hi);
   if (shared_row && pair == 7) shared_row[SART_ASCAN_N_RAYS] += (Sum)n_rays;
 }
 
-// acc scalars += sum over workgroups of the partials; N_RAYS += n_rays.  256 threads: 8 groups x 32 quantity slots (24 used).
-__global__ __launch_bounds__(256) void fold_scalars_kernel(double* __restrict__ scalars, const double* __restrict__ partials,
-                                                           int n_blocks, double n_rays) {
-  static_assert(SART_ACC_COUNT <= 32, "layout of the reduction below");
-  __shared__ double red[8][32];
-  const int k = threadIdx.x & 31, g = threadIdx.x >> 5;
-  double t = 0.0;
-  if (k < SART_ACC_COUNT)
-    for (int b = g; b < n_blocks; b += 8) t += partials[(size_t)b * SART_ACC_COUNT + k];
-  red[g][k] = t;
-  __syncthreads();
-  if (threadIdx.x < SART_ACC_COUNT) {
-    double s = (k == SART_ACC_N_RAYS) ? n_rays : 0.0;
-    for (int i = 0; i < 8; ++i) s += red[i][k];
-    scalars[k] += s;
-  }
-}
-
-// SART_ACCUM_FIXED64 form of the same fold, in integers.  The five sums every passed ray of every launch adds to are kept in
-// two limbs, value = hi * 2^40 + lo (include/sart.h): the workgroup partials (each < 2^62) are split before they are added,
-// so nothing can wrap, and lo is left in [0, 2^40).  Slot k's thread owns slot k and, for a two-limb sum, its *_HI slot; the
-// threads of the *_HI slots (whose partials are zero) write nothing.
+// acc scalars += sum over workgroups of the partials; N_RAYS += n_rays.  256 threads: 8 groups x 32 quantity slots (24 used).  In
+// SART_ACCUM_FIXED64 the five sums every passed ray of every launch adds to, and the weight outside the image, are two-limb sums: slot
+// k's thread owns slot k and its *_HI slot; the threads of the *_HI slots (whose partials are zero) write nothing.
 __device__ __forceinline__ int fixed_hi_slot(int k) {
   return k == SART_ACC_SUM_WEIGHTS ? SART_ACC_SUM_WEIGHTS_HI : k == SART_ACC_SUM_X ? SART_ACC_SUM_X_HI
          : k == SART_ACC_SUM_Y ? SART_ACC_SUM_Y_HI : k == SART_ACC_SUM_R ? SART_ACC_SUM_R_HI
@@ -3481,34 +3552,26 @@ __device__ __forceinline__ int fixed_hi_slot(int k) {
 __device__ __forceinline__ bool fixed_is_hi_slot(int k) {
   return (k >= SART_ACC_SUM_WEIGHTS_HI && k <= SART_ACC_SUM_R_HI) || k == SART_ACC_SUM_WEIGHTS_SQ_HI || k == SART_ACC_SUM_WEIGHTS_OUTSIDE_HI;
 }
+template <bool FIXED>
+__device__ __forceinline__ void fold_scalars(FoldSum<FIXED>* __restrict__ scalars, const FoldSum<FIXED>* __restrict__ partials, int n_blocks,
+                                             FoldSum<FIXED> n_rays) {
+  using Sum = FoldSum<FIXED>;
+  static_assert(SART_ACC_COUNT <= 32, "layout of the reduction below");
+  __shared__ Sum red[FIXED ? 2 : 1][8][32];
+  const int k = threadIdx.x & 31, g = threadIdx.x >> 5;
+  Sum lo, hi;
+  fold_groups<FIXED, 8, 32>(red, g, k, n_blocks, k < SART_ACC_COUNT, [&](int b) { return partials[(size_t)b * SART_ACC_COUNT + k]; }, lo, hi);
+  if (g != 0 || k >= SART_ACC_COUNT || (FIXED && fixed_is_hi_slot(k))) return;
+  if (k == SART_ACC_N_RAYS) lo += n_rays;   // (a plain counter, whose partials are zero: the fold adds the launch's rays)
+  fold_store<FIXED>(scalars, k, fixed_hi_slot(k), lo, hi);
+}
+__global__ __launch_bounds__(256) void fold_scalars_kernel(double* __restrict__ scalars, const double* __restrict__ partials,
+                                                           int n_blocks, double n_rays) {
+  fold_scalars<false>(scalars, partials, n_blocks, n_rays);
+}
 __global__ __launch_bounds__(256) void fold_scalars_fixed_kernel(long long* __restrict__ scalars, const long long* __restrict__ partials,
                                                                  int n_blocks, long long n_rays) {
-  static_assert(SART_ACC_COUNT <= 32, "layout of the reduction below");
-  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
-  __shared__ long long red_lo[8][32], red_hi[8][32];
-  const int k = threadIdx.x & 31, g = threadIdx.x >> 5;
-  long long lo = 0, hi = 0;
-  if (k < SART_ACC_COUNT)
-    for (int b = g; b < n_blocks; b += 8) {
-      const long long p = partials[(size_t)b * SART_ACC_COUNT + k];
-      lo += p & kMask;                 // arithmetic shift + mask: p = (p >> 40) * 2^40 + (p & mask) for negative p as well
-      hi += p >> kFixedLimbBits;
-    }
-  red_lo[g][k] = lo;
-  red_hi[g][k] = hi;
-  __syncthreads();
-  if (threadIdx.x < SART_ACC_COUNT && !fixed_is_hi_slot(k)) {
-    lo = 0; hi = 0;
-    for (int i = 0; i < 8; ++i) { lo += red_lo[i][k]; hi += red_hi[i][k]; }
-    const int kh = fixed_hi_slot(k);
-    if (kh >= 0) {
-      lo += scalars[k];              // < 2^40 + 2^14 * 2^40
-      scalars[k] = lo & kMask;
-      scalars[kh] += hi + (lo >> kFixedLimbBits);
-    } else {
-      scalars[k] += (hi << kFixedLimbBits) + lo + ((k == SART_ACC_N_RAYS) ? n_rays : 0ll);
-    }
-  }
+  fold_scalars<true>(scalars, partials, n_blocks, n_rays);
 }
 
 // acc[i] += sum over replicas; replicas are left zeroed for the next launch.  T = double, or long long (SART_ACCUM_FIXED64).
@@ -3526,187 +3589,106 @@ __global__ __launch_bounds__(256) void fold_replicas_kernel(T* __restrict__ acc,
 }
 
 // Fused mass scan: rows of the scan accumulator (include/sart.h: SART_SCAN_*) += the per-workgroup sums of one launch.
-// 1024 threads = 128 (mass, quantity) pairs x 8 groups of workgroups; group g sums the partial rows g, g + 8, ... of its pair in
-// that order and the pair's first thread adds the eight group sums in order: the summation tree is fixed for a given grid.
-// Pair (k, 2) turns the counts into N_PASSED of mass k = rays with a non-zero mass-independent weight factor minus those whose
-// conversion probability for this mass is exactly zero.  `shared_row` (first group of masses of a scan only, else nullptr): the
-// mass-independent counters.  FIXED: integers, the two sums in two limbs like fold_scalars_fixed_kernel.
+// 1024 threads = 128 (mass, quantity) pairs x 8 groups of workgroups (fold_groups).  Pair (k, 2) turns the counts into N_PASSED of
+// mass k = rays with a non-zero mass-independent weight factor minus those whose conversion probability for this mass is exactly
+// zero.  `shared_row` (first group of masses of a scan only, else nullptr): the mass-independent counters, plain sums of the
+// workgroups' scalars through the same tree.
 template <bool FIXED>
 __global__ __launch_bounds__(1024) void fold_scan_kernel(double* __restrict__ rows_, double* __restrict__ shared_row_, const double* __restrict__ scal_partials_,
                                                         const double* __restrict__ scan_partials_, int n_blocks, int n_masses, double n_rays) {
-  using Sum = std::conditional_t<FIXED, long long, double>;
-  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
+  using Sum = FoldSum<FIXED>;
   constexpr int kPairs = kScanMaxMasses * kScanPartialSlots, kGroups = 8;
   static_assert(kPairs * kGroups == 1024, "one thread per (mass, partial slot, group of workgroups)");
   Sum* const rows = reinterpret_cast<Sum*>(rows_);
   Sum* const shared_row = reinterpret_cast<Sum*>(shared_row_);
   const Sum* const scal = reinterpret_cast<const Sum*>(scal_partials_);
   const Sum* const scan = reinterpret_cast<const Sum*>(scan_partials_);
-  __shared__ Sum red_lo[kGroups][kPairs], red_hi[kGroups][kPairs], red_cnt[kGroups][4];
+  __shared__ Sum red[FIXED ? 2 : 1][kGroups][kPairs], red_cnt[1][kGroups][4];
   const int pair = threadIdx.x % kPairs, g = threadIdx.x / kPairs;
   const int k = pair >> 2, j = pair & 3;
-  Sum lo = 0, hi = 0;
-  if (k < n_masses && j < 3) {
-    for (int b = g; b < n_blocks; b += kGroups) {
-      Sum p = scan[((size_t)b * kScanMaxMasses + k) * kScanPartialSlots + j];
-      if (j == 2) p = scal[(size_t)b * SART_ACC_COUNT + SART_ACC_N_PASSED] - p;
-      if constexpr (FIXED) { lo += p & kMask; hi += p >> kFixedLimbBits; } else lo += p;
-    }
-  }
-  red_lo[g][pair] = lo;
-  red_hi[g][pair] = hi;
-  if (pair < 4) {   // the four counters that come from the workgroup partials
-    const int src = pair == 0 ? SART_ACC_N_REACHED_TELESCOPE : pair == 1 ? SART_ACC_N_SHELL_SELECTED : pair == 2 ? SART_ACC_N_HIT_NICKEL : SART_ACC_N_PASSED;
-    Sum t = 0;
-    if (shared_row)
-      for (int b = g; b < n_blocks; b += kGroups) t += scal[(size_t)b * SART_ACC_COUNT + src];
-    red_cnt[g][pair] = t;
-  }
-  __syncthreads();
+  Sum lo, hi, cnt, none;
+  fold_groups<FIXED, kGroups, kPairs>(red, g, pair, n_blocks, k < n_masses && j < 3, [&](int b) {
+    const Sum p = scan[((size_t)b * kScanMaxMasses + k) * kScanPartialSlots + j];
+    return j == 2 ? scal[(size_t)b * SART_ACC_COUNT + SART_ACC_N_PASSED] - p : p;
+  }, lo, hi);
+  // the four counters that come from the workgroup partials
+  const int src = pair == 0 ? SART_ACC_N_REACHED_TELESCOPE : pair == 1 ? SART_ACC_N_SHELL_SELECTED : pair == 2 ? SART_ACC_N_HIT_NICKEL : SART_ACC_N_PASSED;
+  fold_groups<false, kGroups, 4>(red_cnt, g, pair, n_blocks, shared_row && pair < 4, [&](int b) { return scal[(size_t)b * SART_ACC_COUNT + src]; }, cnt, none);
   if (g != 0) return;
-  if (k < n_masses && j < 3) {
-    lo = 0; hi = 0;
-    for (int i = 0; i < kGroups; ++i) { lo += red_lo[i][pair]; hi += red_hi[i][pair]; }
-    Sum* const row = rows + (size_t)k * SART_SCAN_ROW;
-    if constexpr (FIXED) {
-      if (j == 2) {
-        row[SART_SCAN_N_PASSED] += (hi << kFixedLimbBits) + lo;
-      } else {
-        const int s = j == 0 ? SART_SCAN_SUM_WEIGHTS : SART_SCAN_SUM_WEIGHTS_SQ, sh = j == 0 ? SART_SCAN_SUM_WEIGHTS_HI : SART_SCAN_SUM_WEIGHTS_SQ_HI;
-        lo += row[s];
-        row[s] = lo & kMask;
-        row[sh] += hi + (lo >> kFixedLimbBits);
-      }
-    } else {
-      row[j == 0 ? SART_SCAN_SUM_WEIGHTS : j == 1 ? SART_SCAN_SUM_WEIGHTS_SQ : SART_SCAN_N_PASSED] += lo;
-    }
-  }
+  if (k < n_masses && j < 3)
+    fold_store<FIXED>(rows + (size_t)k * SART_SCAN_ROW, j == 0 ? SART_SCAN_SUM_WEIGHTS : j == 1 ? SART_SCAN_SUM_WEIGHTS_SQ : SART_SCAN_N_PASSED,
+                      j == 0 ? SART_SCAN_SUM_WEIGHTS_HI : j == 1 ? SART_SCAN_SUM_WEIGHTS_SQ_HI : -1, lo, hi);
   if (shared_row && pair < 4) {
     const int dst = pair == 0 ? SART_SCAN_N_REACHED_TELESCOPE : pair == 1 ? SART_SCAN_N_SHELL_SELECTED : pair == 2 ? SART_SCAN_N_HIT_NICKEL : SART_SCAN_N_ON_DETECTOR;
-    Sum t = 0;
-    for (int i = 0; i < kGroups; ++i) t += red_cnt[i][pair];
-    shared_row[dst] += t;
+    shared_row[dst] += cnt;
     if (pair == 0) shared_row[SART_SCAN_N_RAYS] += (Sum)n_rays;
   }
 }
 
 // Banded mass scan: blocks of the spectra accumulator (include/sart.h: SART_MSPEC_*) += the per-workgroup band cells of one launch.
 // One workgroup per mass of the group and, if `counts` (first group of masses of a scan only, else nullptr), one more for the
-// per-band counts.  1024 threads = 64 cells (sum of w of band 0 .. 31, then sum of w^2) x 16 groups of workgroups; group g sums
-// the partial rows g, g + 16, ... of its cell in that order and the cell's first thread adds the sixteen group sums in order: the
-// summation tree is fixed for a given grid.  FIXED: integers, both sums in two limbs like fold_scan_kernel.  `block0`: the block of
-// the group's first mass; n_cells = n_bands + 1 (cells behind them hold zeros and are not stored).
+// per-band counts.  1024 threads = 64 cells (sum of w of band 0 .. 31, then sum of w^2) x 16 groups of workgroups (fold_groups).
+// `block0`: the block of the group's first mass; n_cells = n_bands + 1 (cells behind them hold zeros and are not stored).
 template <bool FIXED>
 __global__ __launch_bounds__(1024) void fold_scan_bands_kernel(double* __restrict__ block0_, double* __restrict__ counts_, const double* __restrict__ band_partials_,
                                                               int n_blocks, int n_masses, int n_cells) {
-  using Sum = std::conditional_t<FIXED, long long, double>;
-  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
+  using Sum = FoldSum<FIXED>;
   constexpr int kCells = 2 * kScanLanes, kGroups = 16;
   static_assert(kCells * kGroups == 1024, "one thread per (cell, group of workgroups)");
   const Sum* const part = reinterpret_cast<const Sum*>(band_partials_);
-  __shared__ Sum red_lo[kGroups][kCells], red_hi[kGroups][kCells];
+  __shared__ Sum red[FIXED ? 2 : 1][kGroups][kCells];
   const int c = threadIdx.x % kCells, g = threadIdx.x / kCells;
   const int k = blockIdx.x;   // mass of the group, or n_masses: the counts
   const bool is_counts = k == n_masses;
   const int row = is_counts ? kScanMaxMasses : k;
   const int band = c & (kScanLanes - 1);
-  Sum lo = 0, hi = 0;
-  if (band < n_cells && !(is_counts && c >= kScanLanes)) {
-    for (int b = g; b < n_blocks; b += kGroups) {
-      const Sum p = part[((size_t)b * (kScanMaxMasses + 1) + (size_t)row) * kCells + c];
-      if constexpr (FIXED) { lo += p & kMask; hi += p >> kFixedLimbBits; } else lo += p;
-    }
-  }
-  red_lo[g][c] = lo;
-  red_hi[g][c] = hi;
-  __syncthreads();
-  if (g != 0 || band >= n_cells) return;
-  lo = 0; hi = 0;
-  for (int i = 0; i < kGroups; ++i) { lo += red_lo[i][c]; hi += red_hi[i][c]; }
+  const bool mine = band < n_cells && !(is_counts && c >= kScanLanes);
+  Sum lo, hi;
+  fold_groups<FIXED, kGroups, kCells>(red, g, c, n_blocks, mine,
+                                      [&](int b) { return part[((size_t)b * (kScanMaxMasses + 1) + (size_t)row) * kCells + c]; }, lo, hi);
+  if (g != 0 || !mine) return;
   if (is_counts) {
-    if (c >= kScanLanes) return;
-    Sum* const dst = reinterpret_cast<Sum*>(counts_) + (size_t)band * SART_MSPEC_CELL;
-    if constexpr (FIXED) dst[SART_MSPEC_N_ON_DETECTOR] += (hi << kFixedLimbBits) + lo; else dst[SART_MSPEC_N_ON_DETECTOR] += lo;
+    fold_add_counter<FIXED>(reinterpret_cast<Sum*>(counts_) + (size_t)band * SART_MSPEC_CELL + SART_MSPEC_N_ON_DETECTOR, lo, hi);
     return;
   }
   Sum* const dst = reinterpret_cast<Sum*>(block0_) + ((size_t)k * (size_t)n_cells + (size_t)band) * SART_MSPEC_CELL;
-  const int s = c < kScanLanes ? SART_MSPEC_SUM_WEIGHTS : SART_MSPEC_SUM_WEIGHTS_SQ;
-  if constexpr (FIXED) {
-    const int sh = c < kScanLanes ? SART_MSPEC_SUM_WEIGHTS_HI : SART_MSPEC_SUM_WEIGHTS_SQ_HI;
-    lo += dst[s];
-    dst[s] = lo & kMask;
-    dst[sh] += hi + (lo >> kFixedLimbBits);
-  } else {
-    dst[s] += lo;
-  }
+  if (c < kScanLanes) fold_add_pair<FIXED>(dst + SART_MSPEC_SUM_WEIGHTS, dst + SART_MSPEC_SUM_WEIGHTS_HI, lo, hi);
+  else fold_add_pair<FIXED>(dst + SART_MSPEC_SUM_WEIGHTS_SQ, dst + SART_MSPEC_SUM_WEIGHTS_SQ_HI, lo, hi);
 }
 
 // Fused energy scan: rows of the scan accumulator (include/sart.h: SART_ESCAN_*) += the per-workgroup sums of one launch.  1024
-// threads = 128 (energy, quantity) pairs x 8 groups of workgroups, summed in a fixed order like fold_scan_kernel.  `shared_row`
-// (first group of energies of a scan only, else nullptr): the energy-independent counters from shared_partials[n_blocks][4].
-// FIXED: integers; the two sums in two limbs (hi 2^40 + lo, lo in [0, 2^40)) like fold_scalars_fixed_kernel.
+// threads = 128 (energy, quantity) pairs x 8 groups of workgroups (fold_groups).  `shared_row` (first group of energies of a scan
+// only, else nullptr): the energy-independent counters from shared_partials[n_blocks][4].
 template <bool FIXED>
 __global__ __launch_bounds__(1024) void fold_escan_kernel(double* __restrict__ rows_, double* __restrict__ shared_row_,
                                                           const double* __restrict__ shared_partials_, const double* __restrict__ escan_partials_,
                                                           int n_blocks, int n_energies, double n_rays) {
-  using Sum = std::conditional_t<FIXED, long long, double>;
-  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
+  using Sum = FoldSum<FIXED>;
   constexpr int kPairs = kEScanMaxEnergies * kScanPartialSlots, kGroups = 8;
   static_assert(kPairs * kGroups == 1024, "one thread per (energy, partial slot, group of workgroups)");
   Sum* const rows = reinterpret_cast<Sum*>(rows_);
   Sum* const shared_row = reinterpret_cast<Sum*>(shared_row_);
   const Sum* const shp = reinterpret_cast<const Sum*>(shared_partials_);
   const Sum* const esp = reinterpret_cast<const Sum*>(escan_partials_);
-  __shared__ Sum red_lo[kGroups][kPairs], red_hi[kGroups][kPairs], red_cnt[kGroups][4];
+  __shared__ Sum red[FIXED ? 2 : 1][kGroups][kPairs], red_cnt[1][kGroups][4];
   const int pair = threadIdx.x % kPairs, g = threadIdx.x / kPairs;
   const int k = pair >> 2, j = pair & 3;
-  Sum lo = 0, hi = 0;
-  if (k < n_energies) {
-    for (int b = g; b < n_blocks; b += kGroups) {
-      const Sum p = esp[((size_t)b * kEScanMaxEnergies + k) * kScanPartialSlots + j];
-      if constexpr (FIXED) { lo += p & kMask; hi += p >> kFixedLimbBits; } else lo += p;
-    }
-  }
-  red_lo[g][pair] = lo;
-  red_hi[g][pair] = hi;
-  if (pair < 4) {
-    Sum t = 0;
-    if (shared_row && pair < 3)
-      for (int b = g; b < n_blocks; b += kGroups) t += shp[(size_t)b * 4 + pair];
-    red_cnt[g][pair] = t;
-  }
-  __syncthreads();
+  Sum lo, hi, cnt, none;
+  fold_groups<FIXED, kGroups, kPairs>(red, g, pair, n_blocks, k < n_energies,
+                                      [&](int b) { return esp[((size_t)b * kEScanMaxEnergies + k) * kScanPartialSlots + j]; }, lo, hi);
+  fold_groups<false, kGroups, 4>(red_cnt, g, pair, n_blocks, shared_row && pair < 3, [&](int b) { return shp[(size_t)b * 4 + pair]; }, cnt, none);
   if (g != 0) return;
   if (k < n_energies) {
-    lo = 0; hi = 0;
-    for (int i = 0; i < kGroups; ++i) { lo += red_lo[i][pair]; hi += red_hi[i][pair]; }
-    Sum* const row = rows + (size_t)k * SART_ESCAN_ROW;
-    if (j >= 2) {
-      const int dst = j == 2 ? SART_ESCAN_N_PASSED : SART_ESCAN_N_PASSED_TILL_WINDOW;
-      if constexpr (FIXED) row[dst] += (hi << kFixedLimbBits) + lo; else row[dst] += lo;
-    } else if constexpr (FIXED) {
-      const int s = j == 0 ? SART_ESCAN_SUM_WEIGHTS : SART_ESCAN_SUM_WEIGHTS_SQ, sh = j == 0 ? SART_ESCAN_SUM_WEIGHTS_HI : SART_ESCAN_SUM_WEIGHTS_SQ_HI;
-      lo += row[s];
-      row[s] = lo & kMask;
-      row[sh] += hi + (lo >> kFixedLimbBits);
-    } else {
-      row[j == 0 ? SART_ESCAN_SUM_WEIGHTS : SART_ESCAN_SUM_WEIGHTS_SQ] += lo;
-    }
+    const int s = j == 0 ? SART_ESCAN_SUM_WEIGHTS : j == 1 ? SART_ESCAN_SUM_WEIGHTS_SQ : j == 2 ? SART_ESCAN_N_PASSED : SART_ESCAN_N_PASSED_TILL_WINDOW;
+    fold_store<FIXED>(rows + (size_t)k * SART_ESCAN_ROW, s, j == 0 ? SART_ESCAN_SUM_WEIGHTS_HI : j == 1 ? SART_ESCAN_SUM_WEIGHTS_SQ_HI : -1, lo, hi);
   }
   if (shared_row && pair < 3) {
     const int dst = pair == 0 ? SART_ESCAN_N_REACHED_TELESCOPE : pair == 1 ? SART_ESCAN_N_SHELL_SELECTED : SART_ESCAN_N_HIT_NICKEL;
-    Sum t = 0;
-    for (int i = 0; i < kGroups; ++i) t += red_cnt[i][pair];
-    shared_row[dst] += t;
+    shared_row[dst] += cnt;
     if (pair == 0) shared_row[SART_ESCAN_N_RAYS] += (Sum)n_rays;
   }
 }
 
-// What the finalize kernels report about a raw SART_ACCUM_FIXED64 accumulator (OR-ed into a word of the context that the next
-// sart_synchronize reads): integers that no longer mean what they should.
-constexpr uint32_t kFixedStatusWrapped = 1u;       // a slot is negative or >= 2^62: wrapped, or about to (weights and counts are >= 0)
-constexpr uint32_t kFixedStatusUnresolved = 2u;    // the accumulated weights average below 2^12 quanta per passed ray
-constexpr uint32_t kFixedStatusNotConserved = 4u;  // pixels (+ outside) / radial / energy weight bins do not add up to SUM_WEIGHTS: a slot wrapped
 // Scratch of one finalize (device memory of the context; word 0 = the status, kept; the rest zeroed before every finalize): exact
 // two-limb sums of the raw slots that must add up to SUM_WEIGHTS.  Every passed ray adds the SAME integer to SUM_WEIGHTS and to one
 // pixel (or to SUM_WEIGHTS_OUTSIDE), one radial bin and one energy bin, so the equalities hold exactly - unless a slot wrapped,
@@ -3722,26 +3704,15 @@ struct FixedCheck {
   long long fail[10];                                       // pix, want_in, rad, en, want: (lo, hi) each
 };
 __device__ __forceinline__ void fixed_check_add(long long v, long long v_hi, bool mine, long long* lo_dst, long long* hi_dst) {
-  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
   if (!__builtin_amdgcn_ballot_w64(mine)) return;   // wave-uniform
   // (v_hi: the slot's limb in the roll-over array, in units of 2^40 - sart_rollover_accumulator_device; 0 without one)
-  long long lo = wave_sum_i64(mine ? (v & kMask) : 0ll), hi = wave_sum_i64(mine ? ((v >> kFixedLimbBits) + v_hi) : 0ll);
-  if ((threadIdx.x & 63) == 0) {
-    hi += lo >> kFixedLimbBits;
-    lo &= kMask;
-    atomicAdd(reinterpret_cast<unsigned long long*>(lo_dst), (unsigned long long)lo);
-    atomicAdd(reinterpret_cast<unsigned long long*>(hi_dst), (unsigned long long)hi);
-  }
+  long long lo = 0, hi = 0;
+  if (mine) { hi = v_hi; limb_add<true>(lo, hi, v); }
+  wave_add_limbs(lo, hi, lo_dst, hi_dst);
 }
 __global__ void fixed_check_kernel(FixedCheck* C) {
-  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
-  auto same = [&](long long alo, long long ahi, long long blo, long long bhi) {
-    ahi += alo >> kFixedLimbBits; alo &= kMask;
-    bhi += blo >> kFixedLimbBits; blo &= kMask;
-    return alo == blo && ahi == bhi;
-  };
-  bool ok = same(C->pix_lo, C->pix_hi, C->want_in_lo, C->want_in_hi);
-  if (C->spectra) ok = ok && same(C->rad_lo, C->rad_hi, C->want_lo, C->want_hi) && same(C->en_lo, C->en_hi, C->want_lo, C->want_hi);
+  bool ok = limbs_equal(C->pix_lo, C->pix_hi, C->want_in_lo, C->want_in_hi);
+  if (C->spectra) ok = ok && limbs_equal(C->rad_lo, C->rad_hi, C->want_lo, C->want_hi) && limbs_equal(C->en_lo, C->en_hi, C->want_lo, C->want_hi);
   if (!ok) {
     if (!(C->status & kFixedStatusNotConserved)) {
       const long long v[10] = {C->pix_lo, C->pix_hi, C->want_in_lo, C->want_in_hi, C->rad_lo, C->rad_hi, C->en_lo, C->en_hi, C->want_lo, C->want_hi};
@@ -3753,18 +3724,10 @@ __global__ void fixed_check_kernel(FixedCheck* C) {
 __device__ __forceinline__ void fixed_status_check_slot(long long v, uint32_t* status) {
   if (v < 0 || v >= (1ll << 62)) atomicOr(status, kFixedStatusWrapped);
 }
-// Returns false if the squared weights average below 2^6 quanta per passed ray: the integers do not resolve them (their quantum
-// 2^-39 of the squared weight bound is as fine as an int64 per workgroup allows); SUM_WEIGHTS_SQ - an error estimate, nothing
-// else depends on it - then reads NaN in the f64 output instead of a number that looks like one.
-// Both means are judged only once kFixedMinRaysForMeans rays have passed: the check is there to catch a weight BOUND that is off by
-// orders of magnitude (an outlier in a table), and the average of a handful of rays says nothing about that - one faint ray alone
-// in an accumulator (a launch of a single low-energy CAST ray, weight 1e-8 of the bound) is exact to half a quantum like every
-// other and no reason to fail the call (found by the round-6 stream: ray 0 of seed 5 is such a ray).
-constexpr double kFixedMinRaysForMeans = 256.0;
+// Sets the status where the weights are not resolved; returns whether the squared weights are (squares_resolved)
 __device__ __forceinline__ bool fixed_status_check_means(double quanta_w, double quanta_w2, double n_passed, uint32_t* status) {
-  if (!(n_passed >= kFixedMinRaysForMeans)) return true;
-  if (quanta_w < 4096.0 * n_passed) atomicOr(status, kFixedStatusUnresolved);
-  return quanta_w2 >= 64.0 * n_passed;
+  if (!weights_resolved(n_passed, quanta_w)) atomicOr(status, kFixedStatusUnresolved);
+  return squares_resolved(n_passed, quanta_w2);
 }
 
 // Raw SART_ACCUM_FIXED64 accumulator -> the f64 layout of include/sart.h (sart_finalize_accumulator_device).  Element-wise, so
@@ -3850,15 +3813,14 @@ __global__ __launch_bounds__(256) void finalize_fixed_kernel(const long long* in
 // sart_rollover_accumulator_device: the bits of every slot above 2^40 move into the slot's limb in `hi` (units of 2^40); the slot
 // keeps [0, 2^40).  A slot that is negative or >= 2^62 has wrapped (or is about to): reported like the finalize kernel does.
 __global__ __launch_bounds__(256) void rollover_fixed_kernel(long long* acc, long long* hi, long long n, FixedCheck* C) {
-  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const long long v = acc[i];
+  long long v = acc[i], h = hi[i];
   fixed_status_check_slot(v, &C->status);
-  const long long h = hi[i] + (v >> kFixedLimbBits);
+  limbs_normalise(v, h);
   if (h < 0) atomicOr(&C->status, kFixedStatusWrapped);
   hi[i] = h;
-  acc[i] = v & kMask;
+  acc[i] = v;
 }
 
 // Raw FIXED64 scan accumulator -> doubles: rows [0, n) of `in` / `out` (a group of up to kScanMaxMasses masses, whose quanta
@@ -3880,14 +3842,13 @@ __global__ __launch_bounds__(64) void finalize_scan_kernel(const long long* in, 
   long long v[SART_SCAN_ROW];
   if (k < F.n_masses) {
     for (int j = 0; j < SART_SCAN_ROW; ++j) { v[j] = in[(size_t)k * SART_SCAN_ROW + j]; fixed_status_check_slot(v[j], status); }
-    const double two40 = (double)(1ll << kFixedLimbBits);
-    const double sw = (double)v[SART_SCAN_SUM_WEIGHTS_HI] * two40 + (double)v[SART_SCAN_SUM_WEIGHTS];
-    const double sw2 = (double)v[SART_SCAN_SUM_WEIGHTS_SQ_HI] * two40 + (double)v[SART_SCAN_SUM_WEIGHTS_SQ];
+    const double sw = limbs_to_double(v[SART_SCAN_SUM_WEIGHTS], v[SART_SCAN_SUM_WEIGHTS_HI]);
+    const double sw2 = limbs_to_double(v[SART_SCAN_SUM_WEIGHTS_SQ], v[SART_SCAN_SUM_WEIGHTS_SQ_HI]);
     const double n_passed = (double)v[SART_SCAN_N_PASSED];
     bool w_ok = true, sq_ok;
     if (F.counter_slots >> 31) {
-      w_ok = !(n_passed >= kFixedMinRaysForMeans) || sw >= 4096.0 * n_passed;
-      sq_ok = !(n_passed >= kFixedMinRaysForMeans) || sw2 >= 64.0 * n_passed;
+      w_ok = weights_resolved(n_passed, sw);
+      sq_ok = squares_resolved(n_passed, sw2);
     } else {
       sq_ok = fixed_status_check_means(sw, sw2, n_passed, status);
     }
@@ -3908,7 +3869,7 @@ __global__ __launch_bounds__(64) void finalize_scan_kernel(const long long* in, 
 // wave for the per-band counts.  `rows`: the RAW scan rows of the group, `shared_row` the raw counter row (finalize_scan_kernel
 // converts and judges those; this kernel only reads them).  Checks: every slot in [0, 2^62); the cells of a mass add up to its scan
 // row, both sums and both limbs, and the band counts to N_ON_DETECTOR - as integers modulo 2^64, which a wrapped slot breaks; a mass
-// whose squared weights the row does not resolve (fixed_status_check_means' rule) reads NaN in every cell's sum of w^2.
+// whose squared weights the row does not resolve (squares_resolved) reads NaN in every cell's sum of w^2.
 struct FinalizeBandsArgs {
   int32_t n_masses, n_cells;
   double q_w[kScanMaxMasses], q_w2[kScanMaxMasses];
@@ -3916,94 +3877,92 @@ struct FinalizeBandsArgs {
 __global__ __launch_bounds__(64) void finalize_scan_bands_kernel(const long long* __restrict__ rows, const long long* __restrict__ shared_row,
                                                                  const long long* in, double* out, const long long* counts_in, double* counts_out,
                                                                  FinalizeBandsArgs F, FixedCheck* C) {
-  constexpr unsigned long long kMask = (1ull << kFixedLimbBits) - 1ull;
+  using U = unsigned long long;
   uint32_t* const status = &C->status;
   const int k = blockIdx.x, c = threadIdx.x;
   const bool mine = c < F.n_cells;
-  auto wave_sum_u64 = [](unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-  };
   if (k == F.n_masses) {   // the counts
     long long v[SART_MSPEC_CELL] = {0, 0, 0, 0};
     if (mine) {
       for (int j = 0; j < SART_MSPEC_CELL; ++j) { v[j] = counts_in[(size_t)c * SART_MSPEC_CELL + j]; fixed_status_check_slot(v[j], status); }
     }
-    const unsigned long long total = wave_sum_u64((unsigned long long)v[SART_MSPEC_N_ON_DETECTOR]);
-    if (c == 0 && total != (unsigned long long)shared_row[SART_SCAN_N_ON_DETECTOR]) atomicOr(status, kFixedStatusNotConserved);
+    const U total = wave_sum((U)v[SART_MSPEC_N_ON_DETECTOR]);
+    if (c == 0 && total != (U)shared_row[SART_SCAN_N_ON_DETECTOR]) atomicOr(status, kFixedStatusNotConserved);
     if (mine)
       for (int j = 0; j < SART_MSPEC_CELL; ++j) counts_out[(size_t)c * SART_MSPEC_CELL + j] = j == SART_MSPEC_N_ON_DETECTOR ? (double)v[j] : 0.0;
     return;
   }
   const long long* const row = rows + (size_t)k * SART_SCAN_ROW;
-  const double two40 = (double)(1ll << kFixedLimbBits);
-  const double n_passed = (double)row[SART_SCAN_N_PASSED];
-  const double row_sw2 = (double)row[SART_SCAN_SUM_WEIGHTS_SQ_HI] * two40 + (double)row[SART_SCAN_SUM_WEIGHTS_SQ];
-  const bool sq_ok = !(n_passed >= kFixedMinRaysForMeans) || row_sw2 >= 64.0 * n_passed;
+  const bool sq_ok = squares_resolved((double)row[SART_SCAN_N_PASSED], limbs_to_double(row[SART_SCAN_SUM_WEIGHTS_SQ], row[SART_SCAN_SUM_WEIGHTS_SQ_HI]));
   long long v[SART_MSPEC_CELL] = {0, 0, 0, 0};
   const size_t at = ((size_t)k * (size_t)F.n_cells + (size_t)c) * SART_MSPEC_CELL;
   if (mine)
     for (int j = 0; j < SART_MSPEC_CELL; ++j) { v[j] = in[at + j]; fixed_status_check_slot(v[j], status); }
   // normalised limbs, summed over the cells
-  auto lo_of = [&](int s) { return (unsigned long long)v[s] & kMask; };
-  auto hi_of = [&](int s, int sh) { return (unsigned long long)v[sh] + ((unsigned long long)v[s] >> kFixedLimbBits); };
-  const unsigned long long w_lo = wave_sum_u64(lo_of(SART_MSPEC_SUM_WEIGHTS)), w_hi = wave_sum_u64(hi_of(SART_MSPEC_SUM_WEIGHTS, SART_MSPEC_SUM_WEIGHTS_HI));
-  const unsigned long long q_lo = wave_sum_u64(lo_of(SART_MSPEC_SUM_WEIGHTS_SQ)), q_hi = wave_sum_u64(hi_of(SART_MSPEC_SUM_WEIGHTS_SQ, SART_MSPEC_SUM_WEIGHTS_SQ_HI));
-  if (c == 0) {
-    auto same = [&](unsigned long long lo, unsigned long long hi, int s, int sh) {
-      const unsigned long long r_lo = (unsigned long long)row[s], r_hi = (unsigned long long)row[sh];
-      return ((lo & kMask) == (r_lo & kMask)) && (hi + (lo >> kFixedLimbBits) == r_hi + (r_lo >> kFixedLimbBits));
-    };
-    if (!same(w_lo, w_hi, SART_SCAN_SUM_WEIGHTS, SART_SCAN_SUM_WEIGHTS_HI) || !same(q_lo, q_hi, SART_SCAN_SUM_WEIGHTS_SQ, SART_SCAN_SUM_WEIGHTS_SQ_HI))
-      atomicOr(status, kFixedStatusNotConserved);
-  }
+  U w_lo = 0, w_hi = (U)v[SART_MSPEC_SUM_WEIGHTS_HI], q_lo = 0, q_hi = (U)v[SART_MSPEC_SUM_WEIGHTS_SQ_HI];
+  limb_add<true>(w_lo, w_hi, (U)v[SART_MSPEC_SUM_WEIGHTS]);
+  limb_add<true>(q_lo, q_hi, (U)v[SART_MSPEC_SUM_WEIGHTS_SQ]);
+  w_lo = wave_sum(w_lo); w_hi = wave_sum(w_hi);
+  q_lo = wave_sum(q_lo); q_hi = wave_sum(q_hi);
+  if (c == 0 && (!limbs_equal(w_lo, w_hi, (U)row[SART_SCAN_SUM_WEIGHTS], (U)row[SART_SCAN_SUM_WEIGHTS_HI]) ||
+                 !limbs_equal(q_lo, q_hi, (U)row[SART_SCAN_SUM_WEIGHTS_SQ], (U)row[SART_SCAN_SUM_WEIGHTS_SQ_HI])))
+    atomicOr(status, kFixedStatusNotConserved);
   if (mine) {
-    out[at + SART_MSPEC_SUM_WEIGHTS] = ((double)v[SART_MSPEC_SUM_WEIGHTS_HI] * two40 + (double)v[SART_MSPEC_SUM_WEIGHTS]) * F.q_w[k];
+    out[at + SART_MSPEC_SUM_WEIGHTS] = limbs_to_double(v[SART_MSPEC_SUM_WEIGHTS], v[SART_MSPEC_SUM_WEIGHTS_HI]) * F.q_w[k];
     out[at + SART_MSPEC_SUM_WEIGHTS_SQ] =
-        sq_ok ? ((double)v[SART_MSPEC_SUM_WEIGHTS_SQ_HI] * two40 + (double)v[SART_MSPEC_SUM_WEIGHTS_SQ]) * F.q_w2[k] : __builtin_nan("");
+        sq_ok ? limbs_to_double(v[SART_MSPEC_SUM_WEIGHTS_SQ], v[SART_MSPEC_SUM_WEIGHTS_SQ_HI]) * F.q_w2[k] : __builtin_nan("");
     out[at + SART_MSPEC_SUM_WEIGHTS_HI] = 0.0;
     out[at + SART_MSPEC_SUM_WEIGHTS_SQ_HI] = 0.0;
   }
 }
 
-// Per-shell block (include/sart.h: SART_SHELL_*) += the per-workgroup shell tables of one shell_histogram_kernel launch.  One
-// workgroup per shell, 64 threads = 8 slots (6 used) x 8 groups of workgroups; group g sums the partials g, g + 8, ... in that order
-// and slot j's first thread adds the eight group sums in order: the summation tree is fixed for a given grid.  FIXED: integers, the
-// two sums in two limbs (hi 2^40 + lo, lo in [0, 2^40)) like fold_scalars_fixed_kernel.
-template <bool FIXED>
-__global__ __launch_bounds__(64) void fold_shells_kernel(double* __restrict__ block_, const double* __restrict__ partials_, int n_blocks) {
-  using Sum = std::conditional_t<FIXED, long long, double>;
-  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
-  Sum* const row = reinterpret_cast<Sum*>(block_) + (size_t)blockIdx.x * SART_SHELL_ROW;
-  const Sum* const part = reinterpret_cast<const Sum*>(partials_);
-  __shared__ Sum red_lo[8][8], red_hi[8][8];
-  const int j = threadIdx.x & 7, g = threadIdx.x >> 3;
-  Sum lo = 0, hi = 0;
-  if (j < kShellPartialSlots)
-    for (int b = g; b < n_blocks; b += 8) {
-      const Sum p = part[((size_t)b * kMaxShells + blockIdx.x) * kShellPartialSlots + j];
-      if constexpr (FIXED) { lo += p & kMask; hi += p >> kFixedLimbBits; } else lo += p;
-    }
-  red_lo[g][j] = lo;
-  red_hi[g][j] = hi;
-  __syncthreads();
-  if (g != 0 || j >= kShellPartialSlots) return;
-  lo = 0; hi = 0;
-  for (int i = 0; i < 8; ++i) { lo += red_lo[i][j]; hi += red_hi[i][j]; }
-  // partial slots 0 .. 3 are the counters SART_SHELL_N_*, 4 / 5 the sums
-  if (j < 4) {
-    if constexpr (FIXED) row[j] += (hi << kFixedLimbBits) + lo; else row[j] += lo;
-  } else {
-    const int s = j == 4 ? SART_SHELL_SUM_WEIGHTS : SART_SHELL_SUM_WEIGHTS_SQ, sh = j == 4 ? SART_SHELL_SUM_WEIGHTS_HI : SART_SHELL_SUM_WEIGHTS_SQ_HI;
-    if constexpr (FIXED) {
-      lo += row[s];
-      row[s] = lo & kMask;
-      row[sh] += hi + (lo >> kFixedLimbBits);
-    } else {
-      row[s] += lo;
-    }
+// The folds of the breakdowns: block row blockIdx.x (include/sart.h: SART_SHELL_*, SART_CHAN_*, the head SART_ORIGIN_*) += the
+// per-workgroup tables of one launch.  One workgroup per row, 64 threads = kSlots partial slots (the first kUsed of them used) x
+// 64 / kSlots groups of workgroups (fold_groups); partial (b, row, j) sits at (b kMaxRows + row) kPartialSlots + j and goes to slot
+// dst(j) of the row, a two-limb sum where hi(j) >= 0.
+struct ShellFold {     // partial slots 0 .. 3 are the counters SART_SHELL_N_*, 4 / 5 the sums
+  static constexpr int kSlots = 8, kUsed = kShellPartialSlots, kPartialSlots = kShellPartialSlots, kMaxRows = kMaxShells, kRow = SART_SHELL_ROW;
+  static __device__ int dst(int j) { return j < 4 ? j : j == 4 ? SART_SHELL_SUM_WEIGHTS : SART_SHELL_SUM_WEIGHTS_SQ; }
+  static __device__ int hi(int j) { return j == 4 ? SART_SHELL_SUM_WEIGHTS_HI : j == 5 ? SART_SHELL_SUM_WEIGHTS_SQ_HI : -1; }
+};
+struct ChannelFold {   // partial slots 0 .. 2 are the sums SUM_WEIGHTS, SUM_WEIGHTS_SQ, SUM_WEIGHTS_OUTSIDE, 3 the counter N_CONTRIBUTING
+  static constexpr int kSlots = kChanPartialSlots, kUsed = 4, kPartialSlots = kChanPartialSlots, kMaxRows = kMaxChannels, kRow = SART_CHAN_ROW;
+  static __device__ int dst(int j) {
+    return j == 0 ? SART_CHAN_SUM_WEIGHTS : j == 1 ? SART_CHAN_SUM_WEIGHTS_SQ : j == 2 ? SART_CHAN_SUM_WEIGHTS_OUTSIDE : SART_CHAN_N_CONTRIBUTING;
   }
+  static __device__ int hi(int j) {
+    return j == 0 ? SART_CHAN_SUM_WEIGHTS_HI : j == 1 ? SART_CHAN_SUM_WEIGHTS_SQ_HI : j == 2 ? SART_CHAN_SUM_WEIGHTS_OUTSIDE_HI : -1;
+  }
+};
+struct OriginFold {    // one row, the head (the aperture block's too): partial slot 0 is the counter N_PASSED, 1 / 2 the sums
+  static constexpr int kSlots = kOriginPartialSlots, kUsed = 3, kPartialSlots = kOriginPartialSlots, kMaxRows = 1, kRow = SART_ORIGIN_HEAD;
+  static __device__ int dst(int j) { return j == 0 ? SART_ORIGIN_N_PASSED : j == 1 ? SART_ORIGIN_SUM_WEIGHTS : SART_ORIGIN_SUM_WEIGHTS_SQ; }
+  static __device__ int hi(int j) { return j == 1 ? SART_ORIGIN_SUM_WEIGHTS_HI : j == 2 ? SART_ORIGIN_SUM_WEIGHTS_SQ_HI : -1; }
+};
+template <bool FIXED, class B>
+__device__ __forceinline__ void fold_breakdown(double* __restrict__ block_, const double* __restrict__ partials_, int n_blocks) {
+  using Sum = FoldSum<FIXED>;
+  constexpr int kGroups = 64 / B::kSlots;
+  static_assert(B::kSlots * kGroups == 64 && B::kUsed <= B::kSlots && B::kUsed <= B::kPartialSlots, "one thread per (partial slot, group of workgroups)");
+  const Sum* const part = reinterpret_cast<const Sum*>(partials_);
+  __shared__ Sum red[FIXED ? 2 : 1][kGroups][B::kSlots];
+  const int j = threadIdx.x % B::kSlots, g = threadIdx.x / B::kSlots;
+  Sum lo, hi;
+  fold_groups<FIXED, kGroups, B::kSlots>(red, g, j, n_blocks, j < B::kUsed,
+                                         [&](int b) { return part[((size_t)b * B::kMaxRows + blockIdx.x) * B::kPartialSlots + j]; }, lo, hi);
+  if (g == 0 && j < B::kUsed) fold_store<FIXED>(reinterpret_cast<Sum*>(block_) + (size_t)blockIdx.x * B::kRow, B::dst(j), B::hi(j), lo, hi);
+}
+template <bool FIXED>
+__global__ __launch_bounds__(64) void fold_shells_kernel(double* __restrict__ block, const double* __restrict__ partials, int n_blocks) {
+  fold_breakdown<FIXED, ShellFold>(block, partials, n_blocks);     // 8 groups
+}
+template <bool FIXED>
+__global__ __launch_bounds__(64) void fold_channels_kernel(double* __restrict__ block, const double* __restrict__ partials, int n_blocks) {
+  fold_breakdown<FIXED, ChannelFold>(block, partials, n_blocks);   // 16 groups
+}
+template <bool FIXED>
+__global__ __launch_bounds__(64) void fold_origin_kernel(double* __restrict__ block, const double* __restrict__ partials, int n_blocks) {
+  fold_breakdown<FIXED, OriginFold>(block, partials, n_blocks);    // 16 groups
 }
 
 // Raw FIXED64 shell block -> doubles (sart_finalize_shells_device).  One workgroup per shell: its row and, with spectra, its two
@@ -4016,7 +3975,6 @@ struct FinalizeShellsArgs {
   double q_w, q_w2;
 };
 __global__ __launch_bounds__(256) void finalize_shells_kernel(const long long* in, double* out, FinalizeShellsArgs F, FixedCheck* C) {
-  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
   uint32_t* const status = &C->status;
   const int s = blockIdx.x;
   const long long* const row = in + (size_t)s * SART_SHELL_ROW;
@@ -4034,31 +3992,21 @@ __global__ __launch_bounds__(256) void finalize_shells_kernel(const long long* i
       fixed_status_check_slot(n, status);
       fixed_status_check_slot(w, status);
       c += n;
-      lo += w & kMask;
-      hi += w >> kFixedLimbBits;
+      limb_add<true>(lo, hi, w);
       out[c0 + e] = (double)n;
       out[w0 + e] = (double)w * F.q_w;
     }
-    c = wave_sum_i64(c); lo = wave_sum_i64(lo); hi = wave_sum_i64(hi);
-    if ((threadIdx.x & 63) == 0) {
-      atomicAdd(reinterpret_cast<unsigned long long*>(&cnt_sum), (unsigned long long)c);
-      atomicAdd(reinterpret_cast<unsigned long long*>(&w_lo), (unsigned long long)lo);
-      atomicAdd(reinterpret_cast<unsigned long long*>(&w_hi), (unsigned long long)hi);
-    }
+    wave_add_i64(c, &cnt_sum);
+    wave_add_limbs(lo, hi, &w_lo, &w_hi);
   }
   __syncthreads();
   if (threadIdx.x != 0) return;
   for (int j = 0; j < SART_SHELL_ROW; ++j) fixed_status_check_slot(v[j], status);
-  const double two40 = (double)(1ll << kFixedLimbBits);
-  const double sw = (double)v[SART_SHELL_SUM_WEIGHTS_HI] * two40 + (double)v[SART_SHELL_SUM_WEIGHTS];
-  const double sw2 = (double)v[SART_SHELL_SUM_WEIGHTS_SQ_HI] * two40 + (double)v[SART_SHELL_SUM_WEIGHTS_SQ];
+  const double sw = limbs_to_double(v[SART_SHELL_SUM_WEIGHTS], v[SART_SHELL_SUM_WEIGHTS_HI]);
+  const double sw2 = limbs_to_double(v[SART_SHELL_SUM_WEIGHTS_SQ], v[SART_SHELL_SUM_WEIGHTS_SQ_HI]);
   const bool sq_ok = fixed_status_check_means(sw, sw2, (double)v[SART_SHELL_N_PASSED], status);
-  if (F.spectra) {
-    const long long hi = w_hi + (w_lo >> kFixedLimbBits), lo = w_lo & kMask;
-    const long long want_hi = v[SART_SHELL_SUM_WEIGHTS_HI] + (v[SART_SHELL_SUM_WEIGHTS] >> kFixedLimbBits);
-    const long long want_lo = v[SART_SHELL_SUM_WEIGHTS] & kMask;
-    if (cnt_sum != v[SART_SHELL_N_PASSED] || hi != want_hi || lo != want_lo) atomicOr(status, kFixedStatusNotConserved);
-  }
+  if (F.spectra && (cnt_sum != v[SART_SHELL_N_PASSED] || !limbs_equal(w_lo, w_hi, v[SART_SHELL_SUM_WEIGHTS], v[SART_SHELL_SUM_WEIGHTS_HI])))
+    atomicOr(status, kFixedStatusNotConserved);
   double* const o = out + (size_t)s * SART_SHELL_ROW;
   for (int j = 0; j < SART_SHELL_ROW; ++j) o[j] = 0.0;
   o[SART_SHELL_N_SELECTED] = (double)v[SART_SHELL_N_SELECTED];
@@ -4067,45 +4015,6 @@ __global__ __launch_bounds__(256) void finalize_shells_kernel(const long long* i
   o[SART_SHELL_N_PASSED] = (double)v[SART_SHELL_N_PASSED];
   o[SART_SHELL_SUM_WEIGHTS] = sw * F.q_w;
   o[SART_SHELL_SUM_WEIGHTS_SQ] = sq_ok ? sw2 * F.q_w2 : __builtin_nan("");
-}
-
-// Channel block (include/sart.h: SART_CHAN_*) += the per-workgroup channel tables of one channel_histogram_kernel launch.  One
-// workgroup per channel, 64 threads = 4 slots x 16 groups of workgroups; group g sums the partials g, g + 16, ... in that order and
-// slot j's first thread adds the sixteen group sums in order: the summation tree is fixed for a given grid.  FIXED: integers, the three
-// sums in two limbs (hi 2^40 + lo, lo in [0, 2^40)) like fold_shells_kernel.
-template <bool FIXED>
-__global__ __launch_bounds__(64) void fold_channels_kernel(double* __restrict__ block_, const double* __restrict__ partials_, int n_blocks) {
-  using Sum = std::conditional_t<FIXED, long long, double>;
-  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
-  Sum* const row = reinterpret_cast<Sum*>(block_) + (size_t)blockIdx.x * SART_CHAN_ROW;
-  const Sum* const part = reinterpret_cast<const Sum*>(partials_);
-  __shared__ Sum red_lo[16][kChanPartialSlots], red_hi[16][kChanPartialSlots];
-  const int j = threadIdx.x & (kChanPartialSlots - 1), g = threadIdx.x / kChanPartialSlots;
-  Sum lo = 0, hi = 0;
-  for (int b = g; b < n_blocks; b += 16) {
-    const Sum p = part[((size_t)b * kMaxChannels + blockIdx.x) * kChanPartialSlots + j];
-    if constexpr (FIXED) { lo += p & kMask; hi += p >> kFixedLimbBits; } else lo += p;
-  }
-  red_lo[g][j] = lo;
-  red_hi[g][j] = hi;
-  __syncthreads();
-  if (g != 0) return;
-  lo = 0; hi = 0;
-  for (int i = 0; i < 16; ++i) { lo += red_lo[i][j]; hi += red_hi[i][j]; }
-  // partial slots 0 .. 2 are the sums SUM_WEIGHTS, SUM_WEIGHTS_SQ, SUM_WEIGHTS_OUTSIDE, 3 the counter N_CONTRIBUTING
-  if (j == 3) {
-    if constexpr (FIXED) row[SART_CHAN_N_CONTRIBUTING] += (hi << kFixedLimbBits) + lo; else row[SART_CHAN_N_CONTRIBUTING] += lo;
-  } else {
-    const int s = j == 0 ? SART_CHAN_SUM_WEIGHTS : j == 1 ? SART_CHAN_SUM_WEIGHTS_SQ : SART_CHAN_SUM_WEIGHTS_OUTSIDE;
-    const int sh = j == 0 ? SART_CHAN_SUM_WEIGHTS_HI : j == 1 ? SART_CHAN_SUM_WEIGHTS_SQ_HI : SART_CHAN_SUM_WEIGHTS_OUTSIDE_HI;
-    if constexpr (FIXED) {
-      lo += row[s];
-      row[s] = lo & kMask;
-      row[sh] += hi + (lo >> kFixedLimbBits);
-    } else {
-      row[s] += lo;
-    }
-  }
 }
 
 // Raw FIXED64 channel block -> doubles (sart_finalize_channels_device).  One workgroup per channel: its row, with spectra its energy
@@ -4119,7 +4028,6 @@ struct FinalizeChannelsArgs {
   double q_w, q_w2;
 };
 __global__ __launch_bounds__(256) void finalize_channels_kernel(const long long* in, double* out, FinalizeChannelsArgs F, FixedCheck* C) {
-  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
   uint32_t* const status = &C->status;
   const int t = blockIdx.x;
   const long long* const row = in + (size_t)t * SART_CHAN_ROW;
@@ -4136,79 +4044,30 @@ __global__ __launch_bounds__(256) void finalize_channels_kernel(const long long*
     for (size_t e = threadIdx.x; e < ne; e += 256) {
       const long long w = in[e0 + e];
       fixed_status_check_slot(w, status);
-      acc4[0] += w & kMask;
-      acc4[1] += w >> kFixedLimbBits;
+      limb_add<true>(acc4[0], acc4[1], w);
       out[e0 + e] = (double)w * F.q_w;
     }
   for (size_t p = threadIdx.x; p < (size_t)F.n_img; p += 256) {
     const long long w = in[p0 + p];
     fixed_status_check_slot(w, status);
-    acc4[2] += w & kMask;
-    acc4[3] += w >> kFixedLimbBits;
+    limb_add<true>(acc4[2], acc4[3], w);
     out[p0 + p] = (double)w * F.q_w;
   }
-  for (int k = 0; k < 4; ++k) {
-    const long long s = wave_sum_i64(acc4[k]);
-    if ((threadIdx.x & 63) == 0) atomicAdd(reinterpret_cast<unsigned long long*>(&sums[k]), (unsigned long long)s);
-  }
+  wave_add_limbs(acc4[0], acc4[1], &sums[0], &sums[1]);
+  wave_add_limbs(acc4[2], acc4[3], &sums[2], &sums[3]);
   __syncthreads();
   if (threadIdx.x != 0) return;
   for (int j = 0; j < SART_CHAN_ROW; ++j) fixed_status_check_slot(v[j], status);
-  const double two40 = (double)(1ll << kFixedLimbBits);
-  const long long want_hi = v[SART_CHAN_SUM_WEIGHTS_HI] + (v[SART_CHAN_SUM_WEIGHTS] >> kFixedLimbBits);
-  const long long want_lo = v[SART_CHAN_SUM_WEIGHTS] & kMask;
-  if (F.spectra) {
-    const long long hi = sums[1] + (sums[0] >> kFixedLimbBits), lo = sums[0] & kMask;
-    if (hi != want_hi || lo != want_lo) atomicOr(status, kFixedStatusNotConserved);
-  }
-  {
-    const long long l = sums[2] + v[SART_CHAN_SUM_WEIGHTS_OUTSIDE];
-    const long long hi = sums[3] + v[SART_CHAN_SUM_WEIGHTS_OUTSIDE_HI] + (l >> kFixedLimbBits), lo = l & kMask;
-    if (hi != want_hi || lo != want_lo) atomicOr(status, kFixedStatusNotConserved);
-  }
+  const long long want_lo = v[SART_CHAN_SUM_WEIGHTS], want_hi = v[SART_CHAN_SUM_WEIGHTS_HI];
+  if (F.spectra && !limbs_equal(sums[0], sums[1], want_lo, want_hi)) atomicOr(status, kFixedStatusNotConserved);
+  if (!limbs_equal(sums[2] + v[SART_CHAN_SUM_WEIGHTS_OUTSIDE], sums[3] + v[SART_CHAN_SUM_WEIGHTS_OUTSIDE_HI], want_lo, want_hi))
+    atomicOr(status, kFixedStatusNotConserved);
   double* const o = out + (size_t)t * SART_CHAN_ROW;
   for (int j = 0; j < SART_CHAN_ROW; ++j) o[j] = 0.0;
-  o[SART_CHAN_SUM_WEIGHTS] = ((double)v[SART_CHAN_SUM_WEIGHTS_HI] * two40 + (double)v[SART_CHAN_SUM_WEIGHTS]) * F.q_w;
-  o[SART_CHAN_SUM_WEIGHTS_SQ] = ((double)v[SART_CHAN_SUM_WEIGHTS_SQ_HI] * two40 + (double)v[SART_CHAN_SUM_WEIGHTS_SQ]) * F.q_w2;
+  o[SART_CHAN_SUM_WEIGHTS] = limbs_to_double(v[SART_CHAN_SUM_WEIGHTS], v[SART_CHAN_SUM_WEIGHTS_HI]) * F.q_w;
+  o[SART_CHAN_SUM_WEIGHTS_SQ] = limbs_to_double(v[SART_CHAN_SUM_WEIGHTS_SQ], v[SART_CHAN_SUM_WEIGHTS_SQ_HI]) * F.q_w2;
   o[SART_CHAN_N_CONTRIBUTING] = (double)v[SART_CHAN_N_CONTRIBUTING];
-  o[SART_CHAN_SUM_WEIGHTS_OUTSIDE] = ((double)v[SART_CHAN_SUM_WEIGHTS_OUTSIDE_HI] * two40 + (double)v[SART_CHAN_SUM_WEIGHTS_OUTSIDE]) * F.q_w;
-}
-
-// Head of the origin block (include/sart.h: SART_ORIGIN_*) += the per-workgroup sums of one origin_histogram_kernel launch.  One
-// workgroup, 64 threads = 4 slots (3 used) x 16 groups of workgroups, the summation tree of fold_channels_kernel.  FIXED: integers,
-// the two sums in two limbs (hi 2^40 + lo, lo in [0, 2^40)).
-template <bool FIXED>
-__global__ __launch_bounds__(64) void fold_origin_kernel(double* __restrict__ block_, const double* __restrict__ partials_, int n_blocks) {
-  using Sum = std::conditional_t<FIXED, long long, double>;
-  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
-  Sum* const head = reinterpret_cast<Sum*>(block_);
-  const Sum* const part = reinterpret_cast<const Sum*>(partials_);
-  __shared__ Sum red_lo[16][kOriginPartialSlots], red_hi[16][kOriginPartialSlots];
-  const int j = threadIdx.x & (kOriginPartialSlots - 1), g = threadIdx.x / kOriginPartialSlots;
-  Sum lo = 0, hi = 0;
-  for (int b = g; b < n_blocks; b += 16) {
-    const Sum p = part[(size_t)b * kOriginPartialSlots + j];
-    if constexpr (FIXED) { lo += p & kMask; hi += p >> kFixedLimbBits; } else lo += p;
-  }
-  red_lo[g][j] = lo;
-  red_hi[g][j] = hi;
-  __syncthreads();
-  if (g != 0 || j > 2) return;
-  lo = 0; hi = 0;
-  for (int i = 0; i < 16; ++i) { lo += red_lo[i][j]; hi += red_hi[i][j]; }
-  // partial slot 0 is the counter N_PASSED, 1 / 2 the sums
-  if (j == 0) {
-    if constexpr (FIXED) head[SART_ORIGIN_N_PASSED] += (hi << kFixedLimbBits) + lo; else head[SART_ORIGIN_N_PASSED] += lo;
-  } else {
-    const int s = j == 1 ? SART_ORIGIN_SUM_WEIGHTS : SART_ORIGIN_SUM_WEIGHTS_SQ, sh = j == 1 ? SART_ORIGIN_SUM_WEIGHTS_HI : SART_ORIGIN_SUM_WEIGHTS_SQ_HI;
-    if constexpr (FIXED) {
-      lo += head[s];
-      head[s] = lo & kMask;
-      head[sh] += hi + (lo >> kFixedLimbBits);
-    } else {
-      head[s] += lo;
-    }
-  }
+  o[SART_CHAN_SUM_WEIGHTS_OUTSIDE] = limbs_to_double(v[SART_CHAN_SUM_WEIGHTS_OUTSIDE], v[SART_CHAN_SUM_WEIGHTS_OUTSIDE_HI]) * F.q_w;
 }
 
 // Raw FIXED64 origin block -> doubles (sart_finalize_origin_device), in two steps.  finalize_origin_kernel: the cells, one thread
@@ -4222,16 +4081,9 @@ struct FinalizeOriginArgs {
   long long n_cells;
   double q_w, q_w2;
 };
-__device__ __forceinline__ bool origin_squares_resolved(const long long* head) {
-  const double two40 = (double)(1ll << kFixedLimbBits);
-  const double n_passed = (double)head[SART_ORIGIN_N_PASSED];
-  const double sw2 = (double)head[SART_ORIGIN_SUM_WEIGHTS_SQ_HI] * two40 + (double)head[SART_ORIGIN_SUM_WEIGHTS_SQ];
-  return !(n_passed >= kFixedMinRaysForMeans) || sw2 >= 64.0 * n_passed;
-}
 __global__ __launch_bounds__(256) void finalize_origin_kernel(const long long* in, double* out, FinalizeOriginArgs F, FixedCheck* C) {
   uint32_t* const status = &C->status;
-  const bool sq_ok = origin_squares_resolved(in);
-  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
+  const bool sq_ok = squares_resolved((double)in[SART_ORIGIN_N_PASSED], limbs_to_double(in[SART_ORIGIN_SUM_WEIGHTS_SQ], in[SART_ORIGIN_SUM_WEIGHTS_SQ_HI]));
   long long cnt = 0, w_lo = 0, w_hi = 0, w2_lo = 0, w2_hi = 0;   // this thread's cells (a few: the limbs cannot overflow)
   const long long stride = (long long)gridDim.x * 256;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < F.n_cells; i += stride) {
@@ -4242,46 +4094,29 @@ __global__ __launch_bounds__(256) void finalize_origin_kernel(const long long* i
     fixed_status_check_slot(w2, status);
     fixed_status_check_slot(r, status);
     cnt += n;
-    w_lo += w & kMask;
-    w_hi += w >> kFixedLimbBits;
-    w2_lo += w2 & kMask;
-    w2_hi += w2 >> kFixedLimbBits;
+    limb_add<true>(w_lo, w_hi, w);
+    limb_add<true>(w2_lo, w2_hi, w2);
     out[o + SART_ORIGIN_N] = (double)n;
     out[o + SART_ORIGIN_SUM_WEIGHTS] = (double)w * F.q_w;
     out[o + SART_ORIGIN_SUM_WEIGHTS_SQ] = sq_ok ? (double)w2 * F.q_w2 : __builtin_nan("");
     out[o + 3] = 0.0;
   }
   // (every thread is back here: whole waves reduce)
-  cnt = wave_sum_i64(cnt);
-  w_lo = wave_sum_i64(w_lo); w_hi = wave_sum_i64(w_hi);
-  w2_lo = wave_sum_i64(w2_lo); w2_hi = wave_sum_i64(w2_hi);
-  if ((threadIdx.x & 63) == 0) {
-    auto add = [](long long* dst, long long v) { if (v != 0) atomicAdd(reinterpret_cast<unsigned long long*>(dst), (unsigned long long)v); };
-    add(&C->en_lo, cnt);
-    add(&C->pix_lo, w_lo & kMask);
-    add(&C->pix_hi, w_hi + (w_lo >> kFixedLimbBits));
-    add(&C->rad_lo, w2_lo & kMask);
-    add(&C->rad_hi, w2_hi + (w2_lo >> kFixedLimbBits));
-  }
+  wave_add_i64(cnt, &C->en_lo);
+  wave_add_limbs(w_lo, w_hi, &C->pix_lo, &C->pix_hi);
+  wave_add_limbs(w2_lo, w2_hi, &C->rad_lo, &C->rad_hi);
 }
 __global__ __launch_bounds__(64) void finalize_origin_head_kernel(const long long* in, double* out, FinalizeOriginArgs F, FixedCheck* C) {
-  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
   if (threadIdx.x != 0) return;
   uint32_t* const status = &C->status;
   long long v[SART_ORIGIN_HEAD];
   for (int j = 0; j < SART_ORIGIN_HEAD; ++j) { v[j] = in[j]; fixed_status_check_slot(v[j], status); }
-  auto same = [&](long long alo, long long ahi, long long blo, long long bhi) {
-    ahi += alo >> kFixedLimbBits; alo &= kMask;
-    bhi += blo >> kFixedLimbBits; blo &= kMask;
-    return alo == blo && ahi == bhi;
-  };
-  if (C->en_lo != v[SART_ORIGIN_N_PASSED] || !same(C->pix_lo, C->pix_hi, v[SART_ORIGIN_SUM_WEIGHTS], v[SART_ORIGIN_SUM_WEIGHTS_HI]) ||
-      !same(C->rad_lo, C->rad_hi, v[SART_ORIGIN_SUM_WEIGHTS_SQ], v[SART_ORIGIN_SUM_WEIGHTS_SQ_HI]))
+  if (C->en_lo != v[SART_ORIGIN_N_PASSED] || !limbs_equal(C->pix_lo, C->pix_hi, v[SART_ORIGIN_SUM_WEIGHTS], v[SART_ORIGIN_SUM_WEIGHTS_HI]) ||
+      !limbs_equal(C->rad_lo, C->rad_hi, v[SART_ORIGIN_SUM_WEIGHTS_SQ], v[SART_ORIGIN_SUM_WEIGHTS_SQ_HI]))
     atomicOr(status, kFixedStatusNotConserved);
-  const double two40 = (double)(1ll << kFixedLimbBits);
-  const double sw = (double)v[SART_ORIGIN_SUM_WEIGHTS_HI] * two40 + (double)v[SART_ORIGIN_SUM_WEIGHTS];
-  const double sw2 = (double)v[SART_ORIGIN_SUM_WEIGHTS_SQ_HI] * two40 + (double)v[SART_ORIGIN_SUM_WEIGHTS_SQ];
-  const bool sq_ok = origin_squares_resolved(v);
+  const double sw = limbs_to_double(v[SART_ORIGIN_SUM_WEIGHTS], v[SART_ORIGIN_SUM_WEIGHTS_HI]);
+  const double sw2 = limbs_to_double(v[SART_ORIGIN_SUM_WEIGHTS_SQ], v[SART_ORIGIN_SUM_WEIGHTS_SQ_HI]);
+  const bool sq_ok = squares_resolved((double)v[SART_ORIGIN_N_PASSED], sw2);
   for (int j = 0; j < SART_ORIGIN_HEAD; ++j) out[j] = 0.0;
   out[SART_ORIGIN_N_PASSED] = (double)v[SART_ORIGIN_N_PASSED];
   out[SART_ORIGIN_SUM_WEIGHTS] = sw * F.q_w;
@@ -4837,6 +4672,29 @@ int histogram_block_of(int) { return 1024; }
   X(4, true, true, 0, false) X(5, true, false, 0, true) X(6, true, false, 1, true)
 #define SART_SCAN_VARIANTS(X) X(1, false, false, -1, false) X(2, false, true, -1, false) X(3, true, false, 1, false) X(6, true, false, 1, true)
 
+// The instantiation of fold kernel K for the accumulation mode
+#define SART_FOLD_OF(K, fixed) ((fixed) ? K<true> : K<false>)
+// What every accumulator launch ends with: the scalars (acc scalars += the workgroup partials) ...
+static void launch_scalars_fold(double* scalars, const double* partials, const TraceArgs& A, int n_blocks, hipStream_t stream, bool fixed) {
+  if (fixed)
+    hipLaunchKernelGGL(fold_scalars_fixed_kernel, dim3(1), dim3(256), 0, stream, reinterpret_cast<long long*>(scalars),
+                       reinterpret_cast<const long long*>(partials), n_blocks, (long long)A.n_rays);
+  else
+    hipLaunchKernelGGL(fold_scalars_kernel, dim3(1), dim3(256), 0, stream, scalars, partials, n_blocks, (double)A.n_rays);
+}
+// ... and, where the launch used image replicas, those
+static void launch_accumulator_folds(const TraceArgs& A, double* acc, int n_blocks, hipStream_t stream, bool fixed) {
+  const int n_img = A.image_nx * A.image_ny;
+  launch_scalars_fold(acc + n_img, A.partials, A, n_blocks, stream, fixed);
+  if (A.replica_mask == 0u) return;
+  const dim3 grid((n_img + 255) / 256);
+  if (fixed)
+    hipLaunchKernelGGL(fold_replicas_kernel<long long>, grid, dim3(256), 0, stream, reinterpret_cast<long long*>(acc),
+                       reinterpret_cast<long long*>(A.replicas), n_img, (int)A.replica_mask + 1, A.replica_stride);
+  else
+    hipLaunchKernelGGL(fold_replicas_kernel<double>, grid, dim3(256), 0, stream, acc, A.replicas, n_img, (int)A.replica_mask + 1, A.replica_stride);
+}
+
 int histogram_blocks_per_cu(int variant) {   // the FIXED64 and SCAN instantiations use the same LDS and launch bounds
   int n = 0;
   hipError_t e = hipErrorInvalidValue;
@@ -4861,20 +4719,7 @@ void launch_trace_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, 
 #undef X
     default: return;
   }
-  const int n_img = A.image_nx * A.image_ny;
-  if (fixed) {
-    long long* const acc_i = reinterpret_cast<long long*>(acc);
-    hipLaunchKernelGGL(fold_scalars_fixed_kernel, dim3(1), dim3(256), 0, stream, acc_i + n_img,
-                       reinterpret_cast<const long long*>(A.partials), n_blocks, (long long)A.n_rays);
-    if (A.replica_mask != 0u)
-      hipLaunchKernelGGL(fold_replicas_kernel<long long>, dim3((n_img + 255) / 256), dim3(256), 0, stream, acc_i,
-                         reinterpret_cast<long long*>(A.replicas), n_img, (int)A.replica_mask + 1, A.replica_stride);
-    return;
-  }
-  hipLaunchKernelGGL(fold_scalars_kernel, dim3(1), dim3(256), 0, stream, acc + n_img, A.partials, n_blocks, (double)A.n_rays);
-  if (A.replica_mask != 0u)
-    hipLaunchKernelGGL(fold_replicas_kernel<double>, dim3((n_img + 255) / 256), dim3(256), 0, stream, acc, A.replicas, n_img,
-                       (int)A.replica_mask + 1, A.replica_stride);
+  launch_accumulator_folds(A, acc, n_blocks, stream, fixed);
 }
 
 // One group of SC.n_masses <= kScanMaxMasses masses over the rays of A: trace + per-mass accumulation, then the fold into
@@ -4890,10 +4735,8 @@ bool launch_trace_mass_scan(const HotA& H, const HotB& HB, const DevBlob* blob, 
 #undef X
     default: return false;
   }
-  if (fixed)
-    hipLaunchKernelGGL(fold_scan_kernel<true>, dim3(1), dim3(1024), 0, stream, rows, shared_row, A.partials, SC.partials, n_blocks, SC.n_masses, (double)A.n_rays);
-  else
-    hipLaunchKernelGGL(fold_scan_kernel<false>, dim3(1), dim3(1024), 0, stream, rows, shared_row, A.partials, SC.partials, n_blocks, SC.n_masses, (double)A.n_rays);
+  hipLaunchKernelGGL(SART_FOLD_OF(fold_scan_kernel, fixed), dim3(1), dim3(1024), 0, stream, rows, shared_row, A.partials, SC.partials, n_blocks,
+                     SC.n_masses, (double)A.n_rays);
   return true;
 }
 
@@ -4923,13 +4766,10 @@ bool launch_trace_mass_scan_spectra(const HotA& H, const HotB& HB, const DevBlob
   }
   const dim3 grid(SC.n_masses + (counts ? 1 : 0));
   const double* const band_partials = SC.partials + (size_t)n_blocks * (kScanMaxMasses * kScanPartialSlots);   // behind the plain rows
-  if (fixed) {
-    hipLaunchKernelGGL(fold_scan_kernel<true>, dim3(1), dim3(1024), 0, stream, rows, shared_row, A.partials, SC.partials, n_blocks, SC.n_masses, (double)A.n_rays);
-    hipLaunchKernelGGL(fold_scan_bands_kernel<true>, grid, dim3(1024), 0, stream, block0, counts, band_partials, n_blocks, SC.n_masses, SC.n_bands + 1);
-  } else {
-    hipLaunchKernelGGL(fold_scan_kernel<false>, dim3(1), dim3(1024), 0, stream, rows, shared_row, A.partials, SC.partials, n_blocks, SC.n_masses, (double)A.n_rays);
-    hipLaunchKernelGGL(fold_scan_bands_kernel<false>, grid, dim3(1024), 0, stream, block0, counts, band_partials, n_blocks, SC.n_masses, SC.n_bands + 1);
-  }
+  hipLaunchKernelGGL(SART_FOLD_OF(fold_scan_kernel, fixed), dim3(1), dim3(1024), 0, stream, rows, shared_row, A.partials, SC.partials, n_blocks,
+                     SC.n_masses, (double)A.n_rays);
+  hipLaunchKernelGGL(SART_FOLD_OF(fold_scan_bands_kernel, fixed), grid, dim3(1024), 0, stream, block0, counts, band_partials, n_blocks, SC.n_masses,
+                     SC.n_bands + 1);
   return true;
 }
 
@@ -4951,10 +4791,8 @@ void launch_trace_angular_scan(const HotA& H, const HotB& HB, const DevBlob* blo
     case 2: hipLaunchKernelGGL((trace_angular_scan_kernel<1024, true, 0, false>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, no_acc, HB, AN); break;
     default: hipLaunchKernelGGL((trace_angular_scan_kernel<1024, true, 0, true>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, no_acc, HB, AN); break;
   }
-  if (fixed)
-    hipLaunchKernelGGL(fold_ascan_kernel<true>, dim3(1), dim3(1024), 0, stream, rows, shared_row, AN.partials, n_blocks, AN.n_angles, (double)A.n_rays);
-  else
-    hipLaunchKernelGGL(fold_ascan_kernel<false>, dim3(1), dim3(1024), 0, stream, rows, shared_row, AN.partials, n_blocks, AN.n_angles, (double)A.n_rays);
+  hipLaunchKernelGGL(SART_FOLD_OF(fold_ascan_kernel, fixed), dim3(1), dim3(1024), 0, stream, rows, shared_row, AN.partials, n_blocks, AN.n_angles,
+                     (double)A.n_rays);
 }
 
 // The fused energy scan of one launch group: the kernel (generic variants: `rotated` = hist_variant_of 2), then the fold into
@@ -4974,10 +4812,8 @@ void launch_trace_energy_scan(const HotA& H, const HotB& HB, const DevBlob* blob
     case 2: hipLaunchKernelGGL((energy_scan_kernel<1024, true, false>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, no_acc, HB, EN); break;
     default: hipLaunchKernelGGL((energy_scan_kernel<1024, true, true>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, no_acc, HB, EN); break;
   }
-  if (fixed)
-    hipLaunchKernelGGL(fold_escan_kernel<true>, dim3(1), dim3(1024), 0, stream, rows, shared_row, A.partials, EN.partials, n_blocks, EN.n_energies, (double)A.n_rays);
-  else
-    hipLaunchKernelGGL(fold_escan_kernel<false>, dim3(1), dim3(1024), 0, stream, rows, shared_row, A.partials, EN.partials, n_blocks, EN.n_energies, (double)A.n_rays);
+  hipLaunchKernelGGL(SART_FOLD_OF(fold_escan_kernel, fixed), dim3(1), dim3(1024), 0, stream, rows, shared_row, A.partials, EN.partials, n_blocks,
+                     EN.n_energies, (double)A.n_rays);
 }
 
 int ascan_images_blocks_per_cu(bool fast) {
@@ -4996,20 +4832,12 @@ void launch_ascan_images(const HotA& H, const HotB& HB, const DevBlob* blob, con
     case 2: hipLaunchKernelGGL((ascan_images_kernel<1024, true, 0, false>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, img_partials, HB, AN); break;
     default: hipLaunchKernelGGL((ascan_images_kernel<1024, true, 0, true>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, img_partials, HB, AN); break;
   }
-  if (fixed)
-    hipLaunchKernelGGL(fold_ascan_kernel<true>, dim3(1), dim3(1024), 0, stream, rows, shared_row, AN.partials, n_blocks, AN.n_angles, (double)A.n_rays);
-  else
-    hipLaunchKernelGGL(fold_ascan_kernel<false>, dim3(1), dim3(1024), 0, stream, rows, shared_row, AN.partials, n_blocks, AN.n_angles, (double)A.n_rays);
+  hipLaunchKernelGGL(SART_FOLD_OF(fold_ascan_kernel, fixed), dim3(1), dim3(1024), 0, stream, rows, shared_row, AN.partials, n_blocks, AN.n_angles,
+                     (double)A.n_rays);
   const size_t n_img = (size_t)A.image_nx * (size_t)A.image_ny;
-  for (int k = 0; k < AN.n_angles; ++k) {
-    double* const scalars = A.replicas + (size_t)k * A.replica_stride + n_img;
-    const double* const part = img_partials + (size_t)k * (size_t)n_blocks * SART_ACC_COUNT;
-    if (fixed)
-      hipLaunchKernelGGL(fold_scalars_fixed_kernel, dim3(1), dim3(256), 0, stream, reinterpret_cast<long long*>(scalars),
-                         reinterpret_cast<const long long*>(part), n_blocks, (long long)A.n_rays);
-    else
-      hipLaunchKernelGGL(fold_scalars_kernel, dim3(1), dim3(256), 0, stream, scalars, part, n_blocks, (double)A.n_rays);
-  }
+  for (int k = 0; k < AN.n_angles; ++k)
+    launch_scalars_fold(A.replicas + (size_t)k * A.replica_stride + n_img, img_partials + (size_t)k * (size_t)n_blocks * SART_ACC_COUNT, A, n_blocks,
+                        stream, fixed);
 }
 
 // The breakdown launches (generic variants: `rotated` = hist_variant_of 2): the kernel, then the folds of launch_trace_histogram
@@ -5049,20 +4877,7 @@ static void launch_breakdown_histogram(const BreakdownKernels<Args>& K, const Ho
                                        const TraceArgs& A, double* acc, const Args& BD, int n_rows, int n_blocks, hipStream_t stream,
                                        bool rotated, bool fixed) {
   hipLaunchKernelGGL(K.trace[kernel_index(rotated, fixed)], dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, BD);
-  const int n_img = A.image_nx * A.image_ny;
-  if (fixed) {
-    long long* const acc_i = reinterpret_cast<long long*>(acc);
-    hipLaunchKernelGGL(fold_scalars_fixed_kernel, dim3(1), dim3(256), 0, stream, acc_i + n_img,
-                       reinterpret_cast<const long long*>(A.partials), n_blocks, (long long)A.n_rays);
-    if (A.replica_mask != 0u)
-      hipLaunchKernelGGL(fold_replicas_kernel<long long>, dim3((n_img + 255) / 256), dim3(256), 0, stream, acc_i,
-                         reinterpret_cast<long long*>(A.replicas), n_img, (int)A.replica_mask + 1, A.replica_stride);
-  } else {
-    hipLaunchKernelGGL(fold_scalars_kernel, dim3(1), dim3(256), 0, stream, acc + n_img, A.partials, n_blocks, (double)A.n_rays);
-    if (A.replica_mask != 0u)
-      hipLaunchKernelGGL(fold_replicas_kernel<double>, dim3((n_img + 255) / 256), dim3(256), 0, stream, acc, A.replicas, n_img,
-                         (int)A.replica_mask + 1, A.replica_stride);
-  }
+  launch_accumulator_folds(A, acc, n_blocks, stream, fixed);
   hipLaunchKernelGGL(K.fold[fixed ? 0 : 1], dim3(n_rows), dim3(64), 0, stream, BD.block, BD.partials, n_blocks);
 }
 int shell_histogram_blocks_per_cu(bool rotated) { return breakdown_blocks_per_cu(kShellKernels, rotated); }
@@ -5120,14 +4935,12 @@ size_t fixed_check_bytes() { return sizeof(FixedCheck); }
 // conservation check, sart_api.hip: status_take)
 std::string fixed_check_describe(const void* host_copy) {
   const FixedCheck& C = *static_cast<const FixedCheck*>(host_copy);
-  constexpr long long kMask = (1ll << kFixedLimbBits) - 1;
-  auto norm = [&](long long lo, long long hi, long long& nlo, long long& nhi) { nhi = hi + (lo >> kFixedLimbBits); nlo = lo & kMask; };
   const char* names[5] = {"pixels", "SUM_WEIGHTS - outside", "radial bins", "energy bins", "SUM_WEIGHTS"};
   std::string s = " [quanta as lo + hi x 2^40:";
   for (int i = 0; i < 5; ++i) {
     if ((i == 2 || i == 3) && !C.spectra) continue;
-    long long lo, hi;
-    norm(C.fail[2 * i], C.fail[2 * i + 1], lo, hi);
+    long long lo = C.fail[2 * i], hi = C.fail[2 * i + 1];
+    limbs_normalise(lo, hi);
     s += std::string(i ? "," : "") + " " + names[i] + " " + std::to_string(lo) + " + " + std::to_string(hi);
   }
   return s + "]";

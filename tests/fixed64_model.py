@@ -315,6 +315,16 @@ def row_sums_exact_mask(raw, n_rows, pairs):
 
 SHELL_PAIRS = ((SHELL_SW, SHELL_SW_HI), (SHELL_SQ, SHELL_SQ_HI))
 CHAN_PAIRS = ((CHAN_SW, CHAN_SW_HI), (CHAN_SQ, CHAN_SQ_HI), (CHAN_OUT, CHAN_OUT_HI))
+# SART_ORIGIN_* / SART_APERTURE_* (the aperture block has the origin block's head and cells): HEAD slots, then cells of CELL slots
+HEAD, CELL = 8, 4
+HEAD_NP, HEAD_SW, HEAD_SQ, HEAD_SW_HI, HEAD_SQ_HI = 0, 1, 2, 4, 5
+CELL_N, CELL_SW, CELL_SQ = 0, 1, 2
+HEAD_PAIRS = ((HEAD_SW, HEAD_SW_HI), (HEAD_SQ, HEAD_SQ_HI))
+# SART_MSPEC_*: cells of MSPEC_CELL slots; the counts block behind the masses' blocks keeps N_ON_DETECTOR in slot MSPEC_N
+MSPEC_CELL = 4
+MSPEC_SW, MSPEC_SQ, MSPEC_SW_HI, MSPEC_SQ_HI = 0, 1, 2, 3
+MSPEC_N = 0
+MSPEC_PAIRS = ((MSPEC_SW, MSPEC_SW_HI), (MSPEC_SQ, MSPEC_SQ_HI))
 
 
 # ---- builders: raw buffers that satisfy every law ---------------------------------------------------------------------------------

@@ -906,3 +906,124 @@ def test_channel_launch_folds_onto_a_crafted_block(chan, carry):
     assert_folded(b_acc, a_acc, c_acc, acc_pairs(sh))
     assert_folded(b_blk, a_blk, c_blk, [(c * 8 + lo, c * 8 + hi) for c in range(t) for lo, hi in M.CHAN_PAIRS])
     assert check_block(chan, "channels", params(False), c_blk, model, M.CHAN_PAIRS, t)[0] == 0
+
+
+TINY = (2, 4)                                                 # the smallest solar tables that build (tests/test_gpu_origin.py)
+
+
+@pytest.fixture(scope="module")
+def tiny():
+    rt = sa.RayTracer(make_setup("babyiaxo_xmm", n_radii=TINY[0], n_energies=TINY[1]))
+    rt.set_accumulation_mode("fixed64")
+    freeze(rt)
+    yield rt
+    rt.close()
+
+
+def crafted_head_block(n_cells, seed, carry):
+    """An origin / aperture block whose cells add up to its head, the head's two low limbs at 2^40 - 1."""
+    rng = np.random.default_rng(seed)
+    blk = [0] * (M.HEAD + n_cells * M.CELL)
+    at = lambda i, j: M.HEAD + i * M.CELL + j
+    for i in range(n_cells):
+        blk[at(i, M.CELL_N)] = M.draw(rng, 1 << 40)
+        blk[at(i, M.CELL_SW)] = M.draw(rng, 1 << 60)
+        blk[at(i, M.CELL_SQ)] = M.draw(rng, 1 << 60)
+    blk[M.HEAD_NP] = sum(blk[at(i, M.CELL_N)] for i in range(n_cells))
+    for (lo, hi), j in zip(M.HEAD_PAIRS, (M.CELL_SW, M.CELL_SQ)):
+        blk[at(1, j)] += 1 << 61                              # high limbs of at least 2^21: room for the carry
+        blk[lo], blk[hi] = M.split_limbs(sum(blk[at(i, j)] for i in range(n_cells)))
+        blk[at(0, j)] += top_pair(blk, lo, hi, carry)
+    assert max(blk) < LIMIT
+    return np.array(blk, dtype=np.int64)
+
+
+@pytest.mark.parametrize("carry", [0, 1 << 20], ids=["normalised", "unnormalised"])
+@pytest.mark.parametrize("which", ["origin", "aperture"])
+def test_head_launch_folds_onto_a_crafted_block(request, which, carry):
+    """The head fold of the origin block, which the aperture block shares; every cell takes the trace's atomics directly."""
+    if which == "origin":
+        rt = request.getfixturevalue("tiny")
+        n_cells = TINY[0] * TINY[1]
+        n_slots, trace, finalize = rt.origin_block_len(), rt.trace_origin_device, rt.finalize_origin_device
+    else:
+        rt = request.getfixturevalue("ctx")
+        rt.set_aperture_grid(3, 2, 0.0, 352.0, -100.0, 250.0)   # a window that leaves rays for the outside cell
+        n_cells = 3 * 2 + 1
+        n_slots, trace, finalize = rt.aperture_block_len(), rt.trace_aperture_device, rt.finalize_aperture_device
+    sh = M.Shape(0, 0)
+    b_acc = crafted_accumulator(sh, 6, carry)
+    b_blk = crafted_head_block(n_cells, 20, carry)
+    assert b_blk.size == n_slots
+    params = lambda acc: rt.shells_params(N_FOLD, seed=25, image_n=0, spectra=False, accumulate=acc)
+    launch = lambda acc, ptrs: trace(params(acc), ptrs[0], ptrs[1])
+    (a_acc, a_blk), (c_acc, c_blk) = fold_through(rt, launch, [sh.total, n_slots], [b_acc, b_blk])
+    cells = a_blk[M.HEAD:].reshape(n_cells, M.CELL)
+    assert cells[:, M.CELL_N].sum() == a_blk[M.HEAD_NP] == a_acc[sh.s0 + M.ACC["N_PASSED"]] > 1000
+    assert (cells[:, M.CELL_N] > 0).sum() >= 4               # (the origin table's first energy has no rays: tests/test_gpu_origin.py)
+    assert_folded(b_acc, a_acc, c_acc, acc_pairs(sh))
+    assert_folded(b_blk, a_blk, c_blk, M.HEAD_PAIRS)
+    d = upload(c_blk)                                         # the finalize's own conservation checks: cells against the head
+    finalize(params(False), d.data_ptr())
+    err = sync(rt)
+    assert err is None, str(err)
+
+
+@pytest.mark.parametrize("carry", [0, 1 << 20], ids=["normalised", "unnormalised"])
+@pytest.mark.parametrize("n_bands", [1, 31])
+def test_banded_scan_launch_folds_onto_crafted_cells(gas, n_bands, carry):
+    """33 masses: a full group of 32 and a group of one; only the first group's launch carries the counts block."""
+    n, n_cells = 33, n_bands + 1
+    xs = np.linspace(0.002, 0.03, n)
+    bands = (30, 240 // n_bands, n_bands)
+    b_rows = crafted_rows(n, M.MASS_COUNTERS, 17, carry)
+    rng = np.random.default_rng(26 + n_bands)
+    spec = [0] * ((n + 1) * n_cells * M.MSPEC_CELL)
+    assert len(spec) == L.mass_scan_spectra_len(n, n_bands)
+    cell = lambda k, c: (k * n_cells + c) * M.MSPEC_CELL
+    pairs = [(cell(k, c) + lo, cell(k, c) + hi) for k in range(n) for c in range(n_cells) for lo, hi in M.MSPEC_PAIRS]
+    for lo, hi in pairs:
+        spec[lo], spec[hi] = M.split_limbs(M.draw(rng, 1 << 60) + (1 << 61))   # high limbs of at least 2^21: room for the carry
+    for k in (0, 31, 32):
+        for c in range(n_cells):
+            for lo, hi in M.MSPEC_PAIRS:
+                top_pair(spec, cell(k, c) + lo, cell(k, c) + hi, carry)
+    for c in range(n_cells):
+        spec[cell(n, c) + M.MSPEC_N] = M.draw(rng, 1 << 60)
+    b_spec = np.array(spec, dtype=np.int64)
+    launch = lambda acc, ptrs: gas.trace_mass_scan_spectra_device(gas.trace_params(N_FOLD, seed=27, accumulate=acc), xs, bands,
+                                                                  ptrs[0], ptrs[1])
+    (a_rows, a_spec), (c_rows, c_spec) = fold_through(gas, launch, [(n + 1) * 8, b_spec.size], [b_rows, b_spec])
+    assert a_rows[n * 8] == N_FOLD and a_rows.reshape(n + 1, 8)[:n, M.SCAN_NP].max() > 100
+    assert_folded(b_rows, a_rows, c_rows, [(k * 8 + lo, k * 8 + hi) for k in range(n) for lo, hi in ((M.SCAN_SW, M.SCAN_SW_HI), (M.SCAN_SQ, M.SCAN_SQ_HI))])
+    assert c_rows[n * 8] == b_rows[n * 8] + N_FOLD
+    # what was traced is a banded scan: the cells of a mass add up to its row, the band counts to N_ON_DETECTOR (slot 4)
+    a = M.ints(a_spec)
+    for k in (0, 31, 32):
+        for (lo, hi), (rlo, rhi) in zip(M.MSPEC_PAIRS, ((M.SCAN_SW, M.SCAN_SW_HI), (M.SCAN_SQ, M.SCAN_SQ_HI))):
+            total = sum(a[cell(k, c) + hi] * TWO40 + a[cell(k, c) + lo] for c in range(n_cells))
+            assert total == int(a_rows[k * 8 + rhi]) * TWO40 + int(a_rows[k * 8 + rlo]), (k, lo)
+    assert sum(a[cell(n, c) + M.MSPEC_N] for c in range(n_cells)) == a_rows[n * 8 + 4] > 100
+    assert_folded(b_spec, a_spec, c_spec, pairs)               # (the counts block: plain sums)
+
+
+@pytest.mark.parametrize("carry", [0, 1 << 20], ids=["normalised", "unnormalised"])
+def test_angular_scan_images_launch_folds_onto_crafted_blocks(ctx, carry):
+    """The scalars of every angle's block go through the scalars fold, once per angle."""
+    sh = shape(8, 8)
+    k_angles = 3
+    angles = np.array(ANGLES[:k_angles])
+    b_rows = crafted_rows(k_angles, M.ANGULAR_COUNTERS, 28, carry)
+    b_blocks = np.concatenate([crafted_accumulator(sh, 30 + k, carry) for k in range(k_angles)])
+    params = lambda acc: ctx.angular_scan_images_params(N_FOLD, seed=29, image_n=8, accumulate=acc)
+    launch = lambda acc, ptrs: ctx.trace_angular_scan_images_device(params(acc), angles, ptrs[0], ptrs[1])
+    (a_rows, a_blocks), (c_rows, c_blocks) = fold_through(ctx, launch, [(k_angles + 1) * 8, k_angles * sh.total], [b_rows, b_blocks])
+    assert a_rows.reshape(k_angles + 1, 8)[:k_angles, M.SCAN_NP].max() > 1000
+    assert_folded(b_rows, a_rows, c_rows, [(k * 8 + lo, k * 8 + hi) for k in range(k_angles) for lo, hi in ((M.SCAN_SW, M.SCAN_SW_HI), (M.SCAN_SQ, M.SCAN_SQ_HI))])
+    for k in range(k_angles):
+        blk = slice(k * sh.total, (k + 1) * sh.total)
+        a = a_blocks[blk]
+        assert a[sh.s0 + M.ACC["N_RAYS"]] == N_FOLD and a[sh.s0 + M.ACC["N_PASSED"]] == a_rows[k * 8 + M.SCAN_NP]
+        assert_folded(b_blocks[blk], a, c_blocks[blk], acc_pairs(sh))
+        assert c_blocks[blk][sh.s0 + M.ACC["N_RAYS"]] == b_blocks[blk][sh.s0 + M.ACC["N_RAYS"]] + N_FOLD
+        assert check_against_model(ctx, sh, c_blocks[blk], in_place_too=False) == 0
