@@ -151,11 +151,14 @@ int64_t sart_emission_oracle_abs_coefs(const sart_solar_zone_t* zones, int32_t n
           int col = -1;
           for (int32_t c = 0; c < t->n_elements; ++c)
             if (t->element_z[c] == Z) col = c;
-          if (col < 0) { outside = 1; break; } /* KeyError of :831 */
+          /* A metal without a column: with the reference's 15 metals listed this cannot happen (the loader refuses a
+           * missing file, the KeyError of :831); a description that lists fewer (sart_emission.h: n_elements is the
+           * caller's) is summed over the columns it has, in the same ascending order. */
+          if (col < 0) continue;
           const int64_t yb = t->table_y_begin[row + (size_t)col], xb = t->table_x_begin[row + (size_t)col];
           const int64_t len = t->table_len[row + (size_t)col];
-          const double* xs = xb < 0 ? line_numbers : t->table_x + xb;
-          if (xb < 0 && len != 10000) { outside = 1; break; }
+          const double* xs = xb < 0 ? line_numbers : t->table_x + xb; /* xb = -1: the line numbers 1 .. len (sart_emission.h) */
+          if (xb < 0 && len > 10000) { outside = 1; break; }
           const double opacity = linear1d_strict(xs, t->table_y + yb, len, table, &outside);
           sum += n_Z[Z] * opacity; /* :834 */
         }
