@@ -218,7 +218,10 @@ struct sart_context {
     int hist_blocks_per_cu = 0;      // SART_HIST_BLOCKS_PER_CU: 0 = occupancy query
     bool no_radial_table = false;    // SART_NO_RADIAL_TABLE: stage A1 of the solar-source histogram kernels decides by its compares, never by the radial verdict table
     int image_tile_max = 0;          // SART_IMAGE_TILE_MAX: upper bound of the LDS image tile's width (0 = what LDS holds); results do not depend on it
+    int a0_wide = 1;                 // SART_A0_WIDE: 0 = one word per pass of stage A0, 1 (or unset) = a0_wide_rule decides, 2 = two words wherever zones exist; results do not depend on it
   } knobs;
+  double a0_wide_survival = -1.0;    // a0_wide_rule's last question and answer (the rule costs a few milliseconds, the zones rarely change)
+  bool a0_wide_on = false;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   std::string device_name;
@@ -904,6 +907,70 @@ void build_zones(const sart_setup_t& s, const DevParams& P, int n_radii, HotA& h
   }
 }
 
+// The share of a launch's rays that stage A0 hands on: the words of the stream are uniform on [0, 2^32) and the zones are disjoint
+// (their radii increase from one to the next), so a ray survives with probability 1 - (sum of the zones' widths) / 2^32.
+double a0_survival_of(const HotA& h) {
+  double covered = 0.0;
+  for (int z = 0; z < h.n_zones; ++z) covered += static_cast<double>(h.zone_hi[z]) - static_cast<double>(h.zone_lo[z]) + 1.0;
+  return std::min(1.0, std::max(0.0, 1.0 - covered / 4294967296.0));
+}
+
+// The wide pass of the histogram kernels' loop (sart_trace_histogram.inc) and when it pays.
+//
+// On an even pass the loop takes a second word of the stream in the same iteration if all of its survivors fit ring 0 behind the
+// first word's; otherwise the word is thrown away after its compares and the next (odd, one-word) pass takes it again: a
+// FALL-BACK, which costs one word's compares and popcounts for nothing, where a wide pass that succeeds saves one whole trip
+// through the loop's glue (the larger part of the two, EXPERIMENTS Part R19 / R20).  Whether fall-backs are rare is a property
+// of the survival rate s alone, and the model is exact: the survivors of a word are Binomial(64, s), independent from word to
+// word (Philox words, disjoint fixed zones), and the ring's fill n at the entry of an even pass is a Markov chain on 0 .. 64:
+//     a, b ~ Binomial(64, s);  n1 = n + a  (always fits: n <= 64)
+//     n1 + b <= 128:  wide pass,   n' = pop(n1 + b)                      with pop(x) = x - 64 if x >= 64, else x
+//     n1 + b  > 128:  fall-back,   n' = pop(pop(n1) + b)                 (the SAME word b, taken by the odd pass)
+// (stage A1 takes 64 entries out per iteration whenever ring 0 holds as many).  The chain is not a plain queue: when the ring
+// runs below 64 entries an iteration passes without a pop, the fill jumps to about 128 s, and the next second word fits only
+// if a + b <= 128 - n - that, not the tail of one binomial against an empty ring, is where the fall-backs at s just below 1/2
+// come from.  For s > 1/2 the inflow of 128 s per wide pass exceeds the 64 that leave, and the fall-backs are what balances them:
+// their share tends to 2 s - 1 of the even passes (0.4 at s = 0.7).  a0_wide_fallback_share returns the stationary share
+// of fall-backs among the even passes (tests/test_a0_wide_model_cpu.py holds it against a simulation of the loop).
+//
+// The rule: wide where the share is at most kA0WideMaxShare = 1/8.  Then, even if a fall-back cost as much as a wide pass saves
+// (it costs less), the loss is below 1/7 of the gain.  The share grows with s; 1/8 is reached near s = 0.56 (the unturned
+// BabyIAXO / XMM setups have s = 0.49: share 0.021; a telescope with the pipes' zone alone has s > 0.9: off).
+constexpr double kA0WideMaxShare = 0.125;
+double a0_wide_fallback_share(double s) {
+  constexpr int W = 64, Q = 2 * W;   // lanes per word; kQueue
+  if (!(s > 0.0)) return 0.0;
+  s = std::min(s, 1.0);
+  double pmf[W + 1];
+  for (int k = 0; k <= W; ++k)
+    pmf[k] = std::exp(std::lgamma(W + 1.0) - std::lgamma(k + 1.0) - std::lgamma(W - k + 1.0) + (k ? k * std::log(s) : 0.0) +
+                      (k < W ? (W - k) * std::log1p(-s) : 0.0));
+  auto pop = [](int x) { return x >= W ? x - W : x; };
+  std::vector<double> T((W + 1) * (W + 1), 0.0), F(W + 1, 0.0);   // T[n][n']: one even pass (with its odd pass after a fall-back)
+  for (int n = 0; n <= W; ++n)
+    for (int a = 0; a <= W; ++a)
+      for (int b = 0; b <= W; ++b) {
+        const double p = pmf[a] * pmf[b];
+        const int n1 = n + a;
+        if (n1 + b <= Q) T[n * (W + 1) + pop(n1 + b)] += p;
+        else { F[n] += p; T[n * (W + 1) + pop(pop(n1) + b)] += p; }
+      }
+  std::vector<double> pi(W + 1, 1.0 / (W + 1)), next(W + 1);
+  for (int it = 0; it < 20000; ++it) {
+    std::fill(next.begin(), next.end(), 0.0);
+    for (int n = 0; n <= W; ++n)
+      for (int m = 0; m <= W; ++m) next[m] += pi[n] * T[n * (W + 1) + m];
+    double d = 0.0;
+    for (int m = 0; m <= W; ++m) d += std::fabs(next[m] - pi[m]);
+    pi.swap(next);
+    if (d < 1e-13) break;
+  }
+  double share = 0.0;
+  for (int n = 0; n <= W; ++n) share += pi[n] * F[n];
+  return share;
+}
+bool a0_wide_rule(double survival) { return a0_wide_fallback_share(survival) <= kA0WideMaxShare; }
+
 // True if every ray from the Sun that survives the three cuts behind the magnetic field (cold-bore exit, two pipe cuts;
 // raytracer.nim:1846-1868) crossed the entrance plane z = 0 inside the bore, i.e. none of them entered through the bore
 // wall (lineIntersectsCylinderOnce, :1825-1843): with |slope| <= s_max a ray that is within R_k of the axis at the plane
@@ -1056,6 +1123,14 @@ int sync_blob(sart_context* c) {
   c->hotb.cdf_stride = c->n_energies + kEnergyCdfPad;
   c->hotb._pad = 0;
   if (!c->knobs.no_early_reject) build_zones(c->setup, c->params, c->n_radii, c->hot, tilt_bound_of(c->setup, c->setup.telescope_turned_y_deg));
+  if (c->hot.n_zones > 0 && c->knobs.a0_wide > 0) {   // the wide pass of the histogram kernels' loop (the fused angular scans keep their loops)
+    const double survival = a0_survival_of(c->hot);
+    if (survival != c->a0_wide_survival) {
+      c->a0_wide_survival = survival;
+      c->a0_wide_on = a0_wide_rule(survival);
+    }
+    if (c->knobs.a0_wide == 2 || c->a0_wide_on) c->hot.zone_reached |= kA0WideMask;
+  }
   c->path_const = path_is_constant(c->params, c->hot, c->n_radii);
   c->blob_dirty = false;
   if (c->spot_may_have_moved) c->tile.valid = false;   // a new axion mass alone (weights only) keeps the tile where it is
@@ -1304,6 +1379,7 @@ int sart_create(int device_ordinal, sart_context** out) {
     c->knobs.hist_blocks_per_cu = number("SART_HIST_BLOCKS_PER_CU");
     c->knobs.no_radial_table = flag("SART_NO_RADIAL_TABLE");
     c->knobs.image_tile_max = number("SART_IMAGE_TILE_MAX");
+    if (const char* e = std::getenv("SART_A0_WIDE")) c->knobs.a0_wide = std::min(2, std::max(0, std::atoi(e)));
   }
   *out = c;
   return 0;
@@ -1637,8 +1713,19 @@ __attribute__((visibility("default"))) int sart_internal_zones(sart_context* c, 
   if (!c || !lo || !hi || !reached_bits) return -1;
   if (hipSetDevice(c->device) != hipSuccess || refresh_derived(c) != 0 || sync_blob(c) != 0) return -1;
   for (int z = 0; z < c->hot.n_zones; ++z) { lo[z] = c->hot.zone_lo[z]; hi[z] = c->hot.zone_hi[z]; }
-  *reached_bits = c->hot.zone_reached;
+  *reached_bits = c->hot.zone_reached & ((1u << kMaxZones) - 1u);
   return c->hot.n_zones;
+}
+
+// Test entries (not in sart.h; no device needed): a0_wide_fallback_share and a0_wide_rule for a survival rate of stage A0, and the
+// switch a launch of this context would carry (HotA::zone_reached, kA0WideMask) with the survival rate its zones leave.
+__attribute__((visibility("default"))) double sart_internal_a0_wide_share(double survival) { return a0_wide_fallback_share(survival); }
+__attribute__((visibility("default"))) int sart_internal_a0_wide_rule(double survival) { return a0_wide_rule(survival) ? 1 : 0; }
+__attribute__((visibility("default"))) int sart_internal_a0_wide(sart_context* c, double* survival) {
+  if (!c || !survival) return -1;
+  if (hipSetDevice(c->device) != hipSuccess || refresh_derived(c) != 0 || sync_blob(c) != 0) return -1;
+  *survival = c->hot.n_zones > 0 ? a0_survival_of(c->hot) : 1.0;
+  return (c->hot.zone_reached >> kA0WideBit) & 1u;
 }
 
 // Test entry (not in sart.h): DevParams::shell0_miss_radius as the next launch would use it (-1: the shortcut is off for this setup).

@@ -178,11 +178,18 @@ struct HotA {
   // radius of the point on the bore exit (r = R sqrt(u3), raytracer.nim:418) lies in zone z if
   // zone_lo[z] <= w <= zone_hi[z]; rays in a zone provably die before the mirrors.  Bit z of zone_reached:
   // they provably pass bore + pipes first (they still count as "reached the telescope").  0 zones: stage off.
+  // Bit kA0WideBit + p of zone_reached (kA0WideMask: p = 0 and 2, the even passes): in pass p the histogram kernels' loop takes two
+  // words of the stream in one iteration where ring 0 has room (sart_trace_histogram.inc: the wide pass; sart_api.hip:
+  // a0_wide_rule decides it per setup).  In this word because the loop reads it once per pass anyway: the switch costs the
+  // kernels no register and no load.
   int32_t n_zones;
   uint32_t zone_reached;
   uint32_t zone_lo[4], zone_hi[4];
 };
 constexpr int kMaxZones = 4;
+constexpr int kA0WideBit = 8;
+constexpr uint32_t kA0WideMask = 0x5u << kA0WideBit;
+static_assert(kA0WideBit >= kMaxZones, "the wide-pass switch lies above the zones' bits");
 
 // What phase B needs as *scalars* at its gathers: the bases of the HBM-resident tables and the sizes their offsets are
 // built from.  Passed by value as a kernel argument and re-read with scalar loads at the start of a phase-B pass, so

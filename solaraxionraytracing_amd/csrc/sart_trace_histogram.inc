@@ -421,36 +421,73 @@
         ZoneTable Z;
         if constexpr (!kZonesInVgprs) reload_zones(Z);
         const uint32_t zone_reached = kZonesInVgprs ? (uint32_t)__builtin_amdgcn_readfirstlane((int)zone_reached_v) : Z.zone_reached;
-        // lane masks of direct compares (v_cmp writes them) and scalar arithmetic on the masks; the final mask becomes the
-        // EXEC mask of the ring write as it is (inverse ballot), with no per-lane 0 / 1 in between
-        uint64_t dead_m = 0, in_first = 0;
+        // One word of the stream against the zones: the lane masks of its survivors (`mask`) and of its dead rays that count as
+        // having reached the telescope (`reached`).  `zr` and `ck` are zone_reached and chunk as the caller holds them: the second
+        // word of a wide pass hands in copies the compiler cannot tell from new values, so that its two wave-uniform tests are a
+        // compare and a branch of their own like the first word's, not lane masks of booleans carried from there (+13 scalar
+        // instructions per iteration when they were, wide pass or not).
+        struct WordMasks { uint64_t mask, reached; };
+        auto a0_masks = [&](uint32_t ww, uint32_t rr, uint32_t zr, uint32_t ck) -> WordMasks {
+          // lane masks of direct compares (v_cmp writes them) and scalar arithmetic on the masks; the final mask becomes the
+          // EXEC mask of the ring write as it is (inverse ballot), with no per-lane 0 / 1 in between
+          uint64_t dead_m = 0, in_first = 0;
 #pragma unroll
-        for (int z = 0; z < kMaxZones; ++z) {   // unused zones are empty: lo > hi
-          const uint64_t in = kZonesInVgprs ? (ballot64(w >= zone_lo_v[z]) & ballot64(w <= zone_hi_v[z]))
-                                            : (ballot64(w >= Z.lo[z]) & ballot64(w <= Z.hi[z]));
-          dead_m |= in;
-          if (z == 0) in_first = in;
-        }
-        // Only the first zone can be one whose rays do not count as having reached the telescope (sart_api.hip: build_zones puts
-        // the zone of kind (a) in front, every zone behind it is of kind (b)): ONE wave-uniform select, not one per zone.
-        const uint64_t reached_m = dead_m & ~((zone_reached & 1u) ? 0ull : in_first);
-        // all four ids of every lane lie inside the launch for every chunk but the first and the last (wave-uniform test)
-        // (only chunk 0 can begin below rel_begin and only chunk n_chunks - 1 can end above rel_end: ONE unsigned compare finds both)
-        uint64_t valid_m = ~0ull;
-        if (chunk - 1u >= n_chunks - 2u) valid_m = ballot64(rel >= rel_begin) & ballot64(rel < rel_end);
-        n_reached += (uint32_t)__popcll(valid_m & reached_m);
+          for (int z = 0; z < kMaxZones; ++z) {   // unused zones are empty: lo > hi
+            const uint64_t in = kZonesInVgprs ? (ballot64(ww >= zone_lo_v[z]) & ballot64(ww <= zone_hi_v[z]))
+                                              : (ballot64(ww >= Z.lo[z]) & ballot64(ww <= Z.hi[z]));
+            dead_m |= in;
+            if (z == 0) in_first = in;
+          }
+          // Only the first zone can be one whose rays do not count as having reached the telescope (sart_api.hip: build_zones puts
+          // the zone of kind (a) in front, every zone behind it is of kind (b)): ONE wave-uniform select, not one per zone.
+          const uint64_t reached_m = dead_m & ~((zr & 1u) ? 0ull : in_first);
+          // all four ids of every lane lie inside the launch for every chunk but the first and the last (wave-uniform test)
+          // (only chunk 0 can begin below rel_begin and only chunk n_chunks - 1 can end above rel_end: ONE unsigned compare finds both)
+          uint64_t valid_m = ~0ull;
+          if (ck - 1u >= n_chunks - 2u) valid_m = ballot64(rr >= rel_begin) & ballot64(rr < rel_end);
 #ifdef SART_DEBUG_KNOBS
-        const uint64_t mask = (A.flags & 0x20000000u) ? 0ull : (valid_m & ~dead_m);   // experiment: nothing reaches stage A1
+          const uint64_t mask = (A.flags & 0x20000000u) ? 0ull : (valid_m & ~dead_m);   // experiment: nothing reaches stage A1
 #else
-        const uint64_t mask = valid_m & ~dead_m;
+          const uint64_t mask = valid_m & ~dead_m;
 #endif
-        if (__builtin_amdgcn_inverse_ballot_w64(mask)) {
-          asm volatile("; hot: ring 0 write");
-          const uint32_t slot = prefix_from(mask, t0) % kQueue;
-          Q.w[wave].ray[slot] = rel;
-          Q.w[wave].u3hi[slot] = w;
+          return WordMasks{mask, valid_m & reached_m};
+        };
+        auto ring0_push = [&](uint64_t mask, uint32_t ww, uint32_t rr) {   // the survivors' ids and words behind what ring 0 holds, in lane order
+          if (__builtin_amdgcn_inverse_ballot_w64(mask)) {
+            asm volatile("; hot: ring 0 write");
+            const uint32_t slot = prefix_from(mask, t0) % kQueue;
+            Q.w[wave].ray[slot] = rr;
+            Q.w[wave].u3hi[slot] = ww;
+          }
+          t0 += (uint32_t)__popcll(mask);
+        };
+        // Invariant: ring 0 holds n0 = t0 - h0 <= 64 entries here (the glue below takes 64 out whenever it holds 64 or more, and an
+        // iteration puts in at most kQueue - n0), so the first word's <= 64 survivors always fit its kQueue = 128 slots.
+        const WordMasks wa = a0_masks(w, rel, zone_reached, chunk);
+        n_reached += (uint32_t)__popcll(wa.reached);
+        ring0_push(wa.mask, w, rel);
+        // The wide pass (HotA::zone_reached bits kA0WideBit + 0 and + 2, set by the host where the zones retire enough rays:
+        // sart_api.hip, a0_wide_rule; bit kA0WideBit + pass: ONE shift and test says "switched on and an even pass"): the lane's
+        // next word - id rel + 1 - goes through the same compares in the same iteration, BEHIND the first word's ring write, if
+        // ring 0 has room for all of its survivors; one trip through the glue below then serves 128 ids.  If it has not,
+        // nothing of the word is counted or written and the next pass - an odd one, never wide - takes it as its one word: every
+        // id enters ring 0 once, in the order of the one-word loop, and stage A1 pops the same 64 entries [64 j, 64 j + 64)
+        // either way.  The loop ends: every iteration with input takes at least one word.
+        if ((zone_reached >> (pass + (uint32_t)kA0WideBit)) & 1u) {   // wave-uniform
+          uint32_t zr = zone_reached, ck = chunk;
+          asm volatile("" : "+s"(zr), "+s"(ck));
+          const uint32_t wb = stream.x;
+          const WordMasks mb = a0_masks(wb, rel + 1u, zr, ck);
+          if ((t0 - h0) + (uint32_t)__popcll(mb.mask) <= (uint32_t)kQueue) {
+            n_reached += (uint32_t)__popcll(mb.reached);
+            ring0_push(mb.mask, wb, rel + 1u);
+            stream.x = stream.y; stream.y = stream.z; stream.z = stream.w;
+            pass += 1u;   // (even before: no carry out of the two bits)
+          }
+          // (else - rare: the second word does not fit ring 0 and the next, one-word pass takes it again.  No block with a marker
+          // of its own: an `else` that holds one turns the test above into a lane mask of a boolean and a second branch on it, three
+          // scalar instructions in every wide pass; the fall-back itself has nothing to execute.)
         }
-        t0 += (uint32_t)__popcll(mask);
       } else {
         run_phase_a(rel, (rel >= rel_begin) & (rel < rel_end), w);   // no early-rejection stage for this configuration
       }
