@@ -43,12 +43,9 @@ bool launch_trace_mass_scan_spectra(const HotA& H, const HotB& HB, const DevBlob
 int mass_scan_spectra_blocks_per_cu(int variant);
 void launch_finalize_scan_bands(const void* rows, const void* shared_row, const void* in, double* out, const void* counts_in, double* counts_out,
                                 int n_masses, int n_cells, const double* q_w, const double* q_w2, void* check_dev, hipStream_t stream);
-void launch_trace_angular_scan(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, const AScanArgs& AN, double* rows,
-                               double* shared_row, int n_blocks, hipStream_t stream, bool fast, bool fixed);
-int angular_scan_blocks_per_cu(bool fast);
-void launch_ascan_images(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, const AScanArgs& AN, double* img_partials,
-                         double* rows, double* shared_row, int n_blocks, hipStream_t stream, bool fast, bool fixed);
-int ascan_images_blocks_per_cu(bool fast);
+void launch_trace_angular_scan(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, const AScanArgs& AN, double* img_partials,
+                               double* rows, double* shared_row, int n_blocks, hipStream_t stream, bool images, bool fast, bool fixed);
+int angular_scan_blocks_per_cu(bool images, bool fast);
 int energy_scan_blocks_per_cu(bool rotated);
 void launch_trace_energy_scan(const HotA& H, const HotB& HB, const DevBlob* blob, const TraceArgs& A, const EScanArgs& EN, double* rows,
                               double* shared_row, int n_blocks, hipStream_t stream, bool rotated, bool fixed);
@@ -198,7 +195,8 @@ size_t lower_bound_idx(const double* a, size_t n, double key) {
 struct sart_context {
   int device = 0;
   int n_cu = 0;
-  int blocks_per_cu_hist[7] = {0, 0, 0, 0, 0, 0, 0}, blocks_per_cu_rec = 0, blocks_per_cu_ascan[2] = {0, 0};
+  int blocks_per_cu_hist[7] = {0, 0, 0, 0, 0, 0, 0}, blocks_per_cu_rec = 0;
+  int blocks_per_cu_ascan[2][2] = {{0, 0}, {0, 0}};   // fused angular scan: [images][fast]
   // tuning / experiment knobs, read from the environment once when the context is created
   struct Knobs {
 #ifdef SART_DEBUG_KNOBS              // experiment builds only (make DEBUG_KNOBS=1); compiled out of the shipped library
@@ -310,7 +308,6 @@ struct sart_context {
   DevBuf<double> d_ascan_partials;   // fused angular scan: per-workgroup per-angle partial sums
   DevBuf<double> d_aimg_partials;    // ... with images: per-angle per-workgroup scalars
   DevBuf<double> d_aimg;             // ... scratch blocks of the blocking form
-  int blocks_per_cu_aimg[2] = {0, 0};
   // fused energy scan: the per-energy tables of the last call's energies (energy_row_of / refl_rows_of, built beside the context's
   // own tables, which they do not touch), reused while the energies and the context's tables stay the same
   uint64_t tables_gen = 0;           // bumped whenever refresh_derived rebuilds the context's tables
@@ -3412,15 +3409,82 @@ AScanAngle ascan_angle_of(const sart_context* c, double angle_y_deg) {
   return a;
 }
 
+int ascan_angles_check(const double* turned_y_deg, int32_t n_angles) {
+  for (int32_t k = 0; k < n_angles; ++k)
+    if (!std::isfinite(turned_y_deg[k]) || !(std::fabs(turned_y_deg[k]) < 90.0))
+      return fail(SART_ERR_INVALID_ARGUMENT, "telescope angles must be finite and inside (-90, 90) degrees");
+  return 0;
+}
+
+// The launches of sart_trace_angular_scan_device (blocks_dev == nullptr) and sart_trace_angular_scan_images_device (blocks_dev: the
+// angles' accumulator blocks of block_len doubles each) for the prepared arguments `a`: the rays in pieces, the angles in launch groups.
+int ascan_launch(sart_context* c, const sart_trace_params_t* p, TraceArgs a, const double* turned_y_deg, int32_t n_angles, double* scan_dev,
+                 double* blocks_dev, size_t block_len) {
+  if (p->n_rays == 0) return 0;
+  const bool images = blocks_dev != nullptr, fixed = c->accum_mode == SART_ACCUM_FIXED64;
+  const DevParams& P = c->params;
+  const bool fast = !P.test_active && !(P.telescope_kind == SART_TK_XMM && P.inner_blocks < 0) && !c->knobs.force_generic && !P.stage_gas;
+  // Stage A0 for a telescope that is turned through several angles: the cuts behind the field do not depend on the angle; the
+  // zones in terms of the radial distance at the entrance (inner disc, ring, beyond the last shell) are built per launch group
+  // with the margin of its largest tilt (build_zones) - a ray inside one of them is dead at EVERY angle of the group and is never
+  // sampled, stashed or turned.
+  HotA hot = c->hot;
+  hot.rotated = 1;
+  int& bpc = c->blocks_per_cu_ascan[images ? 1 : 0][fast ? 1 : 0];
+  if (bpc == 0) {
+    bpc = std::max(1, angular_scan_blocks_per_cu(images, fast));
+    if (c->knobs.hist_blocks_per_cu > 0) bpc = c->knobs.hist_blocks_per_cu;
+  }
+  const int32_t n_groups = (n_angles + kAScanMaxAngles - 1) / kAScanMaxAngles;
+  a.partials = nullptr;
+  for (uint64_t done = 0; done < p->n_rays;) {   // ray indices inside one launch are 32-bit: pieces of at most 2^31 rays
+    const uint64_t n = std::min<uint64_t>(p->n_rays - done, 1ull << 31);
+    a.n_rays = n;
+    a.ray_id_offset = p->ray_id_offset + done;
+    const int n_blocks = grid_for(n, c->n_cu, bpc, 1024);
+    if (c->d_ascan_partials.n < static_cast<size_t>(n_blocks) * kAScanMaxAngles * kAScanPartialSlots ||
+        (images && c->d_aimg_partials.n < static_cast<size_t>(n_blocks) * kAScanMaxAngles * SART_ACC_COUNT)) {
+      SART_HIP(hipStreamSynchronize(c->stream));
+      const size_t rows_need = std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4);
+      if (int rc = c->d_ascan_partials.reserve(rows_need * kAScanMaxAngles * kAScanPartialSlots)) return rc;
+      if (images)
+        if (int rc = c->d_aimg_partials.reserve(rows_need * kAScanMaxAngles * SART_ACC_COUNT)) return rc;
+    }
+    for (int32_t g = 0, k0 = 0; g < n_groups; ++g) {   // balanced groups: sizes differ by at most one
+      AScanArgs an;
+      std::memset(&an, 0, sizeof an);
+      an.n_angles = n_angles / n_groups + (g < n_angles % n_groups ? 1 : 0);
+      an.partials = c->d_ascan_partials.p;
+      double tilt_max = 0.0;
+      for (int k = 0; k < an.n_angles; ++k) {
+        an.a[k] = ascan_angle_of(c, turned_y_deg[k0 + k]);
+        const double t = tilt_bound_of(c->setup, turned_y_deg[k0 + k]);
+        tilt_max = (t < 0.0 || tilt_max < 0.0) ? -1.0 : std::max(tilt_max, t);
+      }
+      if (!c->knobs.no_early_reject) build_zones(c->setup, P, c->n_radii, hot, tilt_max);
+      double* const rows = scan_dev + static_cast<size_t>(k0) * SART_ASCAN_ROW;
+      double* const shared = (k0 == 0) ? scan_dev + static_cast<size_t>(n_angles) * SART_ASCAN_ROW : nullptr;   // counters: once per piece
+      if (images) a.replicas = blocks_dev + static_cast<size_t>(k0) * block_len;   // the group's first block; angle k of the group: + k block_len
+      {
+        TimedLaunch tl(c);
+        launch_trace_angular_scan(hot, c->hotb, c->d_blob.p, a, an, images ? c->d_aimg_partials.p : nullptr, rows, shared, n_blocks, c->stream,
+                                  images, fast, fixed);
+      }
+      SART_HIP(hipGetLastError());
+      k0 += an.n_angles;
+    }
+    done += n;
+  }
+  return 0;
+}
+
 }  // namespace
 
 int sart_trace_angular_scan_device(sart_context* c, const sart_trace_params_t* p, const double* turned_y_deg, int32_t n_angles,
                                    double* scan_dev) {
   if (int rc = ascan_check(c, p, n_angles)) return rc;
   if (!turned_y_deg || !scan_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
-  for (int32_t k = 0; k < n_angles; ++k)
-    if (!std::isfinite(turned_y_deg[k]) || !(std::fabs(turned_y_deg[k]) < 90.0))
-      return fail(SART_ERR_INVALID_ARGUMENT, "telescope angles must be finite and inside (-90, 90) degrees");
+  if (int rc = ascan_angles_check(turned_y_deg, n_angles)) return rc;
   SART_HIP(hipSetDevice(c->device));
   if (int rc = refresh_derived(c)) return rc;
   if (int rc = sync_blob(c)) return rc;
@@ -3440,57 +3504,7 @@ int sart_trace_angular_scan_device(sart_context* c, const sart_trace_params_t* p
     a.fx_scale_w2 = std::ldexp(1.0, -qe.w2);
   }
   if (!p->accumulate) SART_HIP(hipMemsetAsync(scan_dev, 0, sart_angular_scan_len(n_angles) * sizeof(double), c->stream));
-  if (p->n_rays == 0) return 0;
-  const DevParams& P = c->params;
-  const bool fast = !P.test_active && !(P.telescope_kind == SART_TK_XMM && P.inner_blocks < 0) && !c->knobs.force_generic && !P.stage_gas;
-  // Stage A0 for a telescope that is turned through several angles: the cuts behind the field do not depend on the angle; the
-  // zones in terms of the radial distance at the entrance (inner disc, ring, beyond the last shell) are built per launch group
-  // with the margin of its largest tilt (build_zones) - a ray inside one of them is dead at EVERY angle of the group and is never
-  // sampled, stashed or turned.
-  HotA hot = c->hot;
-  hot.rotated = 1;
-  int& bpc = c->blocks_per_cu_ascan[fast ? 1 : 0];
-  if (bpc == 0) {
-    bpc = std::max(1, angular_scan_blocks_per_cu(fast));
-    if (c->knobs.hist_blocks_per_cu > 0) bpc = c->knobs.hist_blocks_per_cu;
-  }
-  const int32_t n_groups = (n_angles + kAScanMaxAngles - 1) / kAScanMaxAngles;
-  for (uint64_t done = 0; done < p->n_rays;) {   // ray indices inside one launch are 32-bit: pieces of at most 2^31 rays
-    const uint64_t n = std::min<uint64_t>(p->n_rays - done, 1ull << 31);
-    a.n_rays = n;
-    a.ray_id_offset = p->ray_id_offset + done;
-    const int n_blocks = grid_for(n, c->n_cu, bpc, 1024);
-    const size_t need = static_cast<size_t>(n_blocks) * kAScanMaxAngles * kAScanPartialSlots;
-    if (c->d_ascan_partials.n < need) {
-      SART_HIP(hipStreamSynchronize(c->stream));
-      const size_t rows = std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4);
-      if (int rc = c->d_ascan_partials.resize(rows * kAScanMaxAngles * kAScanPartialSlots)) return rc;
-    }
-    a.partials = nullptr;
-    for (int32_t g = 0, k0 = 0; g < n_groups; ++g) {   // balanced groups: sizes differ by at most one
-      AScanArgs an;
-      std::memset(&an, 0, sizeof an);
-      an.n_angles = n_angles / n_groups + (g < n_angles % n_groups ? 1 : 0);
-      an.partials = c->d_ascan_partials.p;
-      double tilt_max = 0.0;
-      for (int k = 0; k < an.n_angles; ++k) {
-        an.a[k] = ascan_angle_of(c, turned_y_deg[k0 + k]);
-        const double t = tilt_bound_of(c->setup, turned_y_deg[k0 + k]);
-        tilt_max = (t < 0.0 || tilt_max < 0.0) ? -1.0 : std::max(tilt_max, t);
-      }
-      if (!c->knobs.no_early_reject) build_zones(c->setup, P, c->n_radii, hot, tilt_max);
-      double* const rows = scan_dev + static_cast<size_t>(k0) * SART_ASCAN_ROW;
-      double* const shared = (k0 == 0) ? scan_dev + static_cast<size_t>(n_angles) * SART_ASCAN_ROW : nullptr;   // counters: once per piece
-      {
-        TimedLaunch tl(c);
-        launch_trace_angular_scan(hot, c->hotb, c->d_blob.p, a, an, rows, shared, n_blocks, c->stream, fast, fixed);
-      }
-      SART_HIP(hipGetLastError());
-      k0 += an.n_angles;
-    }
-    done += n;
-  }
-  return 0;
+  return ascan_launch(c, p, a, turned_y_deg, n_angles, scan_dev, nullptr, 0);
 }
 
 int sart_finalize_angular_scan_device(sart_context* c, const sart_trace_params_t* p, int32_t n_angles, const void* raw_dev, double* out_dev) {
@@ -3549,9 +3563,7 @@ int aimg_check(sart_context* c, const sart_trace_params_t* p, const double* turn
   if (!turned_y_deg || !scan || !blocks) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
   if (p->image_nx < 1 || p->image_ny < 1)
     return fail(SART_ERR_INVALID_ARGUMENT, "the image scan needs image_nx, image_ny >= 1 (the flux-only scan is sart_trace_angular_scan)");
-  for (int32_t k = 0; k < n_angles; ++k)
-    if (!std::isfinite(turned_y_deg[k]) || !(std::fabs(turned_y_deg[k]) < 90.0))
-      return fail(SART_ERR_INVALID_ARGUMENT, "telescope angles must be finite and inside (-90, 90) degrees");
+  if (int rc = ascan_angles_check(turned_y_deg, n_angles)) return rc;
   if (p->spectra && (p->n_radial_bins < 1 || !c->have_solar)) return fail(SART_ERR_INVALID_ARGUMENT, "invalid spectra specification");
   if (acc_len_of(c, p) > 0xFFFFFFFFull) return fail(SART_ERR_INVALID_ARGUMENT, "accumulator block too large for the image scan");
   return 0;
@@ -3587,57 +3599,9 @@ int sart_trace_angular_scan_images_device(sart_context* c, const sart_trace_para
     SART_HIP(hipMemsetAsync(scan_dev, 0, sart_angular_scan_len(n_angles) * sizeof(double), c->stream));
     SART_HIP(hipMemsetAsync(blocks_dev, 0, static_cast<size_t>(n_angles) * block_len * sizeof(double), c->stream));
   }
-  if (p->n_rays == 0) return 0;
-  const DevParams& P = c->params;
-  const bool fast = !P.test_active && !(P.telescope_kind == SART_TK_XMM && P.inner_blocks < 0) && !c->knobs.force_generic && !P.stage_gas;
-  HotA hot = c->hot;   // stage A0 zones per launch group, as in sart_trace_angular_scan_device
-  hot.rotated = 1;
-  int& bpc = c->blocks_per_cu_aimg[fast ? 1 : 0];
-  if (bpc == 0) {
-    bpc = std::max(1, ascan_images_blocks_per_cu(fast));
-    if (c->knobs.hist_blocks_per_cu > 0) bpc = c->knobs.hist_blocks_per_cu;
-  }
-  const int32_t n_groups = (n_angles + kAScanMaxAngles - 1) / kAScanMaxAngles;
   a.replica_mask = 0u;
   a.replica_stride = static_cast<uint32_t>(block_len);
-  a.partials = nullptr;
-  for (uint64_t done = 0; done < p->n_rays;) {   // pieces of at most 2^31 rays (32-bit ray indices inside a launch)
-    const uint64_t n = std::min<uint64_t>(p->n_rays - done, 1ull << 31);
-    a.n_rays = n;
-    a.ray_id_offset = p->ray_id_offset + done;
-    const int n_blocks = grid_for(n, c->n_cu, bpc, 1024);
-    const size_t rows_need = std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4);
-    if (c->d_ascan_partials.n < static_cast<size_t>(n_blocks) * kAScanMaxAngles * kAScanPartialSlots ||
-        c->d_aimg_partials.n < static_cast<size_t>(n_blocks) * kAScanMaxAngles * SART_ACC_COUNT) {
-      SART_HIP(hipStreamSynchronize(c->stream));
-      if (int rc = c->d_ascan_partials.reserve(rows_need * kAScanMaxAngles * kAScanPartialSlots)) return rc;
-      if (int rc = c->d_aimg_partials.reserve(rows_need * kAScanMaxAngles * SART_ACC_COUNT)) return rc;
-    }
-    for (int32_t g = 0, k0 = 0; g < n_groups; ++g) {   // balanced groups, as in the flux-only scan
-      AScanArgs an;
-      std::memset(&an, 0, sizeof an);
-      an.n_angles = n_angles / n_groups + (g < n_angles % n_groups ? 1 : 0);
-      an.partials = c->d_ascan_partials.p;
-      double tilt_max = 0.0;
-      for (int k = 0; k < an.n_angles; ++k) {
-        an.a[k] = ascan_angle_of(c, turned_y_deg[k0 + k]);
-        const double t = tilt_bound_of(c->setup, turned_y_deg[k0 + k]);
-        tilt_max = (t < 0.0 || tilt_max < 0.0) ? -1.0 : std::max(tilt_max, t);
-      }
-      if (!c->knobs.no_early_reject) build_zones(c->setup, P, c->n_radii, hot, tilt_max);
-      double* const rows = scan_dev + static_cast<size_t>(k0) * SART_ASCAN_ROW;
-      double* const shared = (k0 == 0) ? scan_dev + static_cast<size_t>(n_angles) * SART_ASCAN_ROW : nullptr;
-      a.replicas = blocks_dev + static_cast<size_t>(k0) * block_len;   // the group's first block; angle k of the group: + k block_len
-      {
-        TimedLaunch tl(c);
-        launch_ascan_images(hot, c->hotb, c->d_blob.p, a, an, c->d_aimg_partials.p, rows, shared, n_blocks, c->stream, fast, fixed);
-      }
-      SART_HIP(hipGetLastError());
-      k0 += an.n_angles;
-    }
-    done += n;
-  }
-  return 0;
+  return ascan_launch(c, p, a, turned_y_deg, n_angles, scan_dev, blocks_dev, block_len);
 }
 
 int sart_trace_angular_scan_images(sart_context* c, const sart_trace_params_t* p, const double* turned_y_deg, int32_t n_angles,

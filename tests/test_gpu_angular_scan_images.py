@@ -126,6 +126,43 @@ def test_one_launch_group_equals_single_launches(k):
             assert_block_equals_single(blocks[j], raw_single(rt, torch, a, n, seed, 0, None, False), (k, j))
 
 
+@pytest.mark.parametrize("knobs", [{}, {"SART_FORCE_GENERIC": "1"}], ids=["default", "generic"])
+def test_flux_and_image_scans_alternating_on_one_context_equal_fresh_contexts(knobs):
+    """The two entry points share the launch path, the grid cache and the per-workgroup scratch of a context: either one first,
+    more angles or fewer than the call before, every call writes what it writes alone on a fresh context."""
+    import torch
+    full = make_setup("babyiaxo_xmm")
+    many, few = mixed_angles(35, 0.4), mixed_angles(3, 0.4)   # two launch groups (18 + 17) and one
+    seed, off = 17, 1000
+    calls = [   # (with images, angles, rays, spectra); the ray counts are off the 64 and 256 grids
+        (False, many, 200_003, False),
+        (True, few, 100_001, True),
+        (False, few, 100_001, False),
+        (True, many, 200_003, False),
+    ]
+
+    def run(rt, images, an, n, spectra):
+        if images:
+            return raw_images(rt, torch, an, [(off, off + n)], seed, None, spectra)
+        return (raw_scan(rt, torch, an, [(off, off + n)], seed),)
+
+    with env(**knobs):
+        with sa.RayTracer(full) as rt:
+            rt.set_accumulation_mode("fixed64")
+            shared = [run(rt, *call) for call in calls]
+        alone = []
+        for call in calls:
+            with sa.RayTracer(full) as rt:
+                rt.set_accumulation_mode("fixed64")
+                alone.append(run(rt, *call))
+    for j, (got, want) in enumerate(zip(shared, alone)):
+        assert len(got) == len(want)
+        for g, w in zip(got, want):
+            assert g.dtype == np.int64 and np.array_equal(g, w), j
+    assert np.array_equal(shared[1][0], shared[2][0])   # the image scan's rows are the flux-only scan's
+    assert shared[0][0][:-1, L.ASCAN["N_PASSED"]].max() > 100 and shared[3][1][:, :N_IMG].any()   # (the calls traced something)
+
+
 def test_angle_zero_agrees_with_the_unrotated_launch():
     """Turned x = y = 0: the single launch runs the unrotated kernel (an exact frame change where the rotation by 0 rounds)."""
     full = make_setup("babyiaxo_xmm")
