@@ -1270,6 +1270,100 @@ struct TimedLaunch {
   ~TimedLaunch() { if (stop) (void)hipEventRecord(stop, c->stream); }
 };
 
+// One launch of a ray kernel of records_block() threads for the rays of p (trace_records_kernel, columns_stage_kernel): the
+// setup brought up to date, the launch arguments, the grid.  launch(args, n_blocks) enqueues the kernel on the context's stream,
+// between the timing events when timing is on; it is not called for zero rays.
+template <class Launch>
+int launch_record_rays(sart_context* c, const sart_trace_params_t* p, Launch&& launch) {
+  if (int rc = refresh_derived(c)) return rc;
+  if (int rc = sync_blob(c)) return rc;
+  TraceArgs a;
+  if (int rc = make_args(c, p, a)) return rc;
+  if (a.n_rays == 0) return 0;
+  if (c->blocks_per_cu_rec == 0) c->blocks_per_cu_rec = 4;
+  TimedLaunch tl(c);
+  launch(a, grid_for(a.n_rays, c->n_cu, c->blocks_per_cu_rec, records_block()));
+  return 0;
+}
+
+// ---- the chunk pipeline of the three blocking record doors (sart_trace_records, _records_passed, _columns_passed) -----------
+// The first HIP error of a pipeline and the step it came from; step(e, name) is true when e is no error.
+struct HipLatch {
+  hipError_t err = hipSuccess;
+  const char* what = "";
+  bool operator()(hipError_t e, const char* name) {
+    if (e != hipSuccess && err == hipSuccess) { err = e; what = name; }
+    return e == hipSuccess;
+  }
+};
+// The rays of p in chunks of `chunk`, two streams, two half-buffers: chunk k is produced into half-buffer b = k & 1 on the
+// context's stream while chunk k - 1 leaves half-buffer (k - 1) & 1 for the caller's memory on copy_stream.
+//   produce(q, b, step)           traces (and compacts) the rays of q into half-buffer b on c->stream; returns a sart error code
+//   consume(j, b, traced, step)   waits for `traced` (chunk j is complete in half-buffer b) in the way its door needs, and
+//                                 enqueues the copies of chunk j on c->copy_stream
+// Both report HIP errors through step and go on to nothing after one.  What holds here, once, for every door:
+//   - From the first enqueue that names the caller's buffer until both streams are synchronised there is no `return` and no
+//     SART_HIP early exit: kernels and copies into the CALLER's buffer are queued on two streams, and the caller may free or
+//     reuse that buffer the moment the call returns.  Every step records its error and breaks; both streams are synchronised
+//     on every way out.  (The stream and the events are created before the loop, where nothing is queued yet.)
+//   - The first error wins: the sart code of a producer, else the first HIP error with its step, else a synchronise error.
+//   - The doors check their arguments, zero the caller's counts and reserve their scratch before they come here; the scratch is
+//     theirs (grow-only, one half-buffer when one chunk does it), this function allocates nothing on the device.
+// SART_RECORDS_FAIL_CHUNK=k (test hook): the k-th chunk fails instead of being produced.
+template <class Produce, class Consume>
+int record_chunk_pipeline(sart_context* c, const char* entry, const sart_trace_params_t* p, uint64_t chunk, Produce&& produce,
+                          Consume&& consume) {
+  if (!c->copy_stream) SART_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+  for (int k = 0; k < 2; ++k) {
+    if (!c->rec_traced[k]) SART_HIP(hipEventCreateWithFlags(&c->rec_traced[k], hipEventDisableTiming));
+    if (!c->rec_copied[k]) SART_HIP(hipEventCreateWithFlags(&c->rec_copied[k], hipEventDisableTiming));
+  }
+  const uint64_t n = p->n_rays, n_chunks = (n + chunk - 1) / chunk;
+  sart_trace_params_t q = *p;
+  int rc = 0;
+  HipLatch step;
+  for (uint64_t k = 0; k <= n_chunks && rc == 0 && step.err == hipSuccess; ++k) {
+    if (k < n_chunks) {   // chunk k into half-buffer k & 1 once the copies of chunk k - 2 have left it
+      const int b = static_cast<int>(k & 1);
+      if (k >= 2 && !step(hipStreamWaitEvent(c->stream, c->rec_copied[b], 0), "hipStreamWaitEvent(stream)")) break;
+      q.n_rays = std::min(chunk, n - k * chunk);
+      q.ray_id_offset = p->ray_id_offset + k * chunk;
+      rc = (c->knobs.records_fail_chunk > 0 && k + 1 == static_cast<uint64_t>(c->knobs.records_fail_chunk))
+               ? fail(SART_ERR_INTERNAL, std::string(entry) + ": failure injected by SART_RECORDS_FAIL_CHUNK (test hook)")
+               : produce(q, b, step);
+      if (rc || step.err != hipSuccess) break;
+      if (!step(hipEventRecord(c->rec_traced[b], c->stream), "hipEventRecord(traced)")) break;
+    }
+    if (k > 0) {          // chunk k - 1 crosses PCIe while chunk k is traced (the copies may block the host: pageable destination)
+      const int b = static_cast<int>((k - 1) & 1);
+      consume(k - 1, b, c->rec_traced[b], step);
+      if (step.err != hipSuccess) break;
+      if (!step(hipEventRecord(c->rec_copied[b], c->copy_stream), "hipEventRecord(copied)")) break;
+    }
+  }
+  const hipError_t e1 = hipStreamSynchronize(c->copy_stream), e2 = hipStreamSynchronize(c->stream);
+  if (rc) return rc;
+  if (step.err != hipSuccess) return fail(SART_ERR_NO_DEVICE, std::string(entry) + ": " + step.what + ": " + hipGetErrorString(step.err));
+  if (e1 != hipSuccess || e2 != hipSuccess) return fail(SART_ERR_NO_DEVICE, std::string(entry) + ": " + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+  return 0;
+}
+
+// The chunk loop of the two _device doors: counts_dev zeroed unless the launch accumulates, the scratch for the largest chunk,
+// then one_chunk(q) for the rays of each chunk, all on the context's stream.
+template <class Scratch, class Chunk>
+int device_chunks(sart_context* c, const sart_trace_params_t* p, uint64_t* counts_dev, uint64_t chunk, Scratch&& scratch, Chunk&& one_chunk) {
+  if (!p->accumulate) SART_HIP(hipMemsetAsync(counts_dev, 0, 4 * sizeof(uint64_t), c->stream));
+  if (p->n_rays == 0) return 0;
+  if (int rc = scratch(std::min<uint64_t>(chunk, p->n_rays))) return rc;
+  sart_trace_params_t q = *p;
+  for (uint64_t done = 0; done < p->n_rays; done += chunk) {
+    q.n_rays = std::min(chunk, p->n_rays - done);
+    q.ray_id_offset = p->ray_id_offset + done;
+    if (int rc = one_chunk(q)) return rc;
+  }
+  return 0;
+}
+
 }  // namespace
 
 // FIXED64 status word (sart_kernels.hip: kFixedStatus*).  ensure: allocates it; enqueue_copy: behind a finalize kernel, the
@@ -1669,17 +1763,10 @@ int sart_set_detector_tables(sart_context* c, const double* sbx, const double* s
 static int trace_records_impl(sart_context* c, const sart_trace_params_t* p, sart_axion_t* out_dev, const double* uniforms_dev) {
   if (!c || !out_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
   SART_HIP(hipSetDevice(c->device));
-  if (int rc = refresh_derived(c)) return rc;
-  if (int rc = sync_blob(c)) return rc;
-  TraceArgs a;
-  if (int rc = make_args(c, p, a)) return rc;
-  if (a.n_rays == 0) return 0;
-  if (c->blocks_per_cu_rec == 0) c->blocks_per_cu_rec = 4;
-  {
-    TimedLaunch tl(c);
-    launch_trace_records(c->hot, c->hotb, c->d_blob.p, a, out_dev,
-                         grid_for(a.n_rays, c->n_cu, c->blocks_per_cu_rec, records_block()), c->stream, uniforms_dev);
-  }
+  if (int rc = launch_record_rays(c, p, [&](const TraceArgs& a, int n_blocks) {
+        launch_trace_records(c->hot, c->hotb, c->d_blob.p, a, out_dev, n_blocks, c->stream, uniforms_dev);
+      }))
+    return rc;
   SART_HIP(hipGetLastError());
   return 0;
 }
@@ -1917,50 +2004,19 @@ int sart_trace_records(sart_context* c, const sart_trace_params_t* p, sart_axion
   }
   if (int rc = c->d_rec.reserve(chunk)) return rc;
   if (int rc = c->d_rec2.reserve(chunk)) return rc;
-  if (!c->copy_stream) SART_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-  for (int k = 0; k < 2; ++k) {
-    if (!c->rec_traced[k]) SART_HIP(hipEventCreateWithFlags(&c->rec_traced[k], hipEventDisableTiming));
-    if (!c->rec_copied[k]) SART_HIP(hipEventCreateWithFlags(&c->rec_copied[k], hipEventDisableTiming));
-  }
   sart_axion_t* const bufs[2] = {c->d_rec.p, c->d_rec2.p};
-  const uint64_t n_chunks = (n + chunk - 1) / chunk;
+  // (the pipeline has drained both streams when the HostPrefault destructor joins the pre-fault threads)
   HostPrefault prefault(reinterpret_cast<char*>(out), n * sizeof(sart_axion_t), chunk * sizeof(sart_axion_t), !c->knobs.no_host_prefault,
                         static_cast<unsigned>(c->knobs.prefault_threads));
-  sart_trace_params_t q = *p;
-  int rc = 0;
-  // A failure inside the pipeline must not leave through an early return: kernels and copies into the CALLER's buffer are queued
-  // on two streams, and the caller may free or reuse that buffer the moment this call returns.  Every step records its error
-  // and breaks; both streams are synchronised on every way out (the HostPrefault destructor joins the pre-fault threads).
-  hipError_t he = hipSuccess;
-  const char* what = "";
-  auto step = [&](hipError_t e, const char* name) {
-    if (e != hipSuccess && he == hipSuccess) { he = e; what = name; }
-    return e == hipSuccess;
-  };
-  for (uint64_t k = 0; k <= n_chunks && rc == 0 && he == hipSuccess; ++k) {
-    if (k < n_chunks) {   // trace chunk k into buffer k & 1 once the copy of chunk k - 2 has left it
-      if (k >= 2 && !step(hipStreamWaitEvent(c->stream, c->rec_copied[k & 1], 0), "hipStreamWaitEvent(stream)")) break;
-      q.n_rays = std::min(chunk, n - k * chunk);
-      q.ray_id_offset = p->ray_id_offset + k * chunk;
-      rc = (c->knobs.records_fail_chunk > 0 && k + 1 == static_cast<uint64_t>(c->knobs.records_fail_chunk))
-               ? fail(SART_ERR_INTERNAL, "sart_trace_records: failure injected by SART_RECORDS_FAIL_CHUNK (test hook)")
-               : sart_trace_records_device(c, &q, bufs[k & 1]);
-      if (rc) break;
-      if (!step(hipEventRecord(c->rec_traced[k & 1], c->stream), "hipEventRecord(traced)")) break;
-    }
-    if (k > 0) {          // chunk k - 1 crosses PCIe while chunk k is traced (the call may block the host: pageable destination)
-      const uint64_t j = k - 1, cnt = std::min(chunk, n - j * chunk);
-      prefault.wait(j);
-      if (!step(hipStreamWaitEvent(c->copy_stream, c->rec_traced[j & 1], 0), "hipStreamWaitEvent(copy_stream)")) break;
-      if (!step(hipMemcpyAsync(out + j * chunk, bufs[j & 1], cnt * sizeof(sart_axion_t), hipMemcpyDeviceToHost, c->copy_stream), "hipMemcpyAsync(records)")) break;
-      if (!step(hipEventRecord(c->rec_copied[j & 1], c->copy_stream), "hipEventRecord(copied)")) break;
-    }
-  }
-  const hipError_t e1 = hipStreamSynchronize(c->copy_stream), e2 = hipStreamSynchronize(c->stream);
-  if (rc) return rc;
-  if (he != hipSuccess) return fail(SART_ERR_NO_DEVICE, std::string("sart_trace_records: ") + what + ": " + hipGetErrorString(he));
-  if (e1 != hipSuccess || e2 != hipSuccess) return fail(SART_ERR_NO_DEVICE, std::string("sart_trace_records: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-  return 0;
+  return record_chunk_pipeline(
+      c, "sart_trace_records", p, chunk,
+      [&](const sart_trace_params_t& q, int b, HipLatch&) { return sart_trace_records_device(c, &q, bufs[b]); },
+      [&](uint64_t j, int b, hipEvent_t traced, HipLatch& step) {   // device-side hand-over: the host does not wait for the trace
+        prefault.wait(j);
+        if (!step(hipStreamWaitEvent(c->copy_stream, traced, 0), "hipStreamWaitEvent(copy_stream)")) return;
+        step(hipMemcpyAsync(out + j * chunk, bufs[b], std::min(chunk, n - j * chunk) * sizeof(sart_axion_t), hipMemcpyDeviceToHost, c->copy_stream),
+             "hipMemcpyAsync(records)");
+      });
 }
 
 // ---- passed rays only ----------------------------------------------------------------------------------------------------------
@@ -1979,25 +2035,47 @@ uint64_t compact_chunk_of(const sart_context* c) {
   const uint64_t cap = static_cast<uint64_t>(compact_chunk_max());
   return c->knobs.records_chunk > 0 ? std::min<uint64_t>(static_cast<uint64_t>(c->knobs.records_chunk), cap) : cap;
 }
+// What the blocking passed doors (records and columns) share beside the pipeline: the four totals of the chunk in half-buffer b,
+// device words d_cmp_totals[4 b ..] behind the compaction kernels and their pinned copy h_cmp_totals[4 b ..], the caller's
+// counts, and how much of the caller's capacity is written.
+struct ChunkTotals {
+  sart_context* c;
+  sart_record_counts_t* counts;
+  uint64_t capacity, written = 0;
+  static int reserve(sart_context* c) {
+    if (int rc = c->d_cmp_totals.resize(8)) return rc;
+    if (!c->h_cmp_totals) SART_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_cmp_totals), 8 * sizeof(unsigned long long), hipHostMallocDefault));
+    return 0;
+  }
+  unsigned long long* dev(int b) const { return c->d_cmp_totals.p + 4 * b; }
+  bool zero(int b, HipLatch& step) const {   // in front of the chunk's kernels
+    return step(hipMemsetAsync(dev(b), 0, 4 * sizeof(unsigned long long), c->stream), "hipMemsetAsync(counts)");
+  }
+  bool to_host(int b, HipLatch& step) const {   // behind them
+    return step(hipMemcpyAsync(c->h_cmp_totals + 4 * b, dev(b), 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(counts)");
+  }
+  // once the chunk's `traced` event has passed: its totals into the caller's counts; returns how many of its passed rays still
+  // fit, which the caller writes at `written` and adds to it
+  uint64_t take(int b) const {
+    const unsigned long long* t = c->h_cmp_totals + 4 * b;
+    counts->n_rays += t[0]; counts->n_passed += t[1]; counts->n_passed_till_window += t[2]; counts->n_hit_nickel += t[3];
+    return std::min<uint64_t>(t[1], capacity - written);
+  }
+};
 }  // namespace
 
 int sart_trace_records_passed_device(sart_context* c, const sart_trace_params_t* p, sart_axion_t* out_dev, uint64_t capacity, uint64_t* counts_dev) {
   if (!c || !p || !counts_dev || (!out_dev && capacity)) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
   SART_HIP(hipSetDevice(c->device));
-  if (!p->accumulate) SART_HIP(hipMemsetAsync(counts_dev, 0, 4 * sizeof(uint64_t), c->stream));
-  if (p->n_rays == 0) return 0;
-  const uint64_t chunk = compact_chunk_of(c);
-  if (int rc = compact_scratch(c, std::min<uint64_t>(chunk, p->n_rays))) return rc;
-  sart_trace_params_t q = *p;
-  for (uint64_t done = 0; done < p->n_rays; done += chunk) {
-    q.n_rays = std::min(chunk, p->n_rays - done);
-    q.ray_id_offset = p->ray_id_offset + done;
-    if (int rc = sart_trace_records_device(c, &q, c->d_rec.p)) return rc;
-    launch_compact_records(c->d_rec.p, static_cast<uint32_t>(q.n_rays), out_dev, capacity, c->d_cmp_counts.p, c->d_cmp_first.p,
-                           reinterpret_cast<unsigned long long*>(counts_dev), c->stream);
-    SART_HIP(hipGetLastError());
-  }
-  return 0;
+  return device_chunks(
+      c, p, counts_dev, compact_chunk_of(c), [&](uint64_t largest) { return compact_scratch(c, largest); },
+      [&](const sart_trace_params_t& q) {
+        if (int rc = sart_trace_records_device(c, &q, c->d_rec.p)) return rc;
+        launch_compact_records(c->d_rec.p, static_cast<uint32_t>(q.n_rays), out_dev, capacity, c->d_cmp_counts.p, c->d_cmp_first.p,
+                               reinterpret_cast<unsigned long long*>(counts_dev), c->stream);
+        SART_HIP(hipGetLastError());
+        return 0;
+      });
 }
 
 int sart_trace_records_passed(sart_context* c, const sart_trace_params_t* p, sart_axion_t* out, uint64_t capacity, sart_record_counts_t* counts) {
@@ -2012,63 +2090,31 @@ int sart_trace_records_passed(sart_context* c, const sart_trace_params_t* p, sar
   DevBuf<sart_axion_t>* const cmp[2] = {&c->d_rec2, &c->d_cmp};
   for (int k = 0; k < (n_chunks > 1 ? 2 : 1); ++k)
     if (int rc = cmp[k]->reserve(std::min(chunk, n))) return rc;
-  if (int rc = c->d_cmp_totals.resize(8)) return rc;
-  if (!c->h_cmp_totals) SART_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_cmp_totals), 8 * sizeof(unsigned long long), hipHostMallocDefault));
-  if (!c->copy_stream) SART_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-  for (int k = 0; k < 2; ++k) {
-    if (!c->rec_traced[k]) SART_HIP(hipEventCreateWithFlags(&c->rec_traced[k], hipEventDisableTiming));
-    if (!c->rec_copied[k]) SART_HIP(hipEventCreateWithFlags(&c->rec_copied[k], hipEventDisableTiming));
-  }
+  if (int rc = ChunkTotals::reserve(c)) return rc;
   // (pages of `out` beyond the records written keep what they held: the pre-fault rewrites every page's first byte with itself)
   HostPrefault prefault(reinterpret_cast<char*>(out), std::min(capacity, n) * sizeof(sart_axion_t), chunk * sizeof(sart_axion_t),
                         !c->knobs.no_host_prefault, static_cast<unsigned>(c->knobs.prefault_threads), /*keep=*/true);
   prefault.set_lazy();
-  sart_trace_params_t q = *p;
-  int rc = 0;
-  hipError_t he = hipSuccess;   // as in sart_trace_records: no early return while work on the caller's buffer is queued
-  const char* what = "";
-  auto step = [&](hipError_t e, const char* name) {
-    if (e != hipSuccess && he == hipSuccess) { he = e; what = name; }
-    return e == hipSuccess;
-  };
-  uint64_t written = 0;
-  for (uint64_t k = 0; k <= n_chunks && rc == 0 && he == hipSuccess; ++k) {
-    if (k < n_chunks) {   // trace + compact chunk k into half-buffer k & 1 once the copy of chunk k - 2 has left it
-      const int b = static_cast<int>(k & 1);
-      if (k >= 2 && !step(hipStreamWaitEvent(c->stream, c->rec_copied[b], 0), "hipStreamWaitEvent(stream)")) break;
-      q.n_rays = std::min(chunk, n - k * chunk);
-      q.ray_id_offset = p->ray_id_offset + k * chunk;
-      unsigned long long* totals = c->d_cmp_totals.p + 4 * b;
-      if (!step(hipMemsetAsync(totals, 0, 4 * sizeof(unsigned long long), c->stream), "hipMemsetAsync(counts)")) break;
-      rc = (c->knobs.records_fail_chunk > 0 && k + 1 == static_cast<uint64_t>(c->knobs.records_fail_chunk))
-               ? fail(SART_ERR_INTERNAL, "sart_trace_records_passed: failure injected by SART_RECORDS_FAIL_CHUNK (test hook)")
-               : sart_trace_records_device(c, &q, c->d_rec.p);
-      if (rc) break;
-      launch_compact_records(c->d_rec.p, static_cast<uint32_t>(q.n_rays), cmp[b]->p, q.n_rays, c->d_cmp_counts.p, c->d_cmp_first.p, totals, c->stream);
-      if (!step(hipGetLastError(), "compaction kernels")) break;
-      if (!step(hipMemcpyAsync(c->h_cmp_totals + 4 * b, totals, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(counts)")) break;
-      if (!step(hipEventRecord(c->rec_traced[b], c->stream), "hipEventRecord(traced)")) break;
-    }
-    if (k > 0) {          // the passed records of chunk k - 1 cross PCIe while chunk k is traced
-      const int b = static_cast<int>((k - 1) & 1);
-      if (!step(hipEventSynchronize(c->rec_traced[b]), "hipEventSynchronize(traced)")) break;
-      const unsigned long long* t = c->h_cmp_totals + 4 * b;
-      counts->n_rays += t[0]; counts->n_passed += t[1]; counts->n_passed_till_window += t[2]; counts->n_hit_nickel += t[3];
-      const uint64_t room = capacity - written, cnt = std::min<uint64_t>(t[1], room);
-      if (cnt) {
+  ChunkTotals totals{c, counts, capacity};
+  return record_chunk_pipeline(
+      c, "sart_trace_records_passed", p, chunk,
+      [&](const sart_trace_params_t& q, int b, HipLatch& step) {   // trace into d_rec, compact into half-buffer b
+        if (!totals.zero(b, step)) return 0;
+        if (int rc = sart_trace_records_device(c, &q, c->d_rec.p)) return rc;
+        launch_compact_records(c->d_rec.p, static_cast<uint32_t>(q.n_rays), cmp[b]->p, q.n_rays, c->d_cmp_counts.p, c->d_cmp_first.p,
+                               totals.dev(b), c->stream);
+        if (step(hipGetLastError(), "compaction kernels")) totals.to_host(b, step);
+        return 0;
+      },
+      [&](uint64_t, int b, hipEvent_t traced, HipLatch& step) {   // the host reads the chunk's count: it waits for the trace
+        if (!step(hipEventSynchronize(traced), "hipEventSynchronize(traced)")) return;
+        const uint64_t written = totals.written, cnt = totals.take(b);
+        if (!cnt) return;
         prefault.allow((written + 3 * cnt) / chunk + 1);   // this copy and, at this pass rate, the next two
         for (uint64_t j = written / chunk; j <= (written + cnt - 1) / chunk; ++j) prefault.wait(j);   // (its chunks: `chunk` records each)
-        if (!step(hipMemcpyAsync(out + written, cmp[b]->p, cnt * sizeof(sart_axion_t), hipMemcpyDeviceToHost, c->copy_stream), "hipMemcpyAsync(records)")) break;
-        written += cnt;
-      }
-      if (!step(hipEventRecord(c->rec_copied[b], c->copy_stream), "hipEventRecord(copied)")) break;
-    }
-  }
-  const hipError_t e1 = hipStreamSynchronize(c->copy_stream), e2 = hipStreamSynchronize(c->stream);
-  if (rc) return rc;
-  if (he != hipSuccess) return fail(SART_ERR_NO_DEVICE, std::string("sart_trace_records_passed: ") + what + ": " + hipGetErrorString(he));
-  if (e1 != hipSuccess || e2 != hipSuccess) return fail(SART_ERR_NO_DEVICE, std::string("sart_trace_records_passed: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-  return 0;
+        step(hipMemcpyAsync(out + written, cmp[b]->p, cnt * sizeof(sart_axion_t), hipMemcpyDeviceToHost, c->copy_stream), "hipMemcpyAsync(records)");
+        totals.written += cnt;
+      });
 }
 
 // ---- passed rays as selected columns ---------------------------------------------------------------------------------------------
@@ -2083,18 +2129,12 @@ bool columns_args_ok(uint32_t mask, const void* columns, uint64_t capacity) {
   if (mask == 0 || (mask & ~kColumnMaskAll) || (!columns && capacity)) return false;
   return capacity <= (~uint64_t(0) / 8) / static_cast<uint64_t>(popcount32(mask));   // the buffer's bytes fit 64 bits
 }
-// one chunk: q->n_rays rays staged, counted and scattered to out_dev[K][capacity] behind counts_dev[1]
+// one chunk: q->n_rays > 0 rays staged, counted and scattered to out_dev[K][capacity] behind counts_dev[1]
 int columns_chunk(sart_context* c, const sart_trace_params_t* q, uint32_t mask, uint64_t* out_dev, uint64_t capacity, unsigned long long* counts_dev) {
-  if (int rc = refresh_derived(c)) return rc;
-  if (int rc = sync_blob(c)) return rc;
-  TraceArgs a;
-  if (int rc = make_args(c, q, a)) return rc;
-  if (c->blocks_per_cu_rec == 0) c->blocks_per_cu_rec = 4;
-  {
-    TimedLaunch tl(c);
-    launch_stage_columns(c->hot, c->hotb, c->d_blob.p, a, c->d_col_stage.p, c->d_col_flags.p, mask,
-                         grid_for(a.n_rays, c->n_cu, c->blocks_per_cu_rec, records_block()), c->stream);
-  }
+  if (int rc = launch_record_rays(c, q, [&](const TraceArgs& a, int n_blocks) {
+        launch_stage_columns(c->hot, c->hotb, c->d_blob.p, a, c->d_col_stage.p, c->d_col_flags.p, mask, n_blocks, c->stream);
+      }))
+    return rc;
   launch_compact_columns(c->d_col_stage.p, c->d_col_flags.p, static_cast<uint32_t>(q->n_rays), mask, q->ray_id_offset, out_dev, capacity,
                          c->d_cmp_counts.p, c->d_cmp_first.p, counts_dev, c->stream);
   SART_HIP(hipGetLastError());
@@ -2119,17 +2159,11 @@ int sart_trace_columns_passed_device(sart_context* c, const sart_trace_params_t*
                                      uint64_t* counts_dev) {
   if (!c || !p || !counts_dev || !columns_args_ok(mask, out_dev, capacity)) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument or invalid column mask / capacity");
   SART_HIP(hipSetDevice(c->device));
-  if (!p->accumulate) SART_HIP(hipMemsetAsync(counts_dev, 0, 4 * sizeof(uint64_t), c->stream));
-  if (p->n_rays == 0) return 0;
-  const uint64_t chunk = compact_chunk_of(c);
-  if (int rc = columns_scratch(c, mask, std::min<uint64_t>(chunk, p->n_rays))) return rc;
-  sart_trace_params_t q = *p;
-  for (uint64_t done = 0; done < p->n_rays; done += chunk) {
-    q.n_rays = std::min(chunk, p->n_rays - done);
-    q.ray_id_offset = p->ray_id_offset + done;
-    if (int rc = columns_chunk(c, &q, mask, static_cast<uint64_t*>(out_dev), capacity, reinterpret_cast<unsigned long long*>(counts_dev))) return rc;
-  }
-  return 0;
+  return device_chunks(
+      c, p, counts_dev, compact_chunk_of(c), [&](uint64_t largest) { return columns_scratch(c, mask, largest); },
+      [&](const sart_trace_params_t& q) {
+        return columns_chunk(c, &q, mask, static_cast<uint64_t*>(out_dev), capacity, reinterpret_cast<unsigned long long*>(counts_dev));
+      });
 }
 
 int sart_trace_columns_passed(sart_context* c, const sart_trace_params_t* p, uint32_t mask, void* out, uint64_t capacity,
@@ -2143,58 +2177,26 @@ int sart_trace_columns_passed(sart_context* c, const sart_trace_params_t* p, uin
   if (int rc = columns_scratch(c, mask, pitch)) return rc;
   for (int k = 0; k < (n_chunks > 1 ? 2 : 1); ++k)   // the compacted half-buffers [n_cols][pitch]
     if (int rc = c->d_col_cmp[k].reserve(n_cols * pitch)) return rc;
-  if (int rc = c->d_cmp_totals.resize(8)) return rc;
-  if (!c->h_cmp_totals) SART_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_cmp_totals), 8 * sizeof(unsigned long long), hipHostMallocDefault));
-  if (!c->copy_stream) SART_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-  for (int k = 0; k < 2; ++k) {
-    if (!c->rec_traced[k]) SART_HIP(hipEventCreateWithFlags(&c->rec_traced[k], hipEventDisableTiming));
-    if (!c->rec_copied[k]) SART_HIP(hipEventCreateWithFlags(&c->rec_copied[k], hipEventDisableTiming));
-  }
+  if (int rc = ChunkTotals::reserve(c)) return rc;
   uint64_t* const cols = static_cast<uint64_t*>(out);
-  sart_trace_params_t q = *p;
-  int rc = 0;
-  hipError_t he = hipSuccess;   // as in sart_trace_records: no early return while work on the caller's buffer is queued
-  const char* what = "";
-  auto step = [&](hipError_t e, const char* name) {
-    if (e != hipSuccess && he == hipSuccess) { he = e; what = name; }
-    return e == hipSuccess;
-  };
-  uint64_t written = 0;
-  for (uint64_t k = 0; k <= n_chunks && rc == 0 && he == hipSuccess; ++k) {
-    if (k < n_chunks) {   // stage + compact chunk k into half-buffer k & 1 once the copies of chunk k - 2 have left it
-      const int b = static_cast<int>(k & 1);
-      if (k >= 2 && !step(hipStreamWaitEvent(c->stream, c->rec_copied[b], 0), "hipStreamWaitEvent(stream)")) break;
-      q.n_rays = std::min(chunk, n - k * chunk);
-      q.ray_id_offset = p->ray_id_offset + k * chunk;
-      unsigned long long* totals = c->d_cmp_totals.p + 4 * b;
-      if (!step(hipMemsetAsync(totals, 0, 4 * sizeof(unsigned long long), c->stream), "hipMemsetAsync(counts)")) break;
-      rc = (c->knobs.records_fail_chunk > 0 && k + 1 == static_cast<uint64_t>(c->knobs.records_fail_chunk))
-               ? fail(SART_ERR_INTERNAL, "sart_trace_columns_passed: failure injected by SART_RECORDS_FAIL_CHUNK (test hook)")
-               : columns_chunk(c, &q, mask, c->d_col_cmp[b].p, pitch, totals);
-      if (rc) break;
-      if (!step(hipMemcpyAsync(c->h_cmp_totals + 4 * b, totals, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(counts)")) break;
-      if (!step(hipEventRecord(c->rec_traced[b], c->stream), "hipEventRecord(traced)")) break;
-    }
-    if (k > 0) {          // the columns of chunk k - 1 cross PCIe while chunk k is traced: one copy per column
-      const int b = static_cast<int>((k - 1) & 1);
-      if (!step(hipEventSynchronize(c->rec_traced[b]), "hipEventSynchronize(traced)")) break;
-      const unsigned long long* t = c->h_cmp_totals + 4 * b;
-      counts->n_rays += t[0]; counts->n_passed += t[1]; counts->n_passed_till_window += t[2]; counts->n_hit_nickel += t[3];
-      const uint64_t cnt = std::min<uint64_t>(t[1], capacity - written);
-      bool ok = true;
-      for (uint64_t j = 0; j < n_cols && cnt && ok; ++j)
-        ok = step(hipMemcpyAsync(cols + j * capacity + written, c->d_col_cmp[b].p + j * pitch, cnt * 8, hipMemcpyDeviceToHost, c->copy_stream),
-                  "hipMemcpyAsync(column)");
-      if (!ok) break;
-      written += cnt;
-      if (!step(hipEventRecord(c->rec_copied[b], c->copy_stream), "hipEventRecord(copied)")) break;
-    }
-  }
-  const hipError_t e1 = hipStreamSynchronize(c->copy_stream), e2 = hipStreamSynchronize(c->stream);
-  if (rc) return rc;
-  if (he != hipSuccess) return fail(SART_ERR_NO_DEVICE, std::string("sart_trace_columns_passed: ") + what + ": " + hipGetErrorString(he));
-  if (e1 != hipSuccess || e2 != hipSuccess) return fail(SART_ERR_NO_DEVICE, std::string("sart_trace_columns_passed: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-  return 0;
+  ChunkTotals totals{c, counts, capacity};
+  return record_chunk_pipeline(
+      c, "sart_trace_columns_passed", p, chunk,
+      [&](const sart_trace_params_t& q, int b, HipLatch& step) {   // stage + compact into half-buffer b
+        if (!totals.zero(b, step)) return 0;
+        if (int rc = columns_chunk(c, &q, mask, c->d_col_cmp[b].p, pitch, totals.dev(b))) return rc;
+        totals.to_host(b, step);
+        return 0;
+      },
+      [&](uint64_t, int b, hipEvent_t traced, HipLatch& step) {   // the host reads the chunk's count; then one copy per column
+        if (!step(hipEventSynchronize(traced), "hipEventSynchronize(traced)")) return;
+        const uint64_t cnt = totals.take(b);
+        for (uint64_t j = 0; j < n_cols && cnt; ++j)
+          if (!step(hipMemcpyAsync(cols + j * capacity + totals.written, c->d_col_cmp[b].p + j * pitch, cnt * 8, hipMemcpyDeviceToHost, c->copy_stream),
+                    "hipMemcpyAsync(column)"))
+            return;
+        totals.written += cnt;
+      });
 }
 
 int sart_release_scratch(sart_context* c) {

@@ -3498,23 +3498,67 @@ constexpr int kRecBlock = 256;
 // `uniforms` != nullptr (sart_internal_trace_records_uniforms, a test entry): ray i takes its six uniforms from
 // uniforms[6 i .. 6 i + 5] (draw order of SURVEY App. B) instead of from its Philox blocks - physics fixtures keyed by
 // explicit uniforms survive a re-mapping of the random stream.
-// One record to memory as 26 eight-byte words.  The two groups of byte-sized fields are packed by hand: a plain struct copy moves
-// their padding arrays, too, and the compiler then keeps those bytes of the local record in scratch memory.
-__device__ __forceinline__ void store_record(sart_axion_t* dst, const sart_axion_t& r) {
+// The 26 eight-byte words of a record, in memory order: f(w, value), w a literal in every call.  The only list of them: what
+// store_record writes and what the columns hold both come from here.  The two groups of byte-sized fields are packed by hand: a
+// plain struct copy moves their padding arrays, too, and the compiler then keeps those bytes of the local record in scratch memory.
+template <class F>
+__device__ __forceinline__ void for_each_record_word(const sart_axion_t& r, F&& f) {
   static_assert(sizeof(sart_axion_t) == 208 && offsetof(sart_axion_t, pointdataX) == 8 && offsetof(sart_axion_t, kinds) == 128 &&
                     offsetof(sart_axion_t, transProbWindow) == 136 && offsetof(sart_axion_t, shellNumber) == 176,
                 "layout of include/sart.h");
-  uint64_t* o = reinterpret_cast<uint64_t*>(dst);
   auto bits = [](double v) { return (uint64_t)__double_as_longlong(v); };
-  o[0] = (uint64_t)r.passed | ((uint64_t)r.passedTillWindow << 8) | ((uint64_t)r.hitNickel << 16);
-  o[1] = bits(r.pointdataX); o[2] = bits(r.pointdataY); o[3] = bits(r.pointdataXBefore); o[4] = bits(r.pointdataYBefore);
-  o[5] = bits(r.pointdataR); o[6] = bits(r.weights); o[7] = bits(r.weightsAll); o[8] = bits(r.transmissionMagnet);
-  o[9] = bits(r.yawAngles); o[10] = bits(r.pixvalsX); o[11] = bits(r.pixvalsY); o[12] = bits(r.radii);
-  o[13] = bits(r.energiesAx); o[14] = bits(r.energiesAxAll); o[15] = bits(r.energiesAxWindow);
-  o[16] = (uint64_t)r.kinds | ((uint64_t)r.kindsWindow << 8);
-  o[17] = bits(r.transProbWindow); o[18] = bits(r.transProbArgon); o[19] = bits(r.transProbDetector); o[20] = bits(r.transProbMagnet);
-  o[21] = bits(r.deviationDet); o[22] = (uint64_t)r.shellNumber; o[23] = bits(r.energiesPre); o[24] = bits(r.emratesPre);
-  o[25] = bits(r.reflect);
+  f(0u, (uint64_t)r.passed | ((uint64_t)r.passedTillWindow << 8) | ((uint64_t)r.hitNickel << 16));
+  f(1u, bits(r.pointdataX)); f(2u, bits(r.pointdataY)); f(3u, bits(r.pointdataXBefore)); f(4u, bits(r.pointdataYBefore));
+  f(5u, bits(r.pointdataR)); f(6u, bits(r.weights)); f(7u, bits(r.weightsAll)); f(8u, bits(r.transmissionMagnet));
+  f(9u, bits(r.yawAngles)); f(10u, bits(r.pixvalsX)); f(11u, bits(r.pixvalsY)); f(12u, bits(r.radii));
+  f(13u, bits(r.energiesAx)); f(14u, bits(r.energiesAxAll)); f(15u, bits(r.energiesAxWindow));
+  f(16u, (uint64_t)r.kinds | ((uint64_t)r.kindsWindow << 8));
+  f(17u, bits(r.transProbWindow)); f(18u, bits(r.transProbArgon)); f(19u, bits(r.transProbDetector)); f(20u, bits(r.transProbMagnet));
+  f(21u, bits(r.deviationDet)); f(22u, (uint64_t)r.shellNumber); f(23u, bits(r.energiesPre)); f(24u, bits(r.emratesPre));
+  f(25u, bits(r.reflect));
+}
+// One record to memory
+__device__ __forceinline__ void store_record(sart_axion_t* dst, const sart_axion_t& r) {
+  uint64_t* o = reinterpret_cast<uint64_t*>(dst);
+  for_each_record_word(r, [&](uint32_t w, uint64_t v) { o[w] = v; });
+}
+
+// The record of ray i of the launch into rec, which the caller has zeroed: newSeq[Axion] zero-initialises (:2760)
+__device__ __forceinline__ void record_of_ray(const HotA& H, const DevParams& P, const LdsTables& L, const HotB& HB, const TraceArgs& A,
+                                              uint64_t i, const double* __restrict__ uniforms, sart_axion_t& rec) {
+  RayState st;
+  bool sampled, reached;
+  double radial;    // not used here: the record path lets phase B find every miss itself (and so checks the shortcut of the histogram path)
+  LaneMasks masks;  // not used here either: this body branches per lane on the bools
+  const uint64_t ray_id = A.ray_id_offset + i;
+  bool alive;
+  if (uniforms) {   // wave-uniform
+    const double* u = uniforms + 6 * i;
+    const Uniforms U{u[0], u[1], u[2], u[3], u[4], u[5], upper32_of_uniform(u[2])};
+    alive = phase_a_core<false, -1, false>(H, P, L, U, st, sampled, reached, radial, masks);
+  } else {
+    const uint32_t u3_hi = word_of(stream_block(ray_id >> 2, A.seed_lo, A.seed_hi), (uint32_t)ray_id & 3u);
+    alive = phase_a<false, -1, false, false, false>(H, P, L, A.seed_lo, A.seed_hi, ray_id, u3_hi, st, sampled, reached, radial, masks);
+  }
+  int e_idx = -1;
+  if (sampled) {
+    e_idx = H.test_active ? P.n_energies : sample_energy_index(HB, st.r_idx, st.u5);
+    rec.emratesPre = 1.0;                          // :1818
+    rec.energiesPre = load_energy_row(HB, e_idx).energy;  // :1819
+  }
+  if (ballot64(alive)) {
+    RayOut ro;
+    if (!sampled) { st.u5 = 0.0; st.r_idx = 0; }
+    phase_b<true, false, -1, false>(P, L, HB, A, st, e_idx >= 0 ? e_idx : 0, alive, ro, &rec);
+  }
+}
+
+// The setup blob into the block's LDS copy, for the three kernels of kRecBlock threads
+__device__ __forceinline__ void blob_to_lds(DevBlob& B, const DevBlob* __restrict__ blob) {
+  const uint64_t* src = reinterpret_cast<const uint64_t*>(blob);
+  uint64_t* dst = reinterpret_cast<uint64_t*>(&B);
+  for (int i = threadIdx.x; i < (int)(sizeof(DevBlob) / 8); i += kRecBlock) dst[i] = src[i];
+  __syncthreads();
 }
 
 __global__ __launch_bounds__(kRecBlock) void trace_records_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
@@ -3522,44 +3566,15 @@ __global__ __launch_bounds__(kRecBlock) void trace_records_kernel(HotA H, const 
                                                                    const double* __restrict__ uniforms) {
   __shared__ TablesLds S;
   __shared__ DevBlob B;
-  {
-    const uint64_t* src = reinterpret_cast<const uint64_t*>(blob);
-    uint64_t* dst = reinterpret_cast<uint64_t*>(&B);
-    for (int i = threadIdx.x; i < (int)(sizeof(DevBlob) / 8); i += kRecBlock) dst[i] = src[i];
-    __syncthreads();
-  }
+  blob_to_lds(B, blob);
   const DevParams& P = B.P;
   stage_tables<kRecBlock>(S, P, B.T);
   const LdsTables L{S.sincos, S.rcdf_hi, B.T.flux_radius_cdf, S.rguide, S.shells, S.lut};
 
   const uint64_t stride = (uint64_t)gridDim.x * kRecBlock;
   for (uint64_t i = (uint64_t)blockIdx.x * kRecBlock + threadIdx.x; i < A.n_rays; i += stride) {
-    sart_axion_t rec = {};   // newSeq[Axion] zero-initialises (:2760)
-    RayState st;
-    bool sampled, reached;
-    double radial;    // not used here: the record path lets phase B find every miss itself (and so checks the shortcut of the histogram path)
-    LaneMasks masks;  // not used here either: this kernel branches per lane on the bools
-    const uint64_t ray_id = A.ray_id_offset + i;
-    bool alive;
-    if (uniforms) {   // wave-uniform
-      const double* u = uniforms + 6 * i;
-      const Uniforms U{u[0], u[1], u[2], u[3], u[4], u[5], upper32_of_uniform(u[2])};
-      alive = phase_a_core<false, -1, false>(H, P, L, U, st, sampled, reached, radial, masks);
-    } else {
-      const uint32_t u3_hi = word_of(stream_block(ray_id >> 2, A.seed_lo, A.seed_hi), (uint32_t)ray_id & 3u);
-      alive = phase_a<false, -1, false, false, false>(H, P, L, A.seed_lo, A.seed_hi, ray_id, u3_hi, st, sampled, reached, radial, masks);
-    }
-    int e_idx = -1;
-    if (sampled) {
-      e_idx = H.test_active ? P.n_energies : sample_energy_index(HB, st.r_idx, st.u5);
-      rec.emratesPre = 1.0;                          // :1818
-      rec.energiesPre = load_energy_row(HB, e_idx).energy;  // :1819
-    }
-    if (ballot64(alive)) {
-      RayOut ro;
-      if (!sampled) { st.u5 = 0.0; st.r_idx = 0; }
-      phase_b<true, false, -1, false>(P, L, HB, A, st, e_idx >= 0 ? e_idx : 0, alive, ro, &rec);
-    }
+    sart_axion_t rec = {};
+    record_of_ray(H, P, L, HB, A, i, uniforms, rec);
     store_record(&out[i], rec);
   }
 }
@@ -3609,12 +3624,7 @@ __global__ __launch_bounds__(kRecBlock) void mirror_miss_count_kernel(HotA H, co
                                                                        unsigned long long* __restrict__ counts) {
   __shared__ TablesLds S;
   __shared__ DevBlob B;
-  {
-    const uint64_t* src = reinterpret_cast<const uint64_t*>(blob);
-    uint64_t* dst = reinterpret_cast<uint64_t*>(&B);
-    for (int i = threadIdx.x; i < (int)(sizeof(DevBlob) / 8); i += kRecBlock) dst[i] = src[i];
-    __syncthreads();
-  }
+  blob_to_lds(B, blob);
   const DevParams& P = B.P;
   stage_tables<kRecBlock>(S, P, B.T);
   const LdsTables L{S.sincos, S.rcdf_hi, B.T.flux_radius_cdf, S.rguide, S.shells, S.lut};
@@ -3670,11 +3680,11 @@ constexpr int kCompactMaxBlocks = 1024;              // blocks one scan covers: 
 __device__ __forceinline__ uint32_t record_flags(const sart_axion_t* rec, uint32_t i, uint32_t n) {
   return i < n ? *reinterpret_cast<const uint32_t*>(rec + i) : 0u;   // passed @0, passedTillWindow @1, hitNickel @2
 }
-__global__ __launch_bounds__(kCompactBlock) void records_count_kernel(const sart_axion_t* __restrict__ rec, uint32_t n,
-                                                                       uint32_t* __restrict__ block_counts,
-                                                                       unsigned long long* __restrict__ counts) {
+// The flag word f of this thread's ray (0 behind the chunk's end) -> the passed rays of the block to block_counts[block], the
+// other two flags of the block into counts[2] and counts[3]
+__device__ __forceinline__ void count_flag_words(uint32_t f, uint32_t* __restrict__ block_counts,
+                                                 unsigned long long* __restrict__ counts) {
   __shared__ uint32_t part[kCompactBlock / 64][3];
-  const uint32_t f = record_flags(rec, blockIdx.x * kCompactBlock + threadIdx.x, n);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const uint32_t np = (uint32_t)__popcll(ballot64((f & 0xFFu) != 0u)), nw = (uint32_t)__popcll(ballot64((f & 0xFF00u) != 0u)),
                  nn = (uint32_t)__popcll(ballot64((f & 0xFF0000u) != 0u));
@@ -3687,6 +3697,11 @@ __global__ __launch_bounds__(kCompactBlock) void records_count_kernel(const sart
     if (b) atomicAdd(&counts[2], (unsigned long long)b);
     if (c) atomicAdd(&counts[3], (unsigned long long)c);
   }
+}
+__global__ __launch_bounds__(kCompactBlock) void records_count_kernel(const sart_axion_t* __restrict__ rec, uint32_t n,
+                                                                       uint32_t* __restrict__ block_counts,
+                                                                       unsigned long long* __restrict__ counts) {
+  count_flag_words(record_flags(rec, blockIdx.x * kCompactBlock + threadIdx.x, n), block_counts, counts);
 }
 // block_counts[b] -> the index of block b's first passed record in the output (counts[1] = passed records of earlier chunks);
 // counts[0] += n, counts[1] += the passed records of this chunk
@@ -3749,12 +3764,7 @@ __global__ __launch_bounds__(kRecBlock) void columns_stage_kernel(HotA H, const 
                                                                    HotB HB, uint32_t mask) {
   __shared__ TablesLds S;
   __shared__ DevBlob B;
-  {
-    const uint64_t* src = reinterpret_cast<const uint64_t*>(blob);
-    uint64_t* dst = reinterpret_cast<uint64_t*>(&B);
-    for (int i = threadIdx.x; i < (int)(sizeof(DevBlob) / 8); i += kRecBlock) dst[i] = src[i];
-    __syncthreads();
-  }
+  blob_to_lds(B, blob);
   const DevParams& P = B.P;
   stage_tables<kRecBlock>(S, P, B.T);
   const LdsTables L{S.sincos, S.rcdf_hi, B.T.flux_radius_cdf, S.rguide, S.shells, S.lut};
@@ -3762,62 +3772,21 @@ __global__ __launch_bounds__(kRecBlock) void columns_stage_kernel(HotA H, const 
   const uint64_t stride = (uint64_t)gridDim.x * kRecBlock;
   for (uint64_t i = (uint64_t)blockIdx.x * kRecBlock + threadIdx.x; i < A.n_rays; i += stride) {
     sart_axion_t rec = {};
-    RayState st;
-    bool sampled, reached;
-    double radial;
-    LaneMasks masks;
-    const uint64_t ray_id = A.ray_id_offset + i;
-    const uint32_t u3_hi = word_of(stream_block(ray_id >> 2, A.seed_lo, A.seed_hi), (uint32_t)ray_id & 3u);
-    const bool alive = phase_a<false, -1, false, false, false>(H, P, L, A.seed_lo, A.seed_hi, ray_id, u3_hi, st, sampled, reached, radial, masks);
-    int e_idx = -1;
-    if (sampled) {
-      e_idx = H.test_active ? P.n_energies : sample_energy_index(HB, st.r_idx, st.u5);
-      rec.emratesPre = 1.0;
-      rec.energiesPre = load_energy_row(HB, e_idx).energy;
-    }
-    if (ballot64(alive)) {
-      RayOut ro;
-      if (!sampled) { st.u5 = 0.0; st.r_idx = 0; }
-      phase_b<true, false, -1, false>(P, L, HB, A, st, e_idx >= 0 ? e_idx : 0, alive, ro, &rec);
-    }
+    record_of_ray(H, P, L, HB, A, i, nullptr, rec);
     // the words of store_record, each behind a wave-uniform test of its mask bit (w is a literal in every call: the record is
     // never indexed at run time and stays in registers); the slot is a scalar popcount
-    auto bits = [](double v) { return (uint64_t)__double_as_longlong(v); };
-    auto put = [&](uint32_t w, uint64_t v) {
+    for_each_record_word(rec, [&](uint32_t w, uint64_t v) {
+      if (w == 0u) flags[i] = (uint32_t)v;
       if ((mask >> w) & 1u) stage[(uint64_t)__popc(mask & ((1u << w) - 1u)) * A.n_rays + i] = v;
-    };
-    const uint64_t w0 = (uint64_t)rec.passed | ((uint64_t)rec.passedTillWindow << 8) | ((uint64_t)rec.hitNickel << 16);
-    flags[i] = (uint32_t)w0;
-    put(0, w0);
-    put(1, bits(rec.pointdataX)); put(2, bits(rec.pointdataY)); put(3, bits(rec.pointdataXBefore)); put(4, bits(rec.pointdataYBefore));
-    put(5, bits(rec.pointdataR)); put(6, bits(rec.weights)); put(7, bits(rec.weightsAll)); put(8, bits(rec.transmissionMagnet));
-    put(9, bits(rec.yawAngles)); put(10, bits(rec.pixvalsX)); put(11, bits(rec.pixvalsY)); put(12, bits(rec.radii));
-    put(13, bits(rec.energiesAx)); put(14, bits(rec.energiesAxAll)); put(15, bits(rec.energiesAxWindow));
-    put(16, (uint64_t)rec.kinds | ((uint64_t)rec.kindsWindow << 8));
-    put(17, bits(rec.transProbWindow)); put(18, bits(rec.transProbArgon)); put(19, bits(rec.transProbDetector));
-    put(20, bits(rec.transProbMagnet)); put(21, bits(rec.deviationDet)); put(22, (uint64_t)rec.shellNumber);
-    put(23, bits(rec.energiesPre)); put(24, bits(rec.emratesPre)); put(25, bits(rec.reflect));
+    });
   }
 }
 // records_count_kernel on the staged flag words
 __global__ __launch_bounds__(kCompactBlock) void columns_count_kernel(const uint32_t* __restrict__ flags, uint32_t n,
                                                                        uint32_t* __restrict__ block_counts,
                                                                        unsigned long long* __restrict__ counts) {
-  __shared__ uint32_t part[kCompactBlock / 64][3];
   const uint32_t i = blockIdx.x * kCompactBlock + threadIdx.x;
-  const uint32_t f = i < n ? flags[i] : 0u;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const uint32_t np = (uint32_t)__popcll(ballot64((f & 0xFFu) != 0u)), nw = (uint32_t)__popcll(ballot64((f & 0xFF00u) != 0u)),
-                 nn = (uint32_t)__popcll(ballot64((f & 0xFF0000u) != 0u));
-  if (lane == 0) { part[wave][0] = np; part[wave][1] = nw; part[wave][2] = nn; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t a = 0, b = 0, c = 0;
-    for (int w = 0; w < kCompactBlock / 64; ++w) { a += part[w][0]; b += part[w][1]; c += part[w][2]; }
-    block_counts[blockIdx.x] = a;
-    if (b) atomicAdd(&counts[2], (unsigned long long)b);
-    if (c) atomicAdd(&counts[3], (unsigned long long)c);
-  }
+  count_flag_words(i < n ? flags[i] : 0u, block_counts, counts);
 }
 // Passed ray i of the chunk goes to index d = block_first + (passed rays before it in its block) of every column, if d is below
 // the capacity: column j of the output = out[j * capacity ..], the staged ones first, in mask order, then the ray id (bit 26).

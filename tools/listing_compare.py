@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Per-kernel comparison of the gfx950 device code of two builds (no GPU needed):
 
-    python tools/listing_compare.py OLD/csrc/build NEW/csrc/build [substring of the kernel names for the resource table]
+    python tools/listing_compare.py OLD/csrc/build NEW/csrc/build [regular expression of the kernel names for the resource table]
 
 For sart_kernels.o and sart_api.o of both build directories: the code object is taken out of the host object, disassembled, and cut
 into kernels; an instruction is its mnemonic and operands (addresses, encodings and the numbers of branch labels left out).  Prints
-which kernels are the same instruction for instruction, which differ (and in how many lines) and which exist on one side only, then
-the resource table (tools/kernel_resources.py) of the kernels the substring selects in the new build."""
+which kernels are the same instruction for instruction, which differ (in how many lines, and by which mnemonics: new count minus
+old count) and which exist on one side only, then the resource table (tools/kernel_resources.py) of the kernels the expression
+selects, in the old build and in the new."""
+import collections
 import difflib
 import os
 import re
@@ -63,18 +65,22 @@ def main():
             if n in old and n in new and old[n] != new[n]:
                 d = [l for l in difflib.unified_diff(old[n], new[n], lineterm="", n=0) if l[:1] in "+-" and l[:3] not in ("+++", "---")]
                 print("  DIFFERS (%d lines of %d / %d): %s" % (len(d), len(old[n]), len(new[n]), nice[n]))
+                h = collections.Counter(i.split()[0] for i in new[n])
+                h.subtract(collections.Counter(i.split()[0] for i in old[n]))
+                print("    mnemonics, new - old: %s" % (", ".join("%s %+d" % (m, k) for m, k in sorted(h.items()) if k) or "none"))
             elif n not in new:
                 print("  ONLY OLD (%d instructions): %s" % (len(old[n]), nice[n]))
             elif n not in old:
                 print("  ONLY NEW (%d instructions): %s" % (len(new[n]), nice[n]))
-    print()
-    print("resources of the new build's kernels matching %r:" % pat)
-    ks = kernels(code_object_notes(os.path.join(new_dir, "sart_kernels.o")))
-    for k, nm in zip(ks, demangle([k["name"] for k in ks])):
-        if pat in nm and "trace_histogram_kernel" not in nm:
-            print("  %-62s vgpr %3d sgpr %3d scratch %d lds %6d spills v%d s%d kernarg %d" % (
-                re.sub(r"\(.*", "", nm).replace("void sart::", ""), k["vgpr"], k["sgpr"], k["scratch"], k["lds"], k["vgpr_spill"],
-                k["sgpr_spill"], k["kernarg"]))
+    for side, build_dir in (("old", old_dir), ("new", new_dir)):
+        print()
+        print("resources of the %s build's kernels matching %r:" % (side, pat))
+        ks = kernels(code_object_notes(os.path.join(build_dir, "sart_kernels.o")))
+        for k, nm in zip(ks, demangle([k["name"] for k in ks])):
+            if re.search(pat, nm) and "trace_histogram_kernel" not in nm:
+                print("  %-62s vgpr %3d sgpr %3d scratch %d lds %6d spills v%d s%d kernarg %d" % (
+                    re.sub(r"\(.*", "", nm).replace("void sart::", ""), k["vgpr"], k["sgpr"], k["scratch"], k["lds"], k["vgpr_spill"],
+                    k["sgpr_spill"], k["kernarg"]))
 
 
 if __name__ == "__main__":
