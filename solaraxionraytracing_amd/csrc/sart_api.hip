@@ -88,11 +88,15 @@ void launch_build_solar_tables(const double* em_dev, const double* radii_dev, co
                                double* cdf_dev, double* row_sum_dev, double* rcdf_dev, uint16_t* rguide_dev, uint16_t* eguide_dev,
                                uint32_t* status_dev, hipStream_t stream);
 void launch_cdf_hi32(const double* cdf_dev, uint32_t* out_dev, size_t n, hipStream_t stream);
+void launch_build_energy_records(const uint32_t* hi32_dev, const uint16_t* eguide_dev, int n_rows, int n_energies, uint32_t* records_dev,
+                                 hipStream_t stream);
 }  // namespace sart
 
 using namespace sart;
 
 namespace {
+// What SART_ENERGY_RECORDS is when the environment does not say (profiles/EXPERIMENTS.md, Part R24: the A/B that decided it)
+constexpr bool kEnergyRecordsDefault = true;
 
 thread_local std::string g_err;
 int fail(int code, const std::string& msg) {
@@ -217,6 +221,7 @@ struct sart_context {
     bool no_radial_table = false;    // SART_NO_RADIAL_TABLE: stage A1 of the solar-source histogram kernels decides by its compares, never by the radial verdict table
     int image_tile_max = 0;          // SART_IMAGE_TILE_MAX: upper bound of the LDS image tile's width (0 = what LDS holds); results do not depend on it
     int a0_wide = 1;                 // SART_A0_WIDE: 0 = one word per pass of stage A0, 1 (or unset) = a0_wide_rule decides, 2 = two words wherever zones exist; results do not depend on it
+    bool energy_records = kEnergyRecordsDefault;   // SART_ENERGY_RECORDS: 0 = the two-level energy draw (guide word, then candidates), 1 = the bucket records; results do not depend on it
   } knobs;
   double a0_wide_survival = -1.0;    // a0_wide_rule's last question and answer (the rule costs a few milliseconds, the zones rarely change)
   bool a0_wide_on = false;
@@ -254,6 +259,7 @@ struct sart_context {
   DevBuf<double> d_rcdf, d_ecdf, d_refl;
   DevBuf<uint32_t> d_ecdf_hi32;   // upper 32 of the 52 bits of floor(d_ecdf 2^52): the candidates of the energy draw (HotB::cdf_hi32)
   DevBuf<uint16_t> d_rguide, d_eguide;
+  DevBuf<uint32_t> d_erecords;    // bucket records of the word-exact energy draw (HotB::energy_records); empty: the two-level draw
   DevBuf<EnergyDev> d_etab;
   DevBuf<double> d_replicas;   // kImageReplicas scratch images (kept zeroed between launches)
   DevBuf<double> d_partials;   // per-workgroup partial sums of the scalars
@@ -1118,7 +1124,8 @@ int sync_blob(sart_context* c) {
   c->hotb.n_energies = c->n_energies;
   c->hotb.refl_n_angles = c->refl_na;
   c->hotb.cdf_stride = c->n_energies + kEnergyCdfPad;
-  c->hotb._pad = 0;
+  c->hotb.energy_records = c->d_erecords.p;
+  c->hotb.records_on = c->d_erecords.p ? 1 : 0;
   if (!c->knobs.no_early_reject) build_zones(c->setup, c->params, c->n_radii, c->hot, tilt_bound_of(c->setup, c->setup.telescope_turned_y_deg));
   if (c->hot.n_zones > 0 && c->knobs.a0_wide > 0) {   // the wide pass of the histogram kernels' loop (the fused angular scans keep their loops)
     const double survival = a0_survival_of(c->hot);
@@ -1471,6 +1478,7 @@ int sart_create(int device_ordinal, sart_context** out) {
     c->knobs.no_radial_table = flag("SART_NO_RADIAL_TABLE");
     c->knobs.image_tile_max = number("SART_IMAGE_TILE_MAX");
     if (const char* e = std::getenv("SART_A0_WIDE")) c->knobs.a0_wide = std::min(2, std::max(0, std::atoi(e)));
+    if (const char* e = std::getenv("SART_ENERGY_RECORDS")) c->knobs.energy_records = std::atoi(e) != 0;
   }
   *out = c;
   return 0;
@@ -1605,6 +1613,20 @@ int sart_set_axion_mass(sart_context* c, double m) {
   return 0;
 }
 
+// The bucket records of the energy draw, from the guide and the 32-bit table that are already on the device (both entry points
+// below end with it).  A table whose indices do not fit a record, or SART_ENERGY_RECORDS=0: no records, the kernels draw in two levels.
+static int build_energy_records(sart_context* c, int32_t nR, int32_t nE) {
+  if (!c->knobs.energy_records || nE > kEnergyRecordMaxEnergies) {
+    c->d_erecords.release();
+    return 0;
+  }
+  if (int rc = c->d_erecords.resize(static_cast<size_t>(nR) * kEnergyGuideBuckets * 4)) return rc;
+  launch_build_energy_records(c->d_ecdf_hi32.p, c->d_eguide.p, nR, nE, c->d_erecords.p, c->stream);
+  SART_HIP(hipGetLastError());
+  SART_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 int sart_set_solar_tables(sart_context* c, const double* rcdf, const double* ecdf, const double* energies, int32_t nR,
                           int32_t nE) {
   if (!c || !rcdf || !ecdf || !energies) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -1666,6 +1688,7 @@ int sart_set_solar_tables(sart_context* c, const double* rcdf, const double* ecd
   SART_HIP(hipStreamSynchronize(c->stream));
   if (int rc = c->d_rguide.upload(rg.data(), rg.size())) return rc;
   if (int rc = c->d_eguide.upload(eg.data(), eg.size())) return rc;
+  if (int rc = build_energy_records(c, nR, nE)) return rc;
   c->energies.assign(energies, energies + nE);
   c->n_radii = nR;
   c->n_energies = nE;
@@ -1707,6 +1730,7 @@ int sart_set_solar_tables_device(sart_context* c, const double* em_rates_dev, co
   if (status[0] & 1u) return fail(SART_ERR_INVALID_ARGUMENT, "emission table: a radius row does not give a CDF (negative / non-finite rates, or a row that sums to zero)");
   if (status[0] & 2u) return fail(SART_ERR_INVALID_ARGUMENT, "emission table: fluxRadiusCDF is not monotone or does not end at 1.0");
   c->radius_span = static_cast<int>(status[1]);
+  if (int rc = build_energy_records(c, nR, nE)) return rc;
   c->energies.assign(energies, energies + nE);
   c->n_radii = nR;
   c->n_energies = nE;
@@ -1810,6 +1834,14 @@ __attribute__((visibility("default"))) int sart_internal_a0_wide(sart_context* c
   if (hipSetDevice(c->device) != hipSuccess || refresh_derived(c) != 0 || sync_blob(c) != 0) return -1;
   *survival = c->hot.n_zones > 0 ? a0_survival_of(c->hot) : 1.0;
   return (c->hot.zone_reached >> kA0WideBit) & 1u;
+}
+
+// Test entry (not in sart.h): HotB::records_on as the next launch would carry it - 1: the word-exact energy draw goes through the bucket
+// records, 0: it draws in two levels (SART_ENERGY_RECORDS=0, or a table of more than kEnergyRecordMaxEnergies energies); < 0: error.
+__attribute__((visibility("default"))) int sart_internal_energy_records(sart_context* c) {
+  if (!c) return -1;
+  if (hipSetDevice(c->device) != hipSuccess || refresh_derived(c) != 0 || sync_blob(c) != 0) return -1;
+  return (c->hotb.records_on != 0 && c->hotb.energy_records != nullptr) ? 1 : 0;
 }
 
 // Test entry (not in sart.h): DevParams::shell0_miss_radius as the next launch would use it (-1: the shortcut is off for this setup).

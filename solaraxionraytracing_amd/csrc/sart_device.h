@@ -42,6 +42,20 @@ constexpr int kEnergyGuideLogMax = 25 * 64;               // log buckets j = 1 .
 constexpr int kEnergyGuideBuckets = kEnergyGuideUniform + kEnergyGuideLogMax + 1;
 constexpr int kEnergyGuideEntries = kEnergyGuideBuckets + 1;   // u16 per row: bucket k is bracketed by entries k, k + 1
 constexpr uint32_t kEnergyGuideCode0 = (1023u - 5u) << 6;  // (high word of the double 1/32) >> 14
+// Bucket records of the energy draw (HotB::energy_records; built by energy_records_kernel, sart_tables.hip): one 16-byte record per
+// (radius row, guide bucket) that holds the bucket's guide entry `lo` and the first kEnergyRecordK entries of cdf_hi32 inside the
+// bucket, so that ONE gather settles a word-exact draw (energy_draw_finish): lo + #{thresholds below the word}.  Every bucket's
+// words lie in one aligned block of 2^22 once the words of the log buckets are taken one lower (bucket j there is the words 2^32 - m
+// of an aligned block of m: it starts one past an aligned address), so a threshold keeps its low 22 bits:
+//   word s < 4:  t[s] << 10 | ten bits: {lo[0:10) | lo[10] << 8, t[4][14:22) | t[4][6:14) | mark << 8, t[4][0:6) << 2}
+// (the low bytes of words 1 - 3, in that order, are the upper 22 bits of t[4] << 10: two v_perm_b32 put the fifth threshold into the
+// form of the other four, which need no extraction at all - a word whose upper 22 bits are t compares like t << 10)
+// with t[s] = cdf_hi32[lo + s] - off - block (off = 0 uniform, 1 log), kEnergyRecordEmpty where the bucket holds no such entry or the
+// entry is not below the bucket's last word, and mark = "more than kEnergyRecordK entries inside".  lo counts the entries of the
+// bracket that lie below the bucket's first word in (log buckets: the guide takes an upper bound of the edge below).
+constexpr int kEnergyRecordK = 5;
+constexpr uint32_t kEnergyRecordEmpty = 0x3FFFFFu;
+constexpr int kEnergyRecordMaxEnergies = 2047;            // lo has 11 bits: larger tables keep the two-level draw
 constexpr int kEnergyCdfPad = 4;                          // 1.0-valued pad behind every CDF row (four-wide candidate gather)
 constexpr int kShellLutMax = 1024;   // cells of the radial look-up table of the shell selection
 constexpr int kMaxRadii = 2048;      // fluxRadiusCDF entries that fit the LDS stage
@@ -206,7 +220,11 @@ struct HotB {
   const EnergyDev* energy_tab;        // [n_energies + 1]
   const double* refl;                 // [n_coatings][n_energies + 1][n_angles]
   int32_t n_energies, refl_n_angles;
-  int32_t cdf_stride, _pad;           // n_energies + kEnergyCdfPad
+  int32_t cdf_stride;                 // n_energies + kEnergyCdfPad
+  int32_t records_on;                 // 1: energy_records holds the bucket records and the word-exact draw goes through them
+  // [n_radii][kEnergyGuideBuckets][4]: the bucket records of the word-exact draw (above); null (and records_on = 0): the two-level
+  // draw (tables of more than kEnergyRecordMaxEnergies energies, SART_ENERGY_RECORDS=0)
+  const uint32_t* energy_records;
 };
 
 // Device pointers of one context.

@@ -504,26 +504,41 @@ __device__ __forceinline__ T gload(const void* base, uint32_t byte_off) {
 }
 
 // Energy index drawn with u5 from the CDF row of the sampled radius (getRandomEnergyFromSolarModel, :444-471) =
-// lowerBound(row, u5), in three steps that phase B spreads over its mirror arithmetic so that the three gathers of the
-// draw (guide word -> four CDF candidates -> [energy row, reflectivities]) are in flight while the wave computes:
+// lowerBound(row, u5), in three steps that phase B spreads over its mirror arithmetic so that the gathers of the draw are in
+// flight while the wave computes.  Two-level form (guide word -> four CDF candidates -> [energy row, reflectivities]):
 //   begin       bucket of u5 (sart_device.h: kEnergyGuide*), gather of the guide word (entries k, k + 1 of the row)
 //   candidates  bracket [lo, hi] from the guide word, gather of row[lo .. lo + 3] (rows are padded with 1.0)
 //   finish      lo + #{candidates < u5}: the row is sorted and row[hi] >= u5, so candidates at or beyond hi never count;
 //               only a lane whose four candidates are all < u5 with hi > lo + 4 goes on with a binary search
+// Record form (word-exact draw with HotB::records_on; bucket record -> [energy row, reflectivities]):
+//   begin       bucket of the word, gather of the bucket's 16-byte record (sart_device.h: kEnergyRecord*)
+//   candidates  nothing
+//   finish      the record's lo + #{its five thresholds below the word}; only a lane with a marked record and all five below goes
+//               on, from lo + 5, with the guide's entry k + 1, four candidates and the binary search
 typedef uint32_t u4v __attribute__((ext_vector_type(4)));   // native vector: loads as one 16-byte access
-struct EnergyDraw {
+struct EnergyDraw {   // (two-level form | record form: the same registers, one form per launch)
   double u;
-  uint32_t khi;        // upper 32 of the 52 bits of u 2^52
-  uint32_t row;        // element offset of the CDF row
-  uint32_t gword;      // guide entries k (low half) and k + 1 (high half)
-  uint32_t lo, hi;
-  u4v c;               // cdf_hi32 of row[lo .. lo + 3]
+  uint32_t khi;        // upper 32 of the 52 bits of u 2^52 (word form: the word) | the same
+  uint32_t row;        // element offset of the CDF row | the row's INDEX (the rare block forms both tables' offsets from it)
+  uint32_t gword;      // guide entries k (low half) and k + 1 (high half) | unused
+  uint32_t lo, hi;     // the guide's bracket | lo: the bucket k; hi: the word as the thresholds see it, (word - off) << 10
+  u4v c;               // cdf_hi32 of row[lo .. lo + 3] | the bucket's record
 };
 // WORD (compile time): the uniform is a 32-bit random word over 2^32, u5 = word / 2^32 exactly (uniforms_of: every accumulating
 // kernel).  Then  cdf < u5  <=>  cdf 2^32 < word  <=>  floor(cdf 2^32) < word  for every real cdf (word is an integer), and the
 // saturated table entry 0xFFFFFFFF (cdf >= 1 - 2^-32) is never below a word: cdf_hi32 decides every candidate, there is no
 // undecided case and no tie path; the bucket and the uniform / log split are shifts and compares of the word.  The general form
 // (a uniform handed in from outside: the record kernel) makes no assumption about the bits of u5.
+// The word form with bucket records (sart_device.h: kEnergyRecord*; HotB::records_on): ONE 16-byte gather in `begin` in place of the
+// guide word and the candidates behind it, nothing in `candidates`, lo + #{thresholds of the record below the word} in `finish`.
+// The switch is a flag in the kernel arguments, wave-uniform.  Each of the three places tests its own copy of the flag, taken
+// through an empty asm: s_cmp_lg_u32 and a branch.  (One boolean shared by the three becomes a lane mask - s_cselect_b64, s_and_b64
+// with exec, s_cbranch_vccnz at every use.)
+__device__ __forceinline__ bool energy_records_on(const HotB& HB) {
+  int32_t on = HB.records_on;
+  asm volatile("" : "+s"(on));
+  return on != 0;
+}
 template <bool WORD = false>
 __device__ __forceinline__ void energy_draw_begin(const HotB& HB, int r_idx, double u5, uint32_t word, EnergyDraw& d, int r_idx_guide = -1) {
   if (r_idx_guide < 0) r_idx_guide = r_idx;   // (experiment builds pass another row for the guide gather: working-set sensitivity)
@@ -546,11 +561,24 @@ __device__ __forceinline__ void energy_draw_begin(const HotB& HB, int r_idx, dou
   const uint32_t kl = (uint32_t)kEnergyGuideUniform + min(kEnergyGuideCode0 - code, (uint32_t)kEnergyGuideLogMax);
   const bool uniform_bucket = WORD ? word < 0xF8000000u : v > 0.03125;           // u5 < 31/32: uniform buckets
   const uint32_t k = uniform_bucket ? ku : kl;
+  if (WORD && energy_records_on(HB)) {
+    // The bucket's record (sart_device.h: kEnergyRecord*) in ONE gather: lo and the first five entries of the bucket.  d.row keeps the
+    // row and d.lo the bucket for the rare block of energy_draw_finish; d.hi is the word as the thresholds see it: one lower in the
+    // log buckets, its low 22 bits moved to the top (a threshold sits in the upper 22 bits of its word, so the compare needs no
+    // extraction).
+    d.row = (uint32_t)r_idx;
+    d.lo = k;
+    d.hi = (word - (uint32_t)!uniform_bucket) << 10;
+    d.c = gload<u4v>(HB.energy_records, (__umul24((uint32_t)r_idx_guide, (uint32_t)kEnergyGuideBuckets) + k) * 16u);
+    return;
+  }
   d.row = __umul24((uint32_t)r_idx, (uint32_t)HB.cdf_stride);                    // both < 2^24
   // two adjacent u16 as one (possibly unaligned) 32-bit load
   d.gword = gload<uint32_t>(HB.energy_guide, (__umul24((uint32_t)r_idx_guide, (uint32_t)kEnergyGuideEntries) + k) * 2u);
 }
+template <bool WORD = false>
 __device__ __forceinline__ void energy_draw_candidates(const HotB& HB, EnergyDraw& d) {
+  if (WORD && energy_records_on(HB)) return;   // nothing to issue: the record holds the candidates
   d.lo = d.gword & 0xFFFFu;
   d.hi = d.gword >> 16;
   // four consecutive u32 of a row whose stride is a multiple of four entries only by accident: the 16 bytes may straddle a
@@ -560,6 +588,35 @@ __device__ __forceinline__ void energy_draw_candidates(const HotB& HB, EnergyDra
 template <bool WORD = false>
 __device__ __forceinline__ int energy_draw_finish(const HotB& HB, const EnergyDraw& d) {
   const double u = d.u;
+  if (WORD && energy_records_on(HB)) {
+    // lowerBound = lo + #{thresholds of the record below the word}: four in the upper 22 bits of the record's words (whatever the
+    // low ten bits hold, word < xs decides them: xs has zeros there), the fifth in the low bytes of words 1 - 3, which two byte
+    // permutes put into the same form
+    static_assert(kEnergyRecordK == 5 && kEnergyRecordEmpty == 0x3FFFFFu, "the layout energy_records_kernel packs");
+    const uint32_t xs = d.hi;
+    const uint32_t t4s = __builtin_amdgcn_perm(__builtin_amdgcn_perm(d.c.y, d.c.z, 0x04000c0cu), d.c.w, 0x0706000cu);
+    const bool b4 = t4s < xs;
+    uint32_t lo = ((d.c.x & 0x3FFu) | ((d.c.y & 0x100u) << 2)) + (uint32_t)(d.c.x < xs) + (uint32_t)(d.c.y < xs) + (uint32_t)(d.c.z < xs) +
+                  (uint32_t)(d.c.w < xs) + (uint32_t)b4;
+    // (the two conditions meet as lane masks on the scalar unit: as a per-lane bool the compiler builds the predicate from selects)
+    if (__builtin_amdgcn_inverse_ballot_w64(ballot64(b4) & ballot64((d.c.w & 0x100u) != 0u))) {
+      // more than five entries inside the bucket and all five below the word: the two-level draw from lo + 5 on
+      asm volatile("; rare: energy bucket wider than its record");
+      const uint32_t z = d.khi, row = __umul24(d.row, (uint32_t)HB.cdf_stride);
+      const uint32_t hi = gload<uint16_t>(HB.energy_guide, (__umul24(d.row, (uint32_t)kEnergyGuideEntries) + d.lo + 1u) * 2u);
+      const u4v c = gload<u4v>(HB.cdf_hi32, (row + lo) * 4u);
+      const uint32_t lo5 = lo;
+      lo += (uint32_t)(c.x < z) + (uint32_t)(c.y < z) + (uint32_t)(c.z < z) + (uint32_t)(c.w < z);
+      if ((c.w < z) & (hi > lo5 + 4u)) {
+        uint32_t h = hi;
+        while (lo < h) {
+          const uint32_t mid = (lo + h) >> 1;
+          if (gload<double>(HB.diff_flux_cdfs, (row + mid) * 8u) < u) lo = mid + 1; else h = mid;
+        }
+      }
+    }
+    return (int)min(lo, (uint32_t)(HB.n_energies - 1));
+  }
   if (WORD) {
     // lowerBound = lo + #{candidates < word}; only a bucket wider than four entries whose first four are all below goes on
     const uint32_t z = d.khi;
@@ -597,7 +654,7 @@ template <bool WORD = false>
 __device__ __forceinline__ int sample_energy_index(const HotB& HB, int r_idx, double u5, uint32_t word = 0u) {
   EnergyDraw d;
   energy_draw_begin<WORD>(HB, r_idx, u5, word, d);
-  energy_draw_candidates(HB, d);
+  energy_draw_candidates<WORD>(HB, d);
   return energy_draw_finish<WORD>(HB, d);
 }
 
@@ -1190,7 +1247,7 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
   constexpr bool WORD = !RECORDS;
   // the energy draw runs beside the mirror arithmetic (its gathers are issued early, consumed late)
   const bool draw_energy = NODRAW ? false : __builtin_amdgcn_readfirstlane(e_idx_in) < 0;   // wave-uniform: false for the X-ray test source
-  EnergyDraw ed = {};
+  EnergyDraw ed;   // (no initialiser: a field one form of the draw leaves unwritten would carry its zero across that form's branch)
 #ifdef SART_DEBUG_KNOBS
   // working-set experiments (wrong results by design): 0x04000000 guide rows folded onto 16, 0x02000000 CDF rows folded onto 16,
   // 0x01000000 reflectivity / energy rows folded onto 32
@@ -1225,7 +1282,7 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
   double n1z = wolter ? sh.n1_r3t : sh.n1_tan * fma(-sh.n1_tan, z1, sh.r1);
   if (live & !hit1)                           // divergent, skipped when no lane needs it: the normal at the (off-surface) input point
     n1z = normal_z_general(P, sh, 1, m1x, m1y, z1);
-  if (draw_energy) energy_draw_candidates(HB, ed);   // the guide word has had the first mirror's arithmetic to arrive
+  if (draw_energy) energy_draw_candidates<WORD>(HB, ed);   // the guide word has had the first mirror's arithmetic to arrive
   double wx = tsx, wy = tsy, wz = 1.0;
   const double N1 = fma(m1x, m1x, fma(m1y, m1y, n1z * n1z));
   double sin_a1, sin_a2;
@@ -2000,7 +2057,7 @@ __device__ __forceinline__ void breakdown_histogram_body(HotA H, const DevBlob* 
       const DevBlob& Bo = lds_opaque(B);
       HotB HB;
       reload_kernarg(HB, offsetof(HistKernArgs, HB));
-      asm volatile("" :: "s"(HB.cdf_hi32), "s"(HB.energy_guide), "s"(HB.energy_tab), "s"(HB.refl), "s"(HB.refl_n_angles), "s"(HB.cdf_stride));
+      asm volatile("" :: "s"(HB.cdf_hi32), "s"(HB.energy_guide), "s"(HB.energy_records), "s"(HB.records_on), "s"(HB.energy_tab), "s"(HB.refl), "s"(HB.refl_n_angles), "s"(HB.cdf_stride));
       phase_b<false, false, -1, false>(Bo.P, L, HB, lds_opaque(Ab), st, H.test_active ? Pb.n_energies : -1, valid, out, nullptr);
     }
     h1 += n_valid;
@@ -3887,6 +3944,8 @@ extern "C" __attribute__((visibility("default"))) int sart_internal_math_eval(in
 void launch_cdf_hi32(const double* cdf_dev, uint32_t* out_dev, size_t n, hipStream_t stream);
 void launch_build_guides(const double* ecdf_dev, int n_rows, int n_energies, uint16_t* eguide_dev, const double* rcdf_dev, int n_radii,
                          uint16_t* rguide_dev, uint32_t* status_dev, hipStream_t stream);
+void launch_build_energy_records(const uint32_t* hi32_dev, const uint16_t* eguide_dev, int n_rows, int n_energies, uint32_t* records_dev,
+                                 hipStream_t stream);
 __global__ __launch_bounds__(256) void word_draw_energy_kernel(HotB HB, const int32_t* __restrict__ rows, const uint32_t* __restrict__ words, int n,
                                                                int32_t* __restrict__ out_word, int32_t* __restrict__ out_general) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3915,9 +3974,10 @@ __global__ __launch_bounds__(256) void word_draw_radius_kernel(const double* __r
   out_word[i] = radius_draw<true>(L, z, u52(z, 0u));
   out_general[i] = radius_draw<false>(L, z, u52(z, 0u));
 }
-extern "C" __attribute__((visibility("default"))) int sart_internal_word_draw(int kind, const double* cdf_host, int n_rows, int n_cols,
-                                                                               const int32_t* rows_host, const uint32_t* words_host, int n,
-                                                                               int32_t* out_word_host, int32_t* out_general_host) {
+// use_records: the energy draw's word form goes through the bucket records where the table allows them (n_cols <= kEnergyRecordMaxEnergies);
+// *records_used says whether it did, records_out (may be null) receives the table [n_rows][kEnergyGuideBuckets][4].
+static int word_draw_impl(int kind, const double* cdf_host, int n_rows, int n_cols, const int32_t* rows_host, const uint32_t* words_host, int n,
+                          int32_t* out_word_host, int32_t* out_general_host, bool use_records, int* records_used, uint32_t* records_out) {
   if (n < 1 || n_rows < 1 || n_cols < 1 || (kind != 0 && kind != 1) || (kind == 1 && (n_rows != 1 || n_cols > kMaxRadii)) || n_cols > 65535)
     return -1;
   if (kind == 0)
@@ -3932,7 +3992,12 @@ extern "C" __attribute__((visibility("default"))) int sart_internal_word_draw(in
   uint32_t *d_hi = nullptr, *d_words = nullptr, *d_status = nullptr;
   uint16_t* d_guide = nullptr;
   int32_t *d_rows = nullptr, *d_ow = nullptr, *d_og = nullptr;
+  uint32_t* d_rec = nullptr;
+  const bool records = use_records && kind == 0 && n_cols <= kEnergyRecordMaxEnergies;
+  const size_t n_rec = (size_t)n_rows * kEnergyGuideBuckets * 4;
+  if (records_used) *records_used = records ? 1 : 0;
   int rc = -2;
+  if (records && hipMalloc(&d_rec, n_rec * 4) != hipSuccess) return rc;
   if (hipMalloc(&d_cdf, cdf.size() * 8) == hipSuccess && hipMalloc(&d_hi, cdf.size() * 4) == hipSuccess &&
       hipMalloc(&d_guide, n_guide * 2) == hipSuccess && hipMalloc(&d_words, (size_t)n * 4) == hipSuccess &&
       hipMalloc(&d_rows, (size_t)n * 4) == hipSuccess && hipMalloc(&d_ow, (size_t)n * 4) == hipSuccess &&
@@ -3952,6 +4017,11 @@ extern "C" __attribute__((visibility("default"))) int sart_internal_word_draw(in
       HB.energy_guide = d_guide;
       HB.n_energies = n_cols;
       HB.cdf_stride = stride;
+      if (records) {
+        launch_build_energy_records(d_hi, d_guide, n_rows, n_cols, d_rec, nullptr);
+        HB.energy_records = d_rec;
+        HB.records_on = 1;
+      }
       hipLaunchKernelGGL(word_draw_energy_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, HB, d_rows, d_words, n, d_ow, d_og);
     } else {
       launch_build_guides(nullptr, 0, 0, nullptr, d_cdf, n_cols, d_guide, d_status, nullptr);
@@ -3960,11 +4030,26 @@ extern "C" __attribute__((visibility("default"))) int sart_internal_word_draw(in
     }
     const hipError_t e1 = hipMemcpy(out_word_host, d_ow, (size_t)n * 4, hipMemcpyDeviceToHost);
     const hipError_t e2 = hipMemcpy(out_general_host, d_og, (size_t)n * 4, hipMemcpyDeviceToHost);
-    rc = (e1 == hipSuccess && e2 == hipSuccess && hipGetLastError() == hipSuccess) ? 0 : -2;
+    const hipError_t e3 = (records && records_out) ? hipMemcpy(records_out, d_rec, n_rec * 4, hipMemcpyDeviceToHost) : hipSuccess;
+    rc = (e1 == hipSuccess && e2 == hipSuccess && e3 == hipSuccess && hipGetLastError() == hipSuccess) ? 0 : -2;
   }
   (void)hipFree(d_cdf); (void)hipFree(d_hi); (void)hipFree(d_guide); (void)hipFree(d_words); (void)hipFree(d_rows);
-  (void)hipFree(d_ow); (void)hipFree(d_og); (void)hipFree(d_status); (void)hipFree(d_tab);
+  (void)hipFree(d_ow); (void)hipFree(d_og); (void)hipFree(d_status); (void)hipFree(d_tab); (void)hipFree(d_rec);
   return rc;
+}
+extern "C" __attribute__((visibility("default"))) int sart_internal_word_draw(int kind, const double* cdf_host, int n_rows, int n_cols,
+                                                                               const int32_t* rows_host, const uint32_t* words_host, int n,
+                                                                               int32_t* out_word_host, int32_t* out_general_host) {
+  return word_draw_impl(kind, cdf_host, n_rows, n_cols, rows_host, words_host, n, out_word_host, out_general_host, true, nullptr, nullptr);
+}
+// The energy draw alone (tests/test_gpu_energy_records.py), with the bucket records (use_records != 0, where the table allows them:
+// *records_used) or in two levels; records_out may be null.
+extern "C" __attribute__((visibility("default"))) int sart_internal_record_draw(const double* cdf_host, int n_rows, int n_cols,
+                                                                                 const int32_t* rows_host, const uint32_t* words_host, int n,
+                                                                                 int use_records, int32_t* out_word_host, int32_t* out_general_host,
+                                                                                 int* records_used, uint32_t* records_out) {
+  return word_draw_impl(0, cdf_host, n_rows, n_cols, rows_host, words_host, n, out_word_host, out_general_host, use_records != 0, records_used,
+                        records_out);
 }
 
 // ---- launch wrappers (called from sart_api.hip) ----

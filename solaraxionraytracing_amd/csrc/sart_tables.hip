@@ -148,6 +148,59 @@ void launch_cdf_hi32(const double* cdf_dev, uint32_t* out_dev, size_t n, hipStre
   hipLaunchKernelGGL(cdf_hi32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, cdf_dev, out_dev, n);
 }
 
+// ---- bucket records of the energy draw (sart_device.h: kEnergyRecord*): one thread per (row, bucket), from the guide and cdf_hi32 ----
+// Words of bucket k: uniform k < Uniform: [k << 22, (k + 1) << 22); log bucket j = k - Uniform: the words 2^32 - m of the m whose
+// double m 2^-32 has the code Code0 - j (exponent e = 26 - (j - 1) / 64, six mantissa bits f = 63 - (j - 1) % 64), that is
+// m in [(64 + f) 2^(e - 6), (65 + f) 2^(e - 6)) rounded up to integers; j = 0 is the one word 31/32 2^32, the last bucket takes every m
+// down to 1.  (A bucket without a word - e < 6 - gets a record nobody reads.)
+__global__ __launch_bounds__(256) void energy_records_kernel(const uint32_t* __restrict__ hi32, const uint16_t* __restrict__ guide,
+                                                             int n_energies, uint32_t* __restrict__ records) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  const int r = blockIdx.y;
+  if (k >= kEnergyGuideBuckets) return;
+  long long first, last;
+  const long long off = k < kEnergyGuideUniform ? 0 : 1;
+  if (k < kEnergyGuideUniform) {
+    first = (long long)k << 22;
+    last = first + 0x3FFFFF;
+  } else if (k == kEnergyGuideUniform) {
+    first = last = 0xF8000000ll;
+  } else {
+    const int j = k - kEnergyGuideUniform;
+    const int e = 26 - (j - 1) / 64, f = 63 - (j - 1) % 64;
+    const long long m_lo = e >= 6 ? (long long)(64 + f) << (e - 6) : (((long long)(64 + f) + (1ll << (6 - e)) - 1) >> (6 - e));
+    const long long m_hi = e >= 6 ? (long long)(65 + f) << (e - 6) : (((long long)(65 + f) + (1ll << (6 - e)) - 1) >> (6 - e));
+    first = 0x100000000ll - m_hi + 1;
+    last = 0x100000000ll - (j == kEnergyGuideLogMax ? 1 : m_lo);
+  }
+  const long long block = ((first - off) >> 22) << 22;
+  const uint32_t* t = hi32 + (size_t)r * ((size_t)n_energies + kEnergyCdfPad);
+  const uint16_t* g = guide + (size_t)r * kEnergyGuideEntries + k;
+  int lo = g[0];
+  const int hi = g[1];
+  while (lo < hi && (long long)t[lo] < first) ++lo;
+  uint32_t thr[kEnergyRecordK];
+  for (int s = 0; s < kEnergyRecordK; ++s) {
+    const long long v = lo + s < hi ? (long long)t[lo + s] : last + 1;
+    thr[s] = v <= last ? (uint32_t)(v - off - block) : kEnergyRecordEmpty;
+  }
+  const uint32_t mark = lo + kEnergyRecordK < hi ? 1u : 0u;
+  static_assert(kEnergyRecordK == 5, "the packing below holds five thresholds");
+  const uint32_t t4 = thr[4], l = (uint32_t)lo;
+  uint32_t* out = records + ((size_t)r * kEnergyGuideBuckets + k) * 4;
+  out[0] = thr[0] << 10 | (l & 0x3FFu);
+  out[1] = thr[1] << 10 | ((l >> 10) << 8) | (t4 >> 14);
+  out[2] = thr[2] << 10 | ((t4 >> 6) & 0xFFu);
+  out[3] = thr[3] << 10 | (mark << 8) | ((t4 & 0x3Fu) << 2);
+}
+// records_dev: [n_rows][kEnergyGuideBuckets][4] u32, of a guide and a cdf_hi32 that are already in device memory (n_energies <=
+// kEnergyRecordMaxEnergies: the caller checks)
+void launch_build_energy_records(const uint32_t* hi32_dev, const uint16_t* eguide_dev, int n_rows, int n_energies, uint32_t* records_dev,
+                                 hipStream_t stream) {
+  hipLaunchKernelGGL(energy_records_kernel, dim3((kEnergyGuideBuckets + 255) / 256, n_rows), dim3(256), 0, stream, hi32_dev, eguide_dev,
+                     n_energies, records_dev);
+}
+
 // status[0]: bit 0 = a diffFluxCDFs row is not a CDF, bit 1 = fluxRadiusCDF is not; status[1] = radius_span
 void launch_build_solar_tables(const double* em_dev, const double* radii_dev, const double* energies_dev, int n_radii, int n_energies,
                                double* cdf_dev, double* row_sum_dev, double* rcdf_dev, uint16_t* rguide_dev, uint16_t* eguide_dev,

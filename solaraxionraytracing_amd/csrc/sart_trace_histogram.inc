@@ -207,7 +207,7 @@
       HotB HB;
       reload_kernarg(HB, offsetof(HistKernArgs, HB));
       // (one round trip beside the ring reads above, not a second one in the middle of the pass)
-      asm volatile("" :: "s"(HB.cdf_hi32), "s"(HB.energy_guide), "s"(HB.energy_tab), "s"(HB.refl), "s"(HB.refl_n_angles), "s"(HB.cdf_stride));
+      asm volatile("" :: "s"(HB.cdf_hi32), "s"(HB.energy_guide), "s"(HB.energy_records), "s"(HB.records_on), "s"(HB.energy_tab), "s"(HB.refl), "s"(HB.refl_n_angles), "s"(HB.cdf_stride));
       phase_b<false, FAST, GAS, FAST && !ROT && GAS >= 0, SCAN>(Bo.P, L, HB, lds_opaque(Ab), st, (!FAST && H.test_active) ? Pb.n_energies : -1, valid, out, nullptr);
       if constexpr (SCAN) {
         SART_STAGE_MARK("SCAN");
