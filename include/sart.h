@@ -444,6 +444,14 @@ int sart_release_scratch(sart_context* ctx);
  * telescope and gas stage included): a host loop that changes the telescope's angle between image launches pays it per angle.
  * Launches without an image do not: flux-only launches (image_nx = image_ny = 0) and the fused scans (sart_trace_mass_scan,
  * sart_trace_angular_scan) place no tile and never synchronise.
+ * The folded form.  The constant-path kernel of the solar source (vacuum and gas stage) exists twice: reading its wave-uniform
+ * switches per pass, and with the answers of the reference's default configuration compiled in.  A launch takes the folded form
+ * only when every such answer holds: bucket records of the energy draw on, radial verdict table built, stage A0 zones present, XMM
+ * optics (Wolter, 16 spokes), four window strips, none of SART_CF_IGNORE_DET_WINDOW / _GAS_ABS / _REFLECTION / _CONV_PROB /
+ * SART_CF_XRAY_TEST in `flags`, spectra == 0.  Anything else runs the run-time form; the results are the same bit for bit in
+ * FIXED64 and ray for ray in f64.  SART_NO_FOLDED=1 in the environment when the context is created: always the run-time form.
+ * Test entry (libsart exports it, no prototype here): int sart_internal_last_histogram_form(sart_context*) -> 1 if the last launch
+ * of sart_trace_histogram_device on this context took the folded form, 0 for the run-time form, -1 before the first launch.
  */
 int sart_trace_histogram_device(sart_context* ctx, const sart_trace_params_t* params,
                                 double* accumulator_device);

@@ -221,8 +221,10 @@ struct sart_context {
     bool no_radial_table = false;    // SART_NO_RADIAL_TABLE: stage A1 of the solar-source histogram kernels decides by its compares, never by the radial verdict table
     int image_tile_max = 0;          // SART_IMAGE_TILE_MAX: upper bound of the LDS image tile's width (0 = what LDS holds); results do not depend on it
     int a0_wide = 1;                 // SART_A0_WIDE: 0 = one word per pass of stage A0, 1 (or unset) = a0_wide_rule decides, 2 = two words wherever zones exist; results do not depend on it
+    bool no_folded = false;          // SART_NO_FOLDED: the histogram launches never take the folded kernel form (variants 7 / 8); results do not depend on it
     bool energy_records = kEnergyRecordsDefault;   // SART_ENERGY_RECORDS: 0 = the two-level energy draw (guide word, then candidates), 1 = the bucket records; results do not depend on it
   } knobs;
+  int last_hist_folded = -1;         // the form the last histogram launch took: 1 folded, 0 run-time, -1 none yet (sart_internal_last_histogram_form)
   double a0_wide_survival = -1.0;    // a0_wide_rule's last question and answer (the rule costs a few milliseconds, the zones rarely change)
   bool a0_wide_on = false;
   hipStream_t own_stream = nullptr;
@@ -1242,7 +1244,8 @@ int freeze_quanta(sart_context* c, double b, bool refreeze) {
 // 0 / 3 / 4: compile-time specialisations for the solar source without the hole loop (vacuum; gas stage; rotated telescope =
 // the angular scan); 1 / 2: everything else with the switches read at run time (1 not rotated, 2 rotated); 5 / 6: variants
 // 0 / 3 when no surviving ray entered through the bore wall (constant path in the magnetic field: ring 1 does not carry it
-// and the LDS image tile - or the mass scan's accumulators - use its space beside stage A0).
+// and the LDS image tile - or the mass scan's accumulators - use its space beside stage A0).  (The folded forms 7 / 8 of 5 / 6 are a
+// choice of the histogram launch, not of the setup: histogram_launch, fold_inputs_of.)
 int hist_variant_of(const sart_context* c) {
   const DevParams& P = c->params;
   const bool fast = !P.test_active && !(P.telescope_kind == SART_TK_XMM && P.inner_blocks < 0) && !c->knobs.force_generic;
@@ -1251,6 +1254,23 @@ int hist_variant_of(const sart_context* c) {
   if (fast && P.rotated && !P.stage_gas) variant = 4;
   if ((variant == 0 || variant == 3) && c->path_const && !c->knobs.no_path_const) variant = variant == 0 ? 5 : 6;
   return variant;
+}
+
+// What folded_form_applies (sart_device.h) is asked for a launch of this context with the kernel's arguments `a`: variant = what
+// hist_variant_of said.  (After sync_blob: c->hot and c->hotb are those of the launch.)
+FoldInputs fold_inputs_of(const sart_context* c, int variant, const TraceArgs& a) {
+  FoldInputs f;
+  f.constant_path = variant == 5 || variant == 6;
+  f.records_on = c->hotb.records_on != 0 && c->hotb.energy_records != nullptr;
+  f.radial_table = c->hot.radial_table != 0;
+  f.zones = c->hot.n_zones > 0;
+  f.xmm = c->params.telescope_kind == SART_TK_XMM && c->params.telescope_wolter != 0;
+  f.spoke_n = c->hot.spoke_n;
+  f.n_half_strips = c->params.n_half_strips;
+  f.flags = a.flags;
+  f.spectra = a.spectra != 0;
+  f.no_folded = c->knobs.no_folded;
+  return f;
 }
 
 int grid_for(uint64_t n_rays, int n_cu, int blocks_per_cu, int block) {
@@ -1479,6 +1499,7 @@ int sart_create(int device_ordinal, sart_context** out) {
     c->knobs.image_tile_max = number("SART_IMAGE_TILE_MAX");
     if (const char* e = std::getenv("SART_A0_WIDE")) c->knobs.a0_wide = std::min(2, std::max(0, std::atoi(e)));
     if (const char* e = std::getenv("SART_ENERGY_RECORDS")) c->knobs.energy_records = std::atoi(e) != 0;
+    c->knobs.no_folded = flag("SART_NO_FOLDED");
   }
   *out = c;
   return 0;
@@ -1842,6 +1863,19 @@ __attribute__((visibility("default"))) int sart_internal_energy_records(sart_con
   if (!c) return -1;
   if (hipSetDevice(c->device) != hipSuccess || refresh_derived(c) != 0 || sync_blob(c) != 0) return -1;
   return (c->hotb.records_on != 0 && c->hotb.energy_records != nullptr) ? 1 : 0;
+}
+
+// Test entries for the folded kernel form (include/sart.h describes them): the form the context's last histogram launch took, and
+// folded_form_applies itself for a truth table (no device needed) - in[10]: constant_path, records_on, radial_table, zones, xmm,
+// spoke_n, n_half_strips, flags, spectra, no_folded.
+__attribute__((visibility("default"))) int sart_internal_last_histogram_form(sart_context* c) { return c ? c->last_hist_folded : -1; }
+__attribute__((visibility("default"))) int sart_internal_folded_form_applies(const uint32_t* in) {
+  if (!in) return -1;
+  FoldInputs f;
+  f.constant_path = in[0] != 0; f.records_on = in[1] != 0; f.radial_table = in[2] != 0; f.zones = in[3] != 0; f.xmm = in[4] != 0;
+  f.spoke_n = static_cast<int>(in[5]); f.n_half_strips = static_cast<int>(in[6]); f.flags = in[7]; f.spectra = in[8] != 0;
+  f.no_folded = in[9] != 0;
+  return folded_form_applies(f) ? 1 : 0;
 }
 
 // Test entry (not in sart.h): DevParams::shell0_miss_radius as the next launch would use it (-1: the shortcut is off for this setup).
@@ -2449,9 +2483,13 @@ int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_
     if (int rc = c->d_partials.resize(rows * SART_ACC_COUNT)) return rc;
   }
   a.partials = c->d_partials.p;
+  // variants 5 / 6 with their wave-uniform switches folded (7 / 8) where every folded answer is this launch's; grid, tile and
+  // replicas are those of 5 / 6
+  const bool folded = folded_form_applies(fold_inputs_of(c, variant, a));
+  if (!c->tile.in_pilot) c->last_hist_folded = folded ? 1 : 0;
   {
     TimedLaunch tl(c);
-    launch_trace_histogram(c->hot, c->hotb, c->d_blob.p, a, acc_dev, n_blocks, c->stream, variant, fixed);
+    launch_trace_histogram(c->hot, c->hotb, c->d_blob.p, a, acc_dev, n_blocks, c->stream, folded ? variant + 2 : variant, fixed);
   }
   SART_HIP(hipGetLastError());
   return 0;

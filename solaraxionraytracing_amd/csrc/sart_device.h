@@ -227,6 +227,34 @@ struct HotB {
   const uint32_t* energy_records;
 };
 
+// ---- the folded form of the histogram kernel (sart_kernels.hip: HistCfg, folded_histogram_kernel; variants 7 / 8) ----
+// The constant-path variants 5 / 6 compiled with the answers of the reference's default configuration as constants: the values
+// below, and `true` for every member of FoldInputs.  A launch takes the folded form only when folded_form_applies() - the one
+// place that says so on the host - and the kernel's configuration type folds exactly these answers.
+constexpr int kFoldedSpokes = 16;          // the XMM spider (hoist_setup)
+constexpr int kFoldedHalfStrips = 2;       // number_of_strips = 4: every shipped detector setup
+// launch flags whose tests are folded (all clear in the folded form)
+constexpr uint32_t kFoldedFlags = 1u << 0 | 1u << 1 | 1u << 2 | 1u << 3 | 1u << 4;   // SART_CF_IGNORE_DET_WINDOW .. SART_CF_XRAY_TEST
+struct FoldInputs {
+  // the context
+  bool constant_path;     // hist_variant_of says 5 or 6 (solar source, no hole loop, telescope not turned, constant path)
+  bool records_on;        // HotB::records_on: the energy draw goes through the bucket records
+  bool radial_table;      // HotA::radial_table
+  bool zones;             // HotA::n_zones > 0 (stage A0 runs)
+  bool xmm;               // SART_TK_XMM: Wolter optics with the ring and the 16-spoke spider
+  int spoke_n;            // HotA::spoke_n
+  int n_half_strips;      // DevParams::n_half_strips
+  // the launch
+  uint32_t flags;         // sart_trace_params_t::flags
+  bool spectra;           // sart_trace_params_t::spectra
+  // the knob
+  bool no_folded;         // SART_NO_FOLDED
+};
+inline bool folded_form_applies(const FoldInputs& f) {
+  return f.constant_path && f.records_on && f.radial_table && f.zones && f.xmm && f.spoke_n == kFoldedSpokes &&
+         f.n_half_strips == kFoldedHalfStrips && (f.flags & kFoldedFlags) == 0u && !f.spectra && !f.no_folded;
+}
+
 // Device pointers of one context.
 struct DevTables {
   const double* sincos_tab;           // [kSinCosEntries][2]: (cos, sin)(pi k / 64), correctly rounded

@@ -539,7 +539,52 @@ __device__ __forceinline__ bool energy_records_on(const HotB& HB) {
   asm volatile("" : "+s"(on));
   return on != 0;
 }
-template <bool WORD = false>
+
+// ---- configuration type of the histogram kernel body (sart_trace_histogram.inc), of phase A's second half and of phase B ----
+// Every member answers one wave-uniform question that the hot path asks in every pass and whose answer is fixed for the whole
+// launch.  RunTimeCfg answers by today's read of the kernel arguments or of the parameter block (every instantiation that
+// existed before the folded form: the same code as without the type).  FoldedCfg answers with the constants of the reference's
+// default configuration (sart_device.h: folded_form_applies is the host's side of the same list); the compare, the branch, the
+// blocks it cuts and the constants re-materialised per block go away, the arithmetic stays.  Folded per group - stage A1, phase B,
+// accumulation and loop - so that each group can be priced alone (experiment builds: -DSART_FOLD_A1=0 ...).
+#ifndef SART_FOLD_A1
+#define SART_FOLD_A1 1
+#endif
+#ifndef SART_FOLD_B
+#define SART_FOLD_B 1
+#endif
+#ifndef SART_FOLD_ACC
+#define SART_FOLD_ACC 1
+#endif
+// STRIPS: the strip loop of phase B is folded too (its trip count a constant: unrolled).  Vacuum only - in the gas-stage kernel the
+// unrolled loop's eight bounds are live beside the absorption arithmetic and the kernel spills (128 VGPRs + 76 bytes of scratch per
+// lane against 115 without), so its folded form keeps the loop.
+template <bool A1, bool B, bool ACC, bool STRIPS>
+struct HistCfg {
+  // Which groups are folded.  At each place the body writes `CFG::kFoldX ? <the constant> : <the run-time read it always made>`: the
+  // run-time arm stays the expression it was, so that the run-time form compiles to the code it had (a helper function around the
+  // read, inlined, does not: the three tests of energy_records_on come out as one shared lane mask).
+  static constexpr bool kFoldA1 = A1, kFoldB = B, kFoldAcc = ACC;
+  static constexpr bool kFoldStrips = B && STRIPS;
+  // the folded answers
+  // stage A1: the radial verdict table is built; the optics are not the cone telescope; kFoldedSpokes spokes
+  static constexpr int32_t kRadialTable = 1;
+  static constexpr bool kIsLlnl = false;
+  static constexpr int kSpokes = kFoldedSpokes;
+  // phase B: the draw goes through the bucket records; Wolter optics; kFoldedHalfStrips strips (kFoldStrips); every flag of kFoldedFlags clear
+  static constexpr bool kRecordsOn = true;
+  static constexpr int kWolter = 1, kHalfStrips = kFoldedHalfStrips;
+  // accumulation and loop: no spectra; stage A0 runs
+  static constexpr int32_t kSpectra = 0;
+  static constexpr bool kZones = true;
+};
+using RunTimeCfg = HistCfg<false, false, false, false>;
+template <int GAS>
+using FoldedCfg = HistCfg<SART_FOLD_A1 != 0, SART_FOLD_B != 0, SART_FOLD_ACC != 0, GAS == 0>;
+static_assert(kFoldedFlags == (SART_CF_IGNORE_DET_WINDOW | SART_CF_IGNORE_GAS_ABS | SART_CF_IGNORE_REFLECTION | SART_CF_IGNORE_CONV_PROB |
+                               SART_CF_XRAY_TEST), "the flags phase B tests");
+
+template <bool WORD = false, class CFG = RunTimeCfg>
 __device__ __forceinline__ void energy_draw_begin(const HotB& HB, int r_idx, double u5, uint32_t word, EnergyDraw& d, int r_idx_guide = -1) {
   if (r_idx_guide < 0) r_idx_guide = r_idx;   // (experiment builds pass another row for the guide gather: working-set sensitivity)
   d.u = u5;
@@ -561,7 +606,7 @@ __device__ __forceinline__ void energy_draw_begin(const HotB& HB, int r_idx, dou
   const uint32_t kl = (uint32_t)kEnergyGuideUniform + min(kEnergyGuideCode0 - code, (uint32_t)kEnergyGuideLogMax);
   const bool uniform_bucket = WORD ? word < 0xF8000000u : v > 0.03125;           // u5 < 31/32: uniform buckets
   const uint32_t k = uniform_bucket ? ku : kl;
-  if (WORD && energy_records_on(HB)) {
+  if (WORD && (CFG::kFoldB ? CFG::kRecordsOn : energy_records_on(HB))) {
     // The bucket's record (sart_device.h: kEnergyRecord*) in ONE gather: lo and the first five entries of the bucket.  d.row keeps the
     // row and d.lo the bucket for the rare block of energy_draw_finish; d.hi is the word as the thresholds see it: one lower in the
     // log buckets, its low 22 bits moved to the top (a threshold sits in the upper 22 bits of its word, so the compare needs no
@@ -576,19 +621,19 @@ __device__ __forceinline__ void energy_draw_begin(const HotB& HB, int r_idx, dou
   // two adjacent u16 as one (possibly unaligned) 32-bit load
   d.gword = gload<uint32_t>(HB.energy_guide, (__umul24((uint32_t)r_idx_guide, (uint32_t)kEnergyGuideEntries) + k) * 2u);
 }
-template <bool WORD = false>
+template <bool WORD = false, class CFG = RunTimeCfg>
 __device__ __forceinline__ void energy_draw_candidates(const HotB& HB, EnergyDraw& d) {
-  if (WORD && energy_records_on(HB)) return;   // nothing to issue: the record holds the candidates
+  if (WORD && (CFG::kFoldB ? CFG::kRecordsOn : energy_records_on(HB))) return;   // nothing to issue: the record holds the candidates
   d.lo = d.gword & 0xFFFFu;
   d.hi = d.gword >> 16;
   // four consecutive u32 of a row whose stride is a multiple of four entries only by accident: the 16 bytes may straddle a
   // 16-byte boundary, global_load_dwordx4 needs 4-byte alignment only
   d.c = gload<u4v>(HB.cdf_hi32, (d.row + d.lo) * 4u);
 }
-template <bool WORD = false>
+template <bool WORD = false, class CFG = RunTimeCfg>
 __device__ __forceinline__ int energy_draw_finish(const HotB& HB, const EnergyDraw& d) {
   const double u = d.u;
-  if (WORD && energy_records_on(HB)) {
+  if (WORD && (CFG::kFoldB ? CFG::kRecordsOn : energy_records_on(HB))) {
     // lowerBound = lo + #{thresholds of the record below the word}: four in the upper 22 bits of the record's words (whatever the
     // low ten bits hold, word < xs decides them: xs has zeros there), the fifth in the low bytes of words 1 - 3, which two byte
     // permutes put into the same form
@@ -961,7 +1006,7 @@ __device__ __forceinline__ uint32_t radial_verdict_table(const HotA& H, const De
 
 // RTAB (solar-source histogram kernels): with HotA::radial_table set the radial verdicts come from the table; M.keep and M.cand are
 // filled either way, and `r3sq` is not (the caller reads it for the selected shell where it needs it).
-template <bool FAST, int ROT, bool RTAB = false>
+template <bool FAST, int ROT, bool RTAB = false, class CFG = RunTimeCfg>
 __device__ __forceinline__ bool phase_a_telescope(const HotA& H, const DevParams& P, const TelRot& R, const LdsTables& L, const BoreRay& br,
                                                   RayState& st, double& radial_out, LaneMasks& M, double* r3sq = nullptr) {
   static_assert(!RTAB || (FAST && ROT >= 0), "the table serves the solar-source specialisations (no hole loop)");
@@ -1009,19 +1054,19 @@ __device__ __forceinline__ bool phase_a_telescope(const HotA& H, const DevParams
   const double radial = Q0 * inv_radial;       // radialDist (:1905)
 
   if constexpr (RTAB) {
-    if (H.radial_table) {   // wave-uniform
+    if (CFG::kFoldA1 ? CFG::kRadialTable : H.radial_table) {   // wave-uniform
       // the spider's spokes as below; everything else the opaque structures and the shell selection decide is one verdict byte
-      if (H.telescope_kind != SART_TK_LLNL) {
+      if (CFG::kFoldA1 ? !CFG::kIsLlnl : H.telescope_kind != SART_TK_LLNL) {
         const double c_ent = X0 * inv_radial;
         const double xs = fma(H.spider_z, tsx, X0), ys = fma(H.spider_z, tsy, Y0);
         const double c_sp = xs * frsq(fma(xs, xs, ys * ys));
         double meas_a, meas_b;
-        spoke_measure_pair(H.spoke_n, c_ent, c_sp, meas_a, meas_b);
+        spoke_measure_pair(CFG::kFoldA1 ? CFG::kSpokes : H.spoke_n, c_ent, c_sp, meas_a, meas_b);
         const bool spoke_a = meas_a >= H.spoke_cos_thr, spoke_b = meas_b >= H.spoke_cos_thr;
         ok = ok & !(spoke_a | spoke_b);
         okm &= ~(ballot64(spoke_a) | ballot64(spoke_b));
       }
-      const uint32_t v = radial_verdict_table(H, P, L, ROT == 0 && H.telescope_kind != SART_TK_LLNL, radial);
+      const uint32_t v = radial_verdict_table(H, P, L, ROT == 0 && (CFG::kFoldA1 ? !CFG::kIsLlnl : H.telescope_kind != SART_TK_LLNL), radial);
       M.ok = okm & ballot64(v > 63u);
       M.keep = ballot64(v > 127u);
       M.cand = ballot64(v > 191u);
@@ -1133,7 +1178,7 @@ __device__ __forceinline__ bool phase_a_telescope(const HotA& H, const DevParams
 }
 
 // Both halves back to back (histogram and record kernels).
-template <bool FAST, int ROT, bool ZEXT, bool NOWALL = false, bool WORD = false, bool RTAB = false>
+template <bool FAST, int ROT, bool ZEXT, bool NOWALL = false, bool WORD = false, bool RTAB = false, class CFG = RunTimeCfg>
 __device__ __forceinline__ bool phase_a_core(const HotA& H, const DevParams& P, const LdsTables& L, const Uniforms& U, RayState& st,
                                              bool& sampled, bool& reached, double& radial_out, LaneMasks& M, const SinCosCoef* held = nullptr,
                                              double* r3sq = nullptr) {
@@ -1141,7 +1186,7 @@ __device__ __forceinline__ bool phase_a_core(const HotA& H, const DevParams& P, 
   static_assert(!NOWALL || ZEXT, "the constant-path form is a specialisation of the vacuum, unrotated one");
   BoreRay br;
   phase_a_bore<FAST, ZEXT, NOWALL, WORD>(H, P, L, U, st, sampled, reached, br, M, held);
-  return phase_a_telescope<FAST, ROT, RTAB>(H, P, tel_rot_of(P), L, br, st, radial_out, M, r3sq);
+  return phase_a_telescope<FAST, ROT, RTAB, CFG>(H, P, tel_rot_of(P), L, br, st, radial_out, M, r3sq);
 }
 
 // Phase A of the ray with global id `ray_id`: its six uniforms from ONE Philox counter block (x, y, z, w) + its word s of the
@@ -1167,12 +1212,12 @@ __device__ __forceinline__ Uniforms uniforms_of(uint32_t seed_lo, uint32_t seed_
   return U;
 }
 // (WORD = false: the record kernel, which keeps the general draws for both sources of its uniforms)
-template <bool FAST, int ROT, bool ZEXT, bool NOWALL = false, bool WORD = true, bool RTAB = false>
+template <bool FAST, int ROT, bool ZEXT, bool NOWALL = false, bool WORD = true, bool RTAB = false, class CFG = RunTimeCfg>
 __device__ __forceinline__ bool phase_a(const HotA& H, const DevParams& P, const LdsTables& L, uint32_t seed_lo,
                                         uint32_t seed_hi, uint64_t ray_id, uint32_t u3_hi, RayState& st, bool& sampled,
                                         bool& reached, double& radial, LaneMasks& M, const SinCosCoef* held = nullptr,
                                         double* r3sq = nullptr) {
-  return phase_a_core<FAST, ROT, ZEXT, NOWALL, WORD, RTAB>(H, P, L, uniforms_of(seed_lo, seed_hi, ray_id, u3_hi), st, sampled, reached, radial, M, held, r3sq);
+  return phase_a_core<FAST, ROT, ZEXT, NOWALL, WORD, RTAB, CFG>(H, P, L, uniforms_of(seed_lo, seed_hi, ray_id, u3_hi), st, sampled, reached, radial, M, held, r3sq);
 }
 
 // z of pointExitCB in the rotated telescope frame (z0 of :2051) from the ray as phase B knows it: the point of the ray whose z
@@ -1232,7 +1277,8 @@ struct EScanGeo {
   uint64_t m_chip;      // ... and on the chip (the lanes N_PASSED counts, given a non-zero final weight)
   uint64_t m_strip;     // rays inside a strongback strip
 };
-template <bool RECORDS, bool FAST, int GAS, bool ZEXT, bool SCAN = false, bool NODRAW = false, bool ESCAN = false>
+// CFG: HistCfg - how the wave-uniform switches are answered (RunTimeCfg: read per pass; FoldedCfg: constants).
+template <bool RECORDS, bool FAST, int GAS, bool ZEXT, bool SCAN = false, bool NODRAW = false, bool ESCAN = false, class CFG = RunTimeCfg>
 __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, const HotB& HB, const TraceArgs& A,
                                         const RayState& st, int e_idx_in, bool live, RayOut& out, sart_axion_t* rec,
                                         EScanGeo* geo = nullptr) {
@@ -1252,20 +1298,21 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
   // working-set experiments (wrong results by design): 0x04000000 guide rows folded onto 16, 0x02000000 CDF rows folded onto 16,
   // 0x01000000 reflectivity / energy rows folded onto 32
   const uint32_t dbg = (uint32_t)__builtin_amdgcn_readfirstlane((int)A.flags);
-  if (draw_energy) energy_draw_begin<WORD>(HB, (dbg & 0x02000000u) ? (st.r_idx & 15) : st.r_idx, st.u5, st.u5_hi, ed, (dbg & 0x04000000u) ? (st.r_idx & 15) : st.r_idx);
+  if (draw_energy) energy_draw_begin<WORD, CFG>(HB, (dbg & 0x02000000u) ? (st.r_idx & 15) : st.r_idx, st.u5, st.u5_hi, ed, (dbg & 0x04000000u) ? (st.r_idx & 15) : st.r_idx);
 #else
-  if (draw_energy) energy_draw_begin<WORD>(HB, st.r_idx, st.u5, st.u5_hi, ed);
+  if (draw_energy) energy_draw_begin<WORD, CFG>(HB, st.r_idx, st.u5, st.u5_hi, ed);
 #endif
   const ShellDev& sh = L.shells[st.shell];
   // P / A may live in LDS: branch conditions are made wave-uniform (scalar branches) explicitly.
   // FAST: vacuum stage, solar source (known at compile time).
-  const int wolter = __builtin_amdgcn_readfirstlane(P.telescope_wolter);
+  const int wolter = CFG::kFoldB ? CFG::kWolter : __builtin_amdgcn_readfirstlane(P.telescope_wolter);
   static_assert(!ZEXT || GAS >= 0, "the z-extent form needs the stage at compile time");
   static_assert(!SCAN || !RECORDS, "the mass scan accumulates, it writes no records");
   const int stage_gas = (GAS >= 0) ? GAS : __builtin_amdgcn_readfirstlane(P.stage_gas);
   const int test_active = FAST ? 0 : __builtin_amdgcn_readfirstlane(P.test_active);
-  const int n_half_strips = __builtin_amdgcn_readfirstlane(P.n_half_strips);
-  const uint32_t flags = (uint32_t)__builtin_amdgcn_readfirstlane((int)A.flags);
+  const int n_half_strips = CFG::kFoldStrips ? CFG::kHalfStrips : __builtin_amdgcn_readfirstlane(P.n_half_strips);
+  // (folded: every test of a bit of kFoldedFlags is then a constant)
+  const uint32_t flags = CFG::kFoldB ? (uint32_t)__builtin_amdgcn_readfirstlane((int)A.flags) & ~kFoldedFlags : (uint32_t)__builtin_amdgcn_readfirstlane((int)A.flags);
   const double X0 = st.X0, Y0 = st.Y0, tsx = st.tsx, tsy = st.tsy, zcb = st.zcb;
   const double Q0 = fma(X0, X0, Y0 * Y0);
 
@@ -1282,7 +1329,7 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
   double n1z = wolter ? sh.n1_r3t : sh.n1_tan * fma(-sh.n1_tan, z1, sh.r1);
   if (live & !hit1)                           // divergent, skipped when no lane needs it: the normal at the (off-surface) input point
     n1z = normal_z_general(P, sh, 1, m1x, m1y, z1);
-  if (draw_energy) energy_draw_candidates<WORD>(HB, ed);   // the guide word has had the first mirror's arithmetic to arrive
+  if (draw_energy) energy_draw_candidates<WORD, CFG>(HB, ed);   // the guide word has had the first mirror's arithmetic to arrive
   double wx = tsx, wy = tsy, wz = 1.0;
   const double N1 = fma(m1x, m1x, fma(m1y, m1y, n1z * n1z));
   double sin_a1, sin_a2;
@@ -1338,11 +1385,14 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
     double asin_a1, asin_a2;
     asin_small_pair(sin_a1, sin2_a1, sin_a2, sin2_a2, asin_a1, asin_a2);   // getMirrorAngle (:782-795) of both mirrors
     auto angle_cell = [&](double asin_a, double& xu_out) {
-      const double alpha = asin_a * 57.29577951308232;   // degrees
-      const double t = (alpha - amin) * inv_da;
+      // alpha = asin_a * 57.29577951308232 (degrees), and both differences alpha - x as ONE fused operation each: what the
+      // compiler's contraction made of `alpha - x` in every instantiation.  Written out, because the contraction pass decides per
+      // basic block: with the folded form's one block around this arithmetic it kept the product apart - an ulp in xu.
+      constexpr double kDeg = 57.29577951308232;
+      const double t = fma(asin_a, kDeg, -amin) * inv_da;
       int i = (int)t;                 // = floor(t) for t >= 0; negative or NaN t ends in cell 0 through the clamp
       i = max(min(i, na2), 0);
-      xu_out = (alpha - fma((double)i, da, amin)) * inv_da;
+      xu_out = fma(asin_a, kDeg, -fma((double)i, da, amin)) * inv_da;
       return i;
     };
     ia1 = angle_cell(asin_a1, xu1);
@@ -1352,9 +1402,9 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
   // ---- energy index; the energy row and the two reflectivity pairs are requested the moment it is known and consumed
   // behind the detector-plane and window geometry ----
 #ifdef SART_DEBUG_KNOBS
-  const int e_idx = (dbg & 0x01000000u) ? ((draw_energy ? energy_draw_finish<WORD>(HB, ed) : e_idx_in) & 31) : (draw_energy ? energy_draw_finish<WORD>(HB, ed) : e_idx_in);
+  const int e_idx = (dbg & 0x01000000u) ? ((draw_energy ? energy_draw_finish<WORD, CFG>(HB, ed) : e_idx_in) & 31) : (draw_energy ? energy_draw_finish<WORD, CFG>(HB, ed) : e_idx_in);
 #else
-  const int e_idx = draw_energy ? energy_draw_finish<WORD>(HB, ed) : e_idx_in;
+  const int e_idx = draw_energy ? energy_draw_finish<WORD, CFG>(HB, ed) : e_idx_in;
 #endif
   SART_B_STAMP(3, e_idx);
   // Accumulating kernels: only the lanes whose ray is still alive behind both mirrors (nickel, no-hit tests: `live` is settled
@@ -1555,11 +1605,25 @@ __device__ __forceinline__ void phase_b(const DevParams& P, const LdsTables& L, 
     if (gather) behind_the_mirrors();
     // (opaque: the compiler otherwise sinks the compares below into the region and carries their predicates across the join)
     asm volatile("" : "+v"(r_pdx), "+v"(r_pdy), "+v"(r_rdet2), "+v"(r_w_till), "+v"(r_weight));
+#ifdef SART_STAGE_TIMING
+    // Stamps 4 and 5 are taken inside the region.  A value assigned under a lane mask is a per-lane value behind the join: the dead
+    // lanes keep the initial zero - lane 0, whose sums the epilogue stores, among them - and a wave without a live lane skips both
+    // stamps (span 4 = 0 - stamp 3, a number near 2^64 in every such pass).  Both are read back from the first live lane; without one
+    // the region did not run and its two sub-stages are empty: both stamps are stamp 3.
+    {
+      const int src = live_m ? (int)__builtin_ctzll(live_m) : 0;
+      for (int k = 4; k < 6; ++k) {
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)out.tb[k], src);
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(out.tb[k] >> 32), src);
+        out.tb[k] = live_m ? ((uint64_t)hi << 32 | lo) : out.tb[3];
+      }
+    }
+#endif
     // the region's predicates and their masks, with every lane switched on again, as the flat form takes them: the dead
     // lanes' bits are unspecified and fall to live_m (still the rays alive behind the mirrors)
     out.m_till = live_m & ballot64(r_w_till != 0.0);
     if (r_prob_deferred) out.m_till &= ballot64(r_prob != 0.0);
-    const uint64_t off_m = ((flags_j & SART_CF_IGNORE_DET_WINDOW) ? 0ull : ballot64(r_rdet2 > P.radius_window_sq)) | ballot64(fabs(r_pdx) > P.chip_cx) |
+    const uint64_t off_m = ((CFG::kFoldB ? 0u : flags_j & SART_CF_IGNORE_DET_WINDOW) ? 0ull : ballot64(r_rdet2 > P.radius_window_sq)) | ballot64(fabs(r_pdx) > P.chip_cx) |
                            ballot64(fabs(r_pdy) > P.chip_cy);
     out.m_passed = live_m & ~off_m & ballot64(r_weight != 0.0);
     out.reflect = r_reflect; out.weight = r_weight;
@@ -1754,6 +1818,17 @@ template <int BLOCK, bool FAST, bool ROT, int GAS, bool PATHC, bool FIXED, bool 
 __global__ __launch_bounds__(BLOCK) void trace_histogram_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
                                                                 double* __restrict__ acc, HotB HBarg, ScanArgs SCarg) {
   constexpr bool BANDS = false;
+  using CFG = RunTimeCfg;
+#include "sart_trace_histogram.inc"
+}
+// The folded form of the constant-path variants 5 (GAS 0) and 6 (GAS 1): the same body with FoldedCfg - the wave-uniform switches
+// whose answers the reference's default configuration fixes are constants (HistCfg).  The host launches it only where every one of
+// those answers holds (sart_device.h: folded_form_applies); same arguments, same offsets in the argument segment.
+template <int BLOCK, int GAS, bool FIXED>
+__global__ __launch_bounds__(BLOCK) void folded_histogram_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
+                                                                 double* __restrict__ acc, HotB HBarg, ScanArgs SCarg) {
+  constexpr bool FAST = true, ROT = false, PATHC = true, SCAN = false, BANDS = false;
+  using CFG = FoldedCfg<GAS>;
 #include "sart_trace_histogram.inc"
 }
 // The banded mass scan: the SCAN body with BANDS, under a name of its own (same arguments, same offsets in the argument segment).
@@ -1761,6 +1836,7 @@ template <int BLOCK, bool FAST, bool ROT, int GAS, bool PATHC, bool FIXED>
 __global__ __launch_bounds__(BLOCK) void mass_scan_spectra_kernel(HotA H, const DevBlob* __restrict__ blob, TraceArgs A,
                                                                   double* __restrict__ acc, HotB HBarg, ScanArgs SCarg) {
   constexpr bool SCAN = true, BANDS = true;
+  using CFG = RunTimeCfg;
 #include "sart_trace_histogram.inc"
 }
 
@@ -4056,13 +4132,16 @@ extern "C" __attribute__((visibility("default"))) int sart_internal_record_draw(
 int records_block() { return kRecBlock; }
 // Variants: 0 = specialised (solar source, no hole loop) vacuum, not rotated; 1 = generic, not rotated; 2 = generic, rotated;
 // 3 = specialised, gas stage; 4 = specialised, rotated; 5 = variant 0 with the constant path in the magnetic field (PATHC);
-// 6 = variant 3 with the constant path.  All with 1024 threads = 4 waves / SIMD (measured fastest of 256 / 512 / 768 / 1024).
+// 6 = variant 3 with the constant path; 7 / 8 = 5 / 6 with their wave-uniform switches folded (folded_histogram_kernel; the host
+// picks them per launch: sart_device.h, folded_form_applies).  All with 1024 threads = 4 waves / SIMD (measured fastest of 256 / 512 / 768 / 1024).
 // The fused mass scan exists for the variants that can run the gas stage: 1, 2, 3, 6.
 int histogram_block_of(int) { return 1024; }
 
 #define SART_HIST_VARIANTS(X) \
   X(0, true, false, 0, false) X(1, false, false, -1, false) X(2, false, true, -1, false) X(3, true, false, 1, false) \
   X(4, true, true, 0, false) X(5, true, false, 0, true) X(6, true, false, 1, true)
+// 7 / 8: the folded forms of 5 / 6 (folded_histogram_kernel<1024, GAS, FIXED>; launch only: grid and occupancy are those of 5 / 6)
+#define SART_HIST_FOLDED_VARIANTS(X) X(7, 0) X(8, 1)
 #define SART_SCAN_VARIANTS(X) X(1, false, false, -1, false) X(2, false, true, -1, false) X(3, true, false, 1, false) X(6, true, false, 1, true)
 
 // The instantiation of fold kernel K for the accumulation mode
@@ -4109,6 +4188,11 @@ void launch_trace_histogram(const HotA& H, const HotB& HB, const DevBlob* blob, 
     case ID: hipLaunchKernelGGL((trace_histogram_kernel<1024, F, R, G, PC, false>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, SC); break; \
     case 100 + ID: hipLaunchKernelGGL((trace_histogram_kernel<1024, F, R, G, PC, true>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, SC); break;
     SART_HIST_VARIANTS(X)
+#undef X
+#define X(ID, G) \
+    case ID: hipLaunchKernelGGL((folded_histogram_kernel<1024, G, false>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, SC); break; \
+    case 100 + ID: hipLaunchKernelGGL((folded_histogram_kernel<1024, G, true>), dim3(n_blocks), dim3(1024), 0, stream, H, blob, A, acc, HB, SC); break;
+    SART_HIST_FOLDED_VARIANTS(X)
 #undef X
     default: return;
   }

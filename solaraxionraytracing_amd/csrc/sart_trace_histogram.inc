@@ -1,7 +1,8 @@
 // The body of trace_histogram_kernel and of mass_scan_spectra_kernel (sart_kernels.hip, which describes it and includes this file
 // once inside each of the two: one text, so that the histogram kernels compile to the code they had as a single kernel - a shared
 // __device__ function, inlined, does not).  In scope: the template parameters BLOCK, FAST, ROT, GAS, PATHC, FIXED, the constants SCAN
-// and BANDS, and the kernel's parameters H, blob, A, acc, HBarg, SCarg.
+// and BANDS, the configuration type CFG (sart_kernels.hip: HistCfg - RunTimeCfg, or FoldedCfg in folded_histogram_kernel), and the
+// kernel's parameters H, blob, A, acc, HBarg, SCarg.
   // One LDS object with the tables FIRST: their addresses then fit the 16-bit offset field of the ds_ instructions, and a
   // lookup is `ds_read v, v_index_scaled offset:TABLE` instead of a literal moved into a register and added to the index
   // (the rings are addressed from a per-wave scalar base anyway).
@@ -61,12 +62,12 @@
   }
   // The radial verdict table of the solar-source specialisations (HotA::radial_table: the host could build it for this setup).
   constexpr bool RTAB = FAST;
-  if (RTAB && H.radial_table) {
+  if (RTAB && (CFG::kFoldA1 ? CFG::kRadialTable : H.radial_table)) {
     const auto src = as_global(reinterpret_cast<const uint64_t*>(Tb.shell_lut + kRadialTableOffset));
     uint64_t* dst = reinterpret_cast<uint64_t*>(&lds.R);
     for (int i = threadIdx.x; i < kRadialTableCells; i += BLOCK) dst[i] = src[i];
   }
-  stage_tables<BLOCK>(S, Pb, Tb, RTAB && H.radial_table);
+  stage_tables<BLOCK>(S, Pb, Tb, RTAB && (CFG::kFoldA1 ? CFG::kRadialTable : H.radial_table));
   const LdsTables L{S.sincos, S.rcdf_hi, Tb.flux_radius_cdf, S.rguide, S.shells, S.lut, &lds.R, &Tb};
 
   const int lane = threadIdx.x & 63;
@@ -74,7 +75,7 @@
   const uint64_t waves_total = (uint64_t)gridDim.x * (BLOCK / 64);
   const uint64_t wave_global = (uint64_t)blockIdx.x * (BLOCK / 64) + wave;
   // wave-uniform; the host builds no zones for the X-ray test source.  (SCAN without PATHC: ring 0 holds the scan accumulators.)
-  const bool early_reject = (SCAN && !PATHC) ? false : H.n_zones > 0;
+  const bool early_reject = (SCAN && !PATHC) ? false : (CFG::kFoldAcc ? CFG::kZones : H.n_zones > 0);
   // chunks of 256 ids aligned in global-id space; `rel` = id - id_base (fits 32 bits: n_rays < 2^31)
   const uint64_t first_chunk = A.ray_id_offset >> 8;
   uint64_t id_base = first_chunk << 8;
@@ -128,7 +129,7 @@
     constexpr bool ZEXT = FAST && !ROT && GAS >= 0;
     LaneMasks M;
     double r3sq = 0.0;
-    (void)phase_a<FAST, ROT ? 1 : 0, ZEXT, PATHC, true, RTAB>(Hl, Pb, L, A.seed_lo, A.seed_hi, id_base + (uint64_t)rel, u3_hi, st, sampled, reached, radial,
+    (void)phase_a<FAST, ROT ? 1 : 0, ZEXT, PATHC, true, RTAB, CFG>(Hl, Pb, L, A.seed_lo, A.seed_hi, id_base + (uint64_t)rel, u3_hi, st, sampled, reached, radial,
                                                               M, HOLD_SINCOS ? &Ksc : nullptr, ROT ? nullptr : &r3sq);
     const uint64_t valid_m = ballot64(valid);
     n_reached += (uint32_t)__popcll(valid_m & M.reached);
@@ -144,10 +145,10 @@
     uint64_t sure = 0ull;
     // (RTAB: phase A hands both radial compares on as lane masks - from the verdict table where the setup has one, in which case
     // n1_r3sq of the selected shell is read here, where it is needed.)
-    const uint64_t cand = (ROT || Hl.telescope_kind == SART_TK_LLNL) ? 0ull
+    const uint64_t cand = (ROT || (CFG::kFoldA1 ? CFG::kIsLlnl : Hl.telescope_kind == SART_TK_LLNL)) ? 0ull
                                                                      : (selected & (RTAB ? M.cand : ballot64(radial > (double)Pb.mirror_miss_radius)));
     if (cand) {   // wave-uniform
-      if (RTAB && Hl.radial_table) r3sq = L.shells[st.shell].n1_r3sq;
+      if (RTAB && (CFG::kFoldA1 ? CFG::kRadialTable : Hl.radial_table)) r3sq = L.shells[st.shell].n1_r3sq;
       const double zl = Pb.l_mirror, xe = fma(zl, st.tsx, st.X0), ye = fma(zl, st.tsy, st.Y0);
       sure = cand & ballot64(fma(xe, xe, fma(ye, ye, kMirrorMissEps)) < r3sq) &
              ballot64(fma(st.tsx, st.tsx, st.tsy * st.tsy) < (double)Pb.mirror_miss_slope_sq);
@@ -179,6 +180,9 @@
 
   auto run_phase_b = [&](uint32_t n_valid) {
     SART_STAGE_MARK("B");
+#ifdef SART_STAGE_TIMING
+    const uint64_t tb_entry = __builtin_readcyclecounter();
+#endif
     __builtin_amdgcn_s_setprio(SART_PRIO_B);
     RayState st;
     const bool valid = (uint32_t)lane < n_valid;
@@ -208,7 +212,7 @@
       reload_kernarg(HB, offsetof(HistKernArgs, HB));
       // (one round trip beside the ring reads above, not a second one in the middle of the pass)
       asm volatile("" :: "s"(HB.cdf_hi32), "s"(HB.energy_guide), "s"(HB.energy_records), "s"(HB.records_on), "s"(HB.energy_tab), "s"(HB.refl), "s"(HB.refl_n_angles), "s"(HB.cdf_stride));
-      phase_b<false, FAST, GAS, FAST && !ROT && GAS >= 0, SCAN>(Bo.P, L, HB, lds_opaque(Ab), st, (!FAST && H.test_active) ? Pb.n_energies : -1, valid, out, nullptr);
+      phase_b<false, FAST, GAS, FAST && !ROT && GAS >= 0, SCAN, false, false, CFG>(Bo.P, L, HB, lds_opaque(Ab), st, (!FAST && H.test_active) ? Pb.n_energies : -1, valid, out, nullptr);
       if constexpr (SCAN) {
         SART_STAGE_MARK("SCAN");
         // (the per-mass loop stays at phase B's priority: 23.8 against 24.2 ms per 32-mass scan with it below phase A)
@@ -272,7 +276,7 @@
     __builtin_amdgcn_s_setprio(SART_PRIO_ACC);
 #ifdef SART_STAGE_TIMING
     for (int k = 0; k < 5; ++k) cyc_bs[k] += out.tb[k + 1] - out.tb[k];
-    cyc_bs[5] += out.tb[0];     // entry stamps, to place the sub-stages inside the B span
+    cyc_bs[5] += out.tb[0] - tb_entry;   // the ring reads and the argument reload in front of phase B; what follows stamp 5 is the B span minus the six
 #endif
     n_nickel += (uint32_t)__popcll(out.m_nickel);
     n_till += (uint32_t)__popcll(out.m_till);
@@ -351,7 +355,7 @@
           else unsafeAtomicAdd((double*)((gbytes)img + pix * 8u), out.weight);
         }
       }
-      if (Al.spectra) {   // wave-uniform: radial and per-energy histograms behind the scalars
+      if (CFG::kFoldAcc ? CFG::kSpectra : Al.spectra) {   // wave-uniform: radial and per-energy histograms behind the scalars
         double* rad = acc + (size_t)nx * (size_t)ny + SART_ACC_COUNT;
         double* en = rad + 2 * (size_t)Al.n_radial_bins;
         const size_t ne1 = (size_t)Pb.n_energies + 1;
@@ -622,7 +626,7 @@
     r[SART_ACC_N_HIT_NICKEL] = (Sum)(__builtin_amdgcn_s_memrealtime() - real_start);
     // sub-stages of B, packed two per slot (each < 2^40, slot = hi * 2^40 + lo would lose bits in f64): use the sums of x/y/r slots
     r[SART_ACC_SUM_X] = (Sum)cyc_bs[0]; r[SART_ACC_SUM_Y] = (Sum)cyc_bs[1]; r[SART_ACC_SUM_R] = (Sum)cyc_bs[2];
-    r[SART_ACC_SUM_WEIGHTS_SQ] = (Sum)cyc_bs[3]; r[SART_ACC_N_OUTSIDE_IMAGE] = (Sum)cyc_bs[4];
+    r[SART_ACC_SUM_WEIGHTS_SQ] = (Sum)cyc_bs[3]; r[SART_ACC_N_OUTSIDE_IMAGE] = (Sum)cyc_bs[4]; r[SART_ACC_SUM_WEIGHTS] = (Sum)cyc_bs[5];
 #endif
   }
   __syncthreads();

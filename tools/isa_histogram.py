@@ -39,6 +39,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "solaraxionraytracing_amd", "csrc")
 VARIANTS = {0: "Lb1ELb0ELi0ELb0E", 1: "Lb0ELb0ELin1ELb0E", 2: "Lb0ELb1ELin1ELb0E", 3: "Lb1ELb0ELi1ELb0E", 4: "Lb1ELb1ELi0ELb0E",
             5: "Lb1ELb0ELi0ELb1E", 6: "Lb1ELb0ELi1ELb1E"}
+FOLDED = {7: "Li0E", 8: "Li1E"}   # folded_histogram_kernel<1024, GAS, FIXED>: variants 5 / 6 with their wave-uniform switches folded
 
 F64 = re.compile(r"v_(fma|fmac|mul|add|rcp|rsq|sqrt|rndne|trunc|floor|ceil|fract|ldexp|frexp_mant|frexp_exp_i32|div_scale|div_fmas|div_fixup|min|max)_f64")
 CMP = re.compile(r"v_cmpx?_")
@@ -90,7 +91,10 @@ def build_asm() -> str:
 
 
 def kernel_lines(asm_path: str, variant: int, fixed: bool, scan: bool = False, ascan: str | None = None):
-    tag = "_ZN4sart22trace_histogram_kernelILi1024E" + VARIANTS[variant] + ("Lb1E" if fixed else "Lb0E") + ("Lb1E" if scan else "Lb0E")
+    if variant in FOLDED:
+        tag = "_ZN4sart23folded_histogram_kernelILi1024E" + FOLDED[variant] + ("Lb1E" if fixed else "Lb0E")
+    else:
+        tag = "_ZN4sart22trace_histogram_kernelILi1024E" + VARIANTS[variant] + ("Lb1E" if fixed else "Lb0E") + ("Lb1E" if scan else "Lb0E")
     if ascan:   # the fused angular scan: trace_angular_scan_kernel<1024, FAST, GAS, FIXED> (fast: <true, 0>, generic: <false, -1>)
         tag = "_ZN4sart25trace_angular_scan_kernelILi1024E" + ("Lb1ELi0E" if ascan == "fast" else "Lb0ELin1E") + ("Lb1E" if fixed else "Lb0E")
     lines = open(asm_path).read().splitlines()
@@ -114,6 +118,7 @@ def histogram(lines):
     stage = "PROLOGUE"
     next_id = 0
     loop_labels = {}      # label -> index of the first instruction after it (for execnz back edges)
+    back_edge = None      # region of the s_cbranch_execnz just read
     copies = collections.Counter()   # a stage whose marker appears k times was inlined at k call sites: one of them runs per launch
     for raw in lines[1:]:
         l = raw.strip()
@@ -146,8 +151,13 @@ def histogram(lines):
             continue
         parts = l.split()
         mn = parts[0]
+        # `s_cbranch_execnz EARLIER` followed by `s_branch`: the tail of a block the compiler placed out of line, which enters a
+        # guarded region above it if a lane needs it and jumps behind that region otherwise - a guard, not the back edge of a loop
+        if mn == "s_branch" and back_edge is not None:
+            regions[back_edge].update(hot=True, rare=False)
+        back_edge = None
         insts.append([mn, stage, tuple(stack), l])
-        if mn == "s_cbranch_execz" and len(parts) > 1:
+        if mn == "s_cbranch_execz" and len(parts) > 1 and parts[1] not in loop_labels:   # (a label already seen: the guard of a loop, whose region no later label would close)
             regions[next_id] = {"end": parts[1], "hot": False, "rare": False, "weight": 1.0}
             stack.append(next_id)
             next_id += 1
@@ -156,6 +166,7 @@ def histogram(lines):
             regions[next_id] = {"end": None, "hot": False, "rare": True, "weight": 1.0}
             for k in range(loop_labels[parts[1]], len(insts)):
                 insts[k][2] = insts[k][2] + (next_id,)
+            back_edge = next_id
             next_id += 1
     out = collections.OrderedDict()
     dump = []
@@ -288,7 +299,7 @@ def lds_breakdown(hot_lines):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--variant", type=int, default=5, help="0 vacuum, 1 generic, 2 generic rotated, 3 gas, 4 rotated, 5 vacuum + constant path (headline)")
+    ap.add_argument("--variant", type=int, default=5, help="0 vacuum, 1 generic, 2 generic rotated, 3 gas, 4 rotated, 5 vacuum + constant path, 6 gas + constant path, 7 / 8 the folded forms of 5 / 6 (7: headline)")
     ap.add_argument("--fixed", action="store_true", help="the SART_ACCUM_FIXED64 instantiation")
     ap.add_argument("--scan", action="store_true", help="the fused mass-scan instantiation (variants 1, 2, 3, 6)")
     ap.add_argument("--ascan", default=None, choices=["fast", "generic"], help="the fused angular-scan kernel instead (stages A0, A1a, A1b, B, ACC)")

@@ -29,7 +29,7 @@ import csv, glob, collections
 tot = collections.defaultdict(list)
 for f in glob.glob("$OUT/pass*/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
-        if "trace_histogram" in r["Kernel_Name"]:
+        if "trace_histogram" in r["Kernel_Name"] or "folded_histogram" in r["Kernel_Name"]:
             tot[r["Counter_Name"]].append(float(r["Counter_Value"]))
 for k in sorted(tot):
     v = tot[k]

@@ -18,9 +18,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "gpurun_out")
 PROF = os.path.join(ROOT, "profiles")
-WORKLOADS = {   # workload -> (rays per profiled launch, kernel-name substring)
-    "babyiaxo_xmm": (1e9, "trace_histogram"), "cast_llnl_gold": (1e8, "trace_histogram"), "cast_llnl": (1e8, "trace_histogram"), "babyiaxo_xmm_gas": (1e8, "trace_histogram"),
-    "babyiaxo_xmm_rot": (1e8, "trace_histogram"), "babyiaxo_xmm_gas_scan32": (1e9, "trace_histogram"),
+WORKLOADS = {   # workload -> (rays per profiled launch, kernel-name substring; "histogram_kernel": trace_histogram_kernel or its folded form)
+    "babyiaxo_xmm": (1e9, "histogram_kernel"), "cast_llnl_gold": (1e8, "histogram_kernel"), "cast_llnl": (1e8, "histogram_kernel"), "babyiaxo_xmm_gas": (1e8, "histogram_kernel"),
+    "babyiaxo_xmm_rot": (1e8, "histogram_kernel"), "babyiaxo_xmm_gas_scan32": (1e9, "histogram_kernel"),
     "babyiaxo_xmm_ascan16": (2e8, "trace_angular_scan"), "emission_table": (2952000.0, "emission_table_kernel"),
 }
 
@@ -42,7 +42,7 @@ def main():
             shutil.copy(stats[0], os.path.join(PROF, name))
     trace = glob.glob(os.path.join(OUT, "prof_%s" % tag, "**", "*kernel_trace.csv"), recursive=True)
     if trace:
-        rows = [r for r in csv.DictReader(open(trace[0])) if "trace_histogram_kernel" in r["Kernel_Name"]]
+        rows = [r for r in csv.DictReader(open(trace[0])) if "trace_histogram_kernel" in r["Kernel_Name"] or "folded_histogram_kernel" in r["Kernel_Name"]]
         rows.sort(key=lambda r: int(r["Start_Timestamp"]))
         dur = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6 for r in rows]
         big = [x for x in dur if x > 1.0]

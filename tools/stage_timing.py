@@ -32,9 +32,15 @@ for wl in ("babyiaxo_xmm", "cast_llnl_gold", "babyiaxo_xmm/small-tables"):
         wl, ms / nl, tot / waves, tot / waves / (ms / nl * 1e-3) / 1e9, a0 / tot, a1 / tot, b / tot, 1 - (a0 + a1 + b) / tot))
     print("   cycles per launched pass of 64 rays (per wave): A0 %.0f  A1 %.0f  B %.0f  total %.0f" % (
         a0 / passes, a1 / passes, b / passes, tot / passes))
-    bs = [v[L.ACC[k]] for k in ("SUM_X", "SUM_Y", "SUM_R", "SUM_WEIGHTS_SQ", "N_OUTSIDE_IMAGE")]
+    # six spans inside the B span, stamped in phase B (csrc/sart_kernels.hip: SART_B_STAMP; the two stamps inside the live-lane region
+    # are read back from a live lane, a pass without one counts both sub-stages as empty); what is left of the B span lies behind
+    # the last stamp: the lane masks, the counters and the accumulation
+    bs = [v[L.ACC[k]] for k in ("SUM_WEIGHTS", "SUM_X", "SUM_Y", "SUM_R", "SUM_WEIGHTS_SQ", "N_OUTSIDE_IMAGE")]
     nb = v[L.ACC["N_SHELL_SELECTED"]] / 64.0
-    print("   B sub-stages, cycles per B pass: mirror1+nickel %.0f | mirror2+detector plane %.0f | (to weights) %.0f -> energy index %.0f | "
-          "energy row+reflectivity %.0f | window+strips %.0f" % (bs[0] / nb, bs[1] / nb, 0, bs[2] / nb, bs[3] / nb, bs[4] / nb))
-    sel = v[L.ACC["N_SHELL_SELECTED"]] / 64.0
-    print("   B passes %.3g -> %.0f cycles per B pass; shell-selected fraction %.3f" % (sel, b / max(sel, 1), sel / passes))
+    rest = b - sum(bs)
+    assert all(0 <= x < 2.0**53 for x in bs) and rest >= 0, "a sub-stage span is not a span: %r" % (bs,)
+    names = ("ring reads + argument reload", "mirror 1 + nickel", "mirror 2", "angle cells -> energy index", "energy row + reflectivity + detector plane",
+             "window + strips", "masks + accumulation (B span minus the six)")
+    print("   B sub-stages, cycles per B pass: " + " | ".join("%s %.0f" % (nm, x / nb) for nm, x in zip(names, bs + [rest])))
+    print("   B passes %.3g -> %.0f cycles per B pass (sum of the seven: %.0f); shell-selected fraction %.3f" % (
+        nb, b / max(nb, 1), (sum(bs) + rest) / max(nb, 1), nb / passes))
