@@ -309,13 +309,13 @@ struct sart_context {
   DevBuf<uint8_t> d_status;          // a FixedCheck (sart_kernels.hip); its first word is the status
   uint32_t* h_status = nullptr;
   bool status_pending = false;
-  // fused mass scan: per-workgroup per-mass partial sums, scratch accumulators of the blocking call
-  DevBuf<double> d_scan_partials, d_scan, d_scan_fin;
-  DevBuf<double> d_mspec, d_mspec_fin;   // banded mass scan: the blocking form's buffers
+  // Blocking forms of the scans and breakdowns (blocking_form): the scratch the trace fills - rows or accumulator, and the form's
+  // second buffer (banded spectra, per-angle blocks, a breakdown's block) - and the f64 image of both in FIXED64.  Grow-only.
+  DevBuf<double> d_scan, d_scan2, d_scan_fin;
+  DevBuf<double> d_scan_partials;    // fused mass scan: per-workgroup per-mass partial sums
   int blocks_per_cu_mspec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   DevBuf<double> d_ascan_partials;   // fused angular scan: per-workgroup per-angle partial sums
   DevBuf<double> d_aimg_partials;    // ... with images: per-angle per-workgroup scalars
-  DevBuf<double> d_aimg;             // ... scratch blocks of the blocking form
   // fused energy scan: the per-energy tables of the last call's energies (energy_row_of / refl_rows_of, built beside the context's
   // own tables, which they do not touch), reused while the energies and the context's tables stay the same
   uint64_t tables_gen = 0;           // bumped whenever refresh_derived rebuilds the context's tables
@@ -325,25 +325,24 @@ struct sart_context {
   std::vector<double> escan_max;     // [k][4]: |t_window|, |t_strongback|, |a_gas|, max |reflectivity| of energy k (the weight bound)
   std::vector<double> escan_refl;    // [n_coatings][n][n_angles]
   bool escan_uploaded = false;
-  DevBuf<double> d_escan_refl, d_escan_partials, d_escan, d_escan_fin;
+  DevBuf<double> d_escan_refl, d_escan_partials;
   int blocks_per_cu_escan[2] = {0, 0};
-  // per-shell breakdown: per-workgroup shell tables; scratch accumulator / block of the blocking form and their f64 images
-  DevBuf<double> d_shell_partials, d_sacc, d_sacc_fin, d_sblock, d_sblock_fin;
+  // per-shell breakdown: per-workgroup shell tables
+  DevBuf<double> d_shell_partials;
   int blocks_per_cu_shells[2] = {0, 0};
   // emission-channel breakdown: the fraction table [n_radii][n_energies][chan_stride] of the current solar tables (dropped with them),
-  // per-workgroup channel tables; scratch block of the blocking form and its f64 image (the accumulator's scratch is the shells')
+  // per-workgroup channel tables
   bool have_channels = false;
   int n_channels = 0, chan_stride = 0;
-  DevBuf<double> d_chan_frac, d_chan_partials, d_cblock, d_cblock_fin;
+  DevBuf<double> d_chan_frac, d_chan_partials;
   int blocks_per_cu_channels[2] = {0, 0};
-  // solar-origin map (sart_trace_histogram_origin*): per-workgroup head sums, the blocking form's scratch block and its f64 image
-  DevBuf<double> d_origin_partials, d_oblock, d_oblock_fin;
+  // solar-origin map (sart_trace_histogram_origin*): per-workgroup head sums
+  DevBuf<double> d_origin_partials;
   int blocks_per_cu_origin[2] = {0, 0};
-  // aperture map (sart_trace_histogram_aperture*): the grid over the entrance plane (sart_set_aperture_grid), per-workgroup head sums,
-  // the blocking form's scratch block and its f64 image
+  // aperture map (sart_trace_histogram_aperture*): the grid over the entrance plane (sart_set_aperture_grid), per-workgroup head sums
   bool have_aperture = false;
   sart_aperture_grid_t aperture_grid = {};
-  DevBuf<double> d_aperture_partials, d_ablock, d_ablock_fin;
+  DevBuf<double> d_aperture_partials;
   int blocks_per_cu_aperture[2] = {0, 0};
 
   // timing
@@ -1435,6 +1434,134 @@ int status_take(sart_context* c) {   // the stream has been synchronised
   return fail(SART_ERR_ACCUMULATOR, msg);
 }
 
+namespace {
+
+// ---- the host path the fused scans and the histogram launches share ---------------------------------------------------------------
+
+// Workgroups per CU of a kernel: asked once (`query`: the kernel's occupancy), kept in `slot`; SART_HIST_BLOCKS_PER_CU overrides.
+template <class Query>
+int cached_blocks_per_cu(const sart_context* c, int& slot, Query&& query) {
+  if (slot == 0) {
+    slot = std::max(1, query());
+    if (c->knobs.hist_blocks_per_cu > 0) slot = c->knobs.hist_blocks_per_cu;
+  }
+  return slot;
+}
+
+// Per-workgroup partials of a launch of n_blocks workgroups, per_block doubles each.  Too small: launches still running on the
+// context's stream use the buffer that is freed, so the stream is synchronised first; then room for at least 4 workgroups per CU.
+int grow_partials(sart_context* c, DevBuf<double>& buf, int n_blocks, size_t per_block) {
+  if (buf.n >= static_cast<size_t>(n_blocks) * per_block) return 0;
+  SART_HIP(hipStreamSynchronize(c->stream));
+  return buf.resize(std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4) * per_block);
+}
+
+// Launch arguments of a scan, after refresh_derived and sync_blob.  A scan accumulates no image: whatever the caller left in the
+// image fields is not read.
+int scan_args(sart_context* c, const sart_trace_params_t* p, TraceArgs& a) {
+  sart_trace_params_t q = *p;
+  q.image_nx = q.image_ny = 1;
+  q.image_x_min = q.image_y_min = 0.0;
+  q.image_x_max = q.image_y_max = 1.0;
+  q.spectra = 0;
+  if (int rc = make_args(c, &q, a)) return rc;
+  a.fx_scale_w = a.fx_scale_w2 = 0.0;
+  return 0;
+}
+
+// Ray indices inside one launch are 32-bit: f(n, ray_id_offset) for the rays of p in pieces of at most piece_max, until one fails.
+template <class F>
+int for_each_piece(const sart_trace_params_t* p, uint64_t piece_max, F&& f) {
+  for (uint64_t done = 0; done < p->n_rays;) {
+    const uint64_t n = std::min<uint64_t>(p->n_rays - done, piece_max);
+    if (int rc = f(n, p->ray_id_offset + done)) return rc;
+    done += n;
+  }
+  return 0;
+}
+
+// The quanta of rows [k0, k0 + n) of a scan as the finalize kernels take them.  quanta_of(k, qe) gives row k's exponents, formed as
+// the launch that filled the row formed them: a finalized row equals a single launch bit for bit because both come from here.
+template <class QuantaOf>
+int group_quanta(int32_t k0, int n, double* q_w, double* q_w2, QuantaOf&& quanta_of) {
+  for (int k = 0; k < n; ++k) {
+    QuantaExp qe;
+    if (int rc = quanta_of(k0 + k, qe)) return rc;
+    q_w[k] = std::ldexp(1.0, qe.w);
+    q_w2[k] = std::ldexp(1.0, qe.w2);
+  }
+  return 0;
+}
+
+// Raw FIXED64 scan rows -> doubles, after status_ensure: n_points rows of row_len slots in groups of at most kScanMaxMasses from the
+// front (whatever groups the launches took), the shared counter row behind the last one; then the status copy.
+template <class QuantaOf>
+int finalize_scan_rows(sart_context* c, const void* raw_dev, double* out_dev, int32_t n_points, size_t row_len, uint32_t counter_slots,
+                       QuantaOf&& quanta_of) {
+  for (int32_t k0 = 0; k0 < n_points; k0 += kScanMaxMasses) {
+    const int n = std::min<int32_t>(kScanMaxMasses, n_points - k0);
+    double q_w[kScanMaxMasses], q_w2[kScanMaxMasses];
+    if (int rc = group_quanta(k0, n, q_w, q_w2, quanta_of)) return rc;
+    const size_t off = static_cast<size_t>(k0) * row_len;
+    launch_finalize_scan(static_cast<const long long*>(raw_dev) + off, out_dev + off, n, q_w, q_w2, (k0 + n == n_points) ? n : -1,
+                         c->d_status.p, c->stream, counter_slots);
+    SART_HIP(hipGetLastError());
+  }
+  return status_enqueue_copy(c);
+}
+
+// Image, summary and spectra of the accumulator `src` (len doubles, laid out for p) to the host arrays the caller gave.
+int copy_out_accumulator(sart_context* c, const sart_trace_params_t* p, const double* src, size_t len, double* image_out,
+                         sart_summary_t* summary, double* spectra_out) {
+  const size_t nimg = static_cast<size_t>(p->image_nx) * p->image_ny;
+  if (image_out && nimg) SART_HIP(hipMemcpyAsync(image_out, src, nimg * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (summary) SART_HIP(hipMemcpyAsync(summary->v, src + nimg, SART_ACC_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (spectra_out && p->spectra)
+    SART_HIP(hipMemcpyAsync(spectra_out, src + nimg + SART_ACC_COUNT, (len - nimg - SART_ACC_COUNT) * sizeof(double),
+                            hipMemcpyDeviceToHost, c->stream));
+  return 0;
+}
+
+// The blocking form of a scan or a breakdown, after the entry point's own checks: trace(q, dev, dev2) into the context's scratch
+// (grow-only: following the size of every call would free, and so synchronise the device, whenever two calls differ), in FIXED64
+// finalize(raw, raw2, fin) into its f64 image, copy_out(src, src2) to the caller's arrays, synchronise, report what the finalize
+// kernels found.  len2: the form's second buffer (0: none), finalized behind the first (fin + len) or, `fin2_in_place`, by finalize
+// where it lies.
+template <class Trace, class Finalize, class CopyOut>
+int blocking_form(sart_context* c, const sart_trace_params_t* p, size_t len, size_t len2, bool fin2_in_place, Trace&& trace,
+                  Finalize&& finalize, CopyOut&& copy_out) {
+  if (int rc = c->d_scan.reserve(len)) return rc;
+  if (len2)
+    if (int rc = c->d_scan2.reserve(len2)) return rc;
+  sart_trace_params_t q = *p;
+  q.accumulate = 0;   // the blocking form has no accumulator the caller could add into
+  if (int rc = trace(&q, c->d_scan.p, c->d_scan2.p)) return rc;
+  const double *src = c->d_scan.p, *src2 = c->d_scan2.p;
+  if (c->accum_mode == SART_ACCUM_FIXED64) {
+    if (int rc = c->d_scan_fin.reserve(len + (fin2_in_place ? 0 : len2))) return rc;
+    if (int rc = finalize(c->d_scan.p, c->d_scan2.p, c->d_scan_fin.p)) return rc;   // with the caller's p
+    src = c->d_scan_fin.p;
+    if (!fin2_in_place) src2 = c->d_scan_fin.p + len;
+  }
+  if (int rc = copy_out(src, src2)) return rc;
+  SART_HIP(hipStreamSynchronize(c->stream));
+  return status_take(c);
+}
+
+// ... of a scan whose result is its rows alone
+template <class Trace, class Finalize>
+int blocking_rows(sart_context* c, const sart_trace_params_t* p, size_t len, Trace&& trace, Finalize&& finalize, double* out_host) {
+  return blocking_form(
+      c, p, len, 0, true, [&](const sart_trace_params_t* q, double* dev, double*) { return trace(q, dev); },
+      [&](const double* raw, const double*, double* fin) { return finalize(raw, fin); },
+      [&](const double* src, const double*) {
+        SART_HIP(hipMemcpyAsync(out_host, src, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        return 0;
+      });
+}
+
+}  // namespace
+
 // Used by the other translation units of libsart.so (sart_emission.hip); not part of the C-ABI.
 namespace sart {
 __attribute__((visibility("hidden"))) int context_device(sart_context* c) { return c->device; }
@@ -2306,11 +2433,9 @@ struct Breakdown {
   size_t (*block_len)(const sart_context* c, const sart_trace_params_t* p);
   // fills the kernel's argument struct and launches the kernel and its folds
   void (*launch)(sart_context* c, const TraceArgs& a, double* acc_dev, double* block_dev, int n_blocks, bool rotated, bool fixed);
-  // the blocking form: what a launch accepts, the scratch block and its f64 image, the finalize
+  // what a launch and a finalize accept; the finalize kernel of a raw FIXED64 block (breakdown_finalize)
   int (*check)(sart_context* c, const sart_trace_params_t* p);
-  DevBuf<double> sart_context::*block;
-  DevBuf<double> sart_context::*block_fin;
-  int (*finalize)(sart_context* c, const sart_trace_params_t* p, const void* raw_dev, double* out_dev);
+  void (*launch_finalize)(sart_context* c, const sart_trace_params_t* p, const void* raw_dev, double* out_dev);
 };
 struct BreakdownBlock {   // which breakdown a launch fills, if any, and the caller's block
   const Breakdown* kind = nullptr;
@@ -2448,22 +2573,10 @@ int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_
   }
   if (bd.kind) {
     const bool rotated = c->params.rotated != 0;   // generic variants: hist_variant_of 1 / 2
-    int& bpc = (c->*bd.kind->blocks_per_cu)[rotated];
-    if (bpc == 0) {
-      bpc = std::max(1, bd.kind->kernel_blocks_per_cu(rotated));
-      if (c->knobs.hist_blocks_per_cu > 0) bpc = c->knobs.hist_blocks_per_cu;
-    }
+    const int bpc = cached_blocks_per_cu(c, (c->*bd.kind->blocks_per_cu)[rotated], [&] { return bd.kind->kernel_blocks_per_cu(rotated); });
     const int n_blocks = grid_for(a.n_rays, c->n_cu, bpc, 1024);
-    const size_t rows = std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4);
-    if (c->d_partials.n < static_cast<size_t>(n_blocks) * SART_ACC_COUNT) {
-      SART_HIP(hipStreamSynchronize(c->stream));
-      if (int rc = c->d_partials.resize(rows * SART_ACC_COUNT)) return rc;
-    }
-    DevBuf<double>& table_partials = c->*bd.kind->partials;
-    if (table_partials.n < static_cast<size_t>(n_blocks) * bd.kind->partial_slots) {
-      SART_HIP(hipStreamSynchronize(c->stream));
-      if (int rc = table_partials.resize(rows * bd.kind->partial_slots)) return rc;
-    }
+    if (int rc = grow_partials(c, c->d_partials, n_blocks, SART_ACC_COUNT)) return rc;
+    if (int rc = grow_partials(c, c->*bd.kind->partials, n_blocks, bd.kind->partial_slots)) return rc;
     a.partials = c->d_partials.p;
     {
       TimedLaunch tl(c);
@@ -2472,16 +2585,9 @@ int histogram_launch(sart_context* c, const sart_trace_params_t* p, double* acc_
     SART_HIP(hipGetLastError());
     return 0;
   }
-  if (c->blocks_per_cu_hist[variant] == 0) {
-    c->blocks_per_cu_hist[variant] = std::max(1, histogram_blocks_per_cu(variant));
-    if (c->knobs.hist_blocks_per_cu > 0) c->blocks_per_cu_hist[variant] = c->knobs.hist_blocks_per_cu;
-  }
-  const int n_blocks = grid_for(a.n_rays, c->n_cu, c->blocks_per_cu_hist[variant], histogram_block_of(variant));
-  if (c->d_partials.n < static_cast<size_t>(n_blocks) * SART_ACC_COUNT) {   // one row of scalars per workgroup
-    SART_HIP(hipStreamSynchronize(c->stream));
-    const size_t rows = std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4);
-    if (int rc = c->d_partials.resize(rows * SART_ACC_COUNT)) return rc;
-  }
+  const int bpc = cached_blocks_per_cu(c, c->blocks_per_cu_hist[variant], [&] { return histogram_blocks_per_cu(variant); });
+  const int n_blocks = grid_for(a.n_rays, c->n_cu, bpc, histogram_block_of(variant));
+  if (int rc = grow_partials(c, c->d_partials, n_blocks, SART_ACC_COUNT)) return rc;   // one row of scalars per workgroup
   a.partials = c->d_partials.p;
   // variants 5 / 6 with their wave-uniform switches folded (7 / 8) where every folded answer is this launch's; grid, tile and
   // replicas are those of 5 / 6
@@ -2528,6 +2634,25 @@ int aperture_check(sart_context* c, const sart_trace_params_t* p) {
   if (int rc = shells_check(c, p)) return rc;
   if (!c->have_aperture) return fail(SART_ERR_NOT_READY, "no aperture grid (sart_set_aperture_grid)");
   return 0;
+}
+
+// The finalize kernels of the four blocks, with the context's frozen quanta (breakdown_finalize).
+void finalize_shells(sart_context* c, const sart_trace_params_t* p, const void* raw_dev, double* out_dev) {
+  launch_finalize_shells(raw_dev, out_dev, c->setup.n_shells, c->n_energies + 1, p->spectra ? 1 : 0, std::ldexp(1.0, c->weight_exp),
+                         std::ldexp(1.0, c->weight_sq_exp), c->d_status.p, c->stream);
+}
+void finalize_channels(sart_context* c, const sart_trace_params_t* p, const void* raw_dev, double* out_dev) {
+  launch_finalize_channels(raw_dev, out_dev, c->n_channels, c->n_energies + 1, p->spectra ? 1 : 0,
+                           static_cast<size_t>(p->image_nx) * static_cast<size_t>(p->image_ny), std::ldexp(1.0, c->weight_exp),
+                           std::ldexp(1.0, c->weight_sq_exp), c->d_status.p, c->stream);
+}
+void finalize_origin(sart_context* c, const sart_trace_params_t*, const void* raw_dev, double* out_dev) {
+  launch_finalize_origin(raw_dev, out_dev, static_cast<size_t>(c->n_radii) * static_cast<size_t>(c->n_energies),
+                         std::ldexp(1.0, c->weight_exp), std::ldexp(1.0, c->weight_sq_exp), c->d_status.p, c->stream);
+}
+void finalize_aperture(sart_context* c, const sart_trace_params_t*, const void* raw_dev, double* out_dev) {   // cells laid out like the origin map's
+  launch_finalize_origin(raw_dev, out_dev, static_cast<size_t>(c->aperture_grid.nx) * static_cast<size_t>(c->aperture_grid.ny) + 1u,
+                         std::ldexp(1.0, c->weight_exp), std::ldexp(1.0, c->weight_sq_exp), c->d_status.p, c->stream);
 }
 
 void launch_shells(sart_context* c, const TraceArgs& a, double* acc_dev, double* block_dev, int n_blocks, bool rotated, bool fixed) {
@@ -2580,58 +2705,52 @@ void launch_aperture(sart_context* c, const TraceArgs& a, double* acc_dev, doubl
 
 const Breakdown kShells = {kShellImageTileMax, kShellImageTileExtraMax, static_cast<size_t>(kMaxShells) * kShellPartialSlots,
                            &sart_context::d_shell_partials, &sart_context::blocks_per_cu_shells, shell_histogram_blocks_per_cu,
-                           shell_block_len_of, launch_shells, shells_check, &sart_context::d_sblock, &sart_context::d_sblock_fin,
-                           sart_finalize_shells_device};
+                           shell_block_len_of, launch_shells, shells_check, finalize_shells};
 const Breakdown kChannels = {kChanImageTileMax, kChanImageTileExtraMax, static_cast<size_t>(kMaxChannels) * kChanPartialSlots,
                              &sart_context::d_chan_partials, &sart_context::blocks_per_cu_channels, channel_histogram_blocks_per_cu,
-                             channel_block_len_of, launch_channels, channels_check, &sart_context::d_cblock, &sart_context::d_cblock_fin,
-                             sart_finalize_channels_device};
+                             channel_block_len_of, launch_channels, channels_check, finalize_channels};
 
 const Breakdown kOrigin = {kOriginImageTileMax, kOriginImageTileExtraMax, static_cast<size_t>(kOriginPartialSlots),
                            &sart_context::d_origin_partials, &sart_context::blocks_per_cu_origin, origin_histogram_blocks_per_cu,
-                           origin_block_len_of, launch_origin, origin_check, &sart_context::d_oblock, &sart_context::d_oblock_fin,
-                           sart_finalize_origin_device};
+                           origin_block_len_of, launch_origin, origin_check, finalize_origin};
 
 const Breakdown kAperture = {kApertureImageTileMax, kApertureImageTileExtraMax, static_cast<size_t>(kAperturePartialSlots),
                              &sart_context::d_aperture_partials, &sart_context::blocks_per_cu_aperture, aperture_histogram_blocks_per_cu,
-                             aperture_block_len_of, launch_aperture, aperture_check, &sart_context::d_ablock, &sart_context::d_ablock_fin,
-                             sart_finalize_aperture_device};
+                             aperture_block_len_of, launch_aperture, aperture_check, finalize_aperture};
+
+// sart_finalize_{shells,channels,origin,aperture}_device: a raw FIXED64 block of the breakdown `kind` -> doubles.
+int breakdown_finalize(sart_context* c, const sart_trace_params_t* p, const Breakdown& kind, const void* raw_dev, double* out_dev) {
+  if (!c || !p || !raw_dev || !out_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (int rc = kind.check(c, p)) return rc;
+  if (!c->quanta_frozen) return fail(SART_ERR_NOT_READY, "no FIXED64 launch has fixed the quanta yet");
+  SART_HIP(hipSetDevice(c->device));
+  if (int rc = status_ensure(c)) return rc;
+  kind.launch_finalize(c, p, raw_dev, out_dev);
+  SART_HIP(hipGetLastError());
+  return status_enqueue_copy(c);
+}
 
 // The blocking form of a breakdown (sart_trace_histogram_shells / sart_trace_histogram_channels / sart_trace_histogram_origin /
-// sart_trace_histogram_aperture): launch into the context's scratch
-// accumulator and block, finalize both in FIXED64, copy out what the caller asked for.
+// sart_trace_histogram_aperture): launch into the context's scratch accumulator and block, finalize both in FIXED64, copy out what
+// the caller asked for.
 int trace_histogram_breakdown(sart_context* c, const sart_trace_params_t* p, const Breakdown& kind, double* image_out,
                               sart_summary_t* summary, double* spectra_out, double* block_out) {
   if (!c || !p) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
   if (int rc = kind.check(c, p)) return rc;
   SART_HIP(hipSetDevice(c->device));
-  DevBuf<double>& block = c->*kind.block;
-  DevBuf<double>& block_fin = c->*kind.block_fin;
   const size_t len = acc_len_of(c, p), blen = kind.block_len(c, p);
-  if (int rc = c->d_sacc.reserve(len)) return rc;
-  if (int rc = block.reserve(blen)) return rc;
-  sart_trace_params_t q = *p;
-  q.accumulate = 0;   // the blocking form has no accumulator the caller could add into
-  if (int rc = histogram_launch(c, &q, c->d_sacc.p, {&kind, block.p})) return rc;
-  const double* src = c->d_sacc.p;
-  const double* bsrc = block.p;
-  if (c->accum_mode == SART_ACCUM_FIXED64) {
-    if (int rc = c->d_sacc_fin.reserve(len)) return rc;
-    if (int rc = block_fin.reserve(blen)) return rc;
-    if (int rc = sart_finalize_accumulator_device(c, p, c->d_sacc.p, c->d_sacc_fin.p)) return rc;
-    if (int rc = kind.finalize(c, p, block.p, block_fin.p)) return rc;
-    src = c->d_sacc_fin.p;
-    bsrc = block_fin.p;
-  }
-  const size_t nimg = static_cast<size_t>(p->image_nx) * p->image_ny;
-  if (image_out && nimg) SART_HIP(hipMemcpyAsync(image_out, src, nimg * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (summary) SART_HIP(hipMemcpyAsync(summary->v, src + nimg, SART_ACC_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (spectra_out && p->spectra)
-    SART_HIP(hipMemcpyAsync(spectra_out, src + nimg + SART_ACC_COUNT, (len - nimg - SART_ACC_COUNT) * sizeof(double),
-                            hipMemcpyDeviceToHost, c->stream));
-  if (block_out) SART_HIP(hipMemcpyAsync(block_out, bsrc, blen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  SART_HIP(hipStreamSynchronize(c->stream));
-  return status_take(c);
+  return blocking_form(
+      c, p, len, blen, false,
+      [&](const sart_trace_params_t* q, double* acc, double* block) { return histogram_launch(c, q, acc, {&kind, block}); },
+      [&](const double* acc, const double* block, double* fin) {
+        if (int rc = sart_finalize_accumulator_device(c, p, acc, fin)) return rc;
+        return breakdown_finalize(c, p, kind, block, fin + len);
+      },
+      [&](const double* src, const double* bsrc) {
+        if (int rc = copy_out_accumulator(c, p, src, len, image_out, summary, spectra_out)) return rc;
+        if (block_out) SART_HIP(hipMemcpyAsync(block_out, bsrc, blen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        return 0;
+      });
 }
 
 }  // namespace
@@ -2653,15 +2772,7 @@ int sart_trace_histogram_shells_device(sart_context* c, const sart_trace_params_
 }
 
 int sart_finalize_shells_device(sart_context* c, const sart_trace_params_t* p, const void* raw_dev, double* out_dev) {
-  if (!c || !p || !raw_dev || !out_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (int rc = shells_check(c, p)) return rc;
-  if (!c->quanta_frozen) return fail(SART_ERR_NOT_READY, "no FIXED64 launch has fixed the quanta yet");
-  SART_HIP(hipSetDevice(c->device));
-  if (int rc = status_ensure(c)) return rc;
-  launch_finalize_shells(raw_dev, out_dev, c->setup.n_shells, c->n_energies + 1, p->spectra ? 1 : 0, std::ldexp(1.0, c->weight_exp),
-                         std::ldexp(1.0, c->weight_sq_exp), c->d_status.p, c->stream);
-  SART_HIP(hipGetLastError());
-  return status_enqueue_copy(c);
+  return breakdown_finalize(c, p, kShells, raw_dev, out_dev);
 }
 
 int sart_trace_histogram_shells(sart_context* c, const sart_trace_params_t* p, double* image_out, sart_summary_t* summary,
@@ -2777,16 +2888,7 @@ int sart_trace_histogram_channels_device(sart_context* c, const sart_trace_param
 }
 
 int sart_finalize_channels_device(sart_context* c, const sart_trace_params_t* p, const void* raw_dev, double* out_dev) {
-  if (!c || !p || !raw_dev || !out_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (int rc = channels_check(c, p)) return rc;
-  if (!c->quanta_frozen) return fail(SART_ERR_NOT_READY, "no FIXED64 launch has fixed the quanta yet");
-  SART_HIP(hipSetDevice(c->device));
-  if (int rc = status_ensure(c)) return rc;
-  launch_finalize_channels(raw_dev, out_dev, c->n_channels, c->n_energies + 1, p->spectra ? 1 : 0,
-                           static_cast<size_t>(p->image_nx) * static_cast<size_t>(p->image_ny), std::ldexp(1.0, c->weight_exp),
-                           std::ldexp(1.0, c->weight_sq_exp), c->d_status.p, c->stream);
-  SART_HIP(hipGetLastError());
-  return status_enqueue_copy(c);
+  return breakdown_finalize(c, p, kChannels, raw_dev, out_dev);
 }
 
 int sart_trace_histogram_channels(sart_context* c, const sart_trace_params_t* p, double* image_out, sart_summary_t* summary,
@@ -2807,15 +2909,7 @@ int sart_trace_histogram_origin_device(sart_context* c, const sart_trace_params_
 }
 
 int sart_finalize_origin_device(sart_context* c, const sart_trace_params_t* p, const void* raw_dev, double* out_dev) {
-  if (!c || !p || !raw_dev || !out_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (int rc = origin_check(c, p)) return rc;
-  if (!c->quanta_frozen) return fail(SART_ERR_NOT_READY, "no FIXED64 launch has fixed the quanta yet");
-  SART_HIP(hipSetDevice(c->device));
-  if (int rc = status_ensure(c)) return rc;
-  launch_finalize_origin(raw_dev, out_dev, static_cast<size_t>(c->n_radii) * static_cast<size_t>(c->n_energies),
-                         std::ldexp(1.0, c->weight_exp), std::ldexp(1.0, c->weight_sq_exp), c->d_status.p, c->stream);
-  SART_HIP(hipGetLastError());
-  return status_enqueue_copy(c);
+  return breakdown_finalize(c, p, kOrigin, raw_dev, out_dev);
 }
 
 int sart_trace_histogram_origin(sart_context* c, const sart_trace_params_t* p, double* image_out, sart_summary_t* summary,
@@ -2856,15 +2950,7 @@ int sart_trace_histogram_aperture_device(sart_context* c, const sart_trace_param
 }
 
 int sart_finalize_aperture_device(sart_context* c, const sart_trace_params_t* p, const void* raw_dev, double* out_dev) {
-  if (!c || !p || !raw_dev || !out_dev) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (int rc = aperture_check(c, p)) return rc;
-  if (!c->quanta_frozen) return fail(SART_ERR_NOT_READY, "no FIXED64 launch has fixed the quanta yet");
-  SART_HIP(hipSetDevice(c->device));
-  if (int rc = status_ensure(c)) return rc;
-  launch_finalize_origin(raw_dev, out_dev, static_cast<size_t>(c->aperture_grid.nx) * static_cast<size_t>(c->aperture_grid.ny) + 1u,
-                         std::ldexp(1.0, c->weight_exp), std::ldexp(1.0, c->weight_sq_exp), c->d_status.p, c->stream);
-  SART_HIP(hipGetLastError());
-  return status_enqueue_copy(c);
+  return breakdown_finalize(c, p, kAperture, raw_dev, out_dev);
 }
 
 int sart_trace_histogram_aperture(sart_context* c, const sart_trace_params_t* p, double* image_out, sart_summary_t* summary,
@@ -2889,19 +2975,13 @@ int sart_trace_histogram_spectra(sart_context* c, const sart_trace_params_t* p, 
   if (fresh) q.accumulate = 0;
   if (int rc = sart_trace_histogram_device(c, &q, c->d_acc.p)) return rc;
   c->d_acc_stale = false;
-  const size_t nimg = static_cast<size_t>(p->image_nx) * p->image_ny;
   const double* src = c->d_acc.p;
   if (c->accum_mode == SART_ACCUM_FIXED64) {   // the scratch accumulator holds integers: hand out its f64 image
-    if (int rc = c->d_fin.resize(len)) return rc;
+    if (int rc = c->d_fin.reserve(len)) return rc;
     if (int rc = sart_finalize_accumulator_device(c, p, c->d_acc.p, c->d_fin.p)) return rc;
     src = c->d_fin.p;
   }
-  if (image_out && nimg) SART_HIP(hipMemcpyAsync(image_out, src, nimg * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (summary)
-    SART_HIP(hipMemcpyAsync(summary->v, src + nimg, SART_ACC_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (spectra_out && p->spectra)
-    SART_HIP(hipMemcpyAsync(spectra_out, src + nimg + SART_ACC_COUNT, (len - nimg - SART_ACC_COUNT) * sizeof(double),
-                            hipMemcpyDeviceToHost, c->stream));
+  if (int rc = copy_out_accumulator(c, p, src, len, image_out, summary, spectra_out)) return rc;
   SART_HIP(hipStreamSynchronize(c->stream));
   // FIXED64: the quantum is derived from a BOUND of the weights.  If what was accumulated averages below 2^12 quanta per ray
   // (tables or flags the bound does not see through), or a slot wrapped, the finalize kernel has said so: an error, not noise.
@@ -3018,6 +3098,11 @@ int bands_prepare(const sart_context* c, const sart_energy_bands_t* b, BandSpec&
   return 0;
 }
 
+// The quanta of a mass's row: those a single launch at that mass freezes.
+int mass_quanta(const sart_context* c, const sart_trace_params_t* p, double m_axion, QuantaExp& qe) {
+  return quanta_exp_of(c, weight_bound_of(c, p->flags, dm2_abs_of(c, m_axion)), qe);
+}
+
 // The fused mass scan; with `bands` the banded form, which also fills `spectra_dev`.
 int trace_mass_scan_impl(sart_context* c, const sart_trace_params_t* p, const double* masses, int32_t n_masses, const sart_energy_bands_t* bands,
                          double* scan_dev, double* spectra_dev) {
@@ -3033,41 +3118,33 @@ int trace_mass_scan_impl(sart_context* c, const sart_trace_params_t* p, const do
   if (!c->params.stage_gas)
     return fail(SART_ERR_INVALID_ARGUMENT, "sart_trace_mass_scan: the setup's stage is vacuum, whose conversion probability "
                                            "(raytracer.nim:363-365) does not depend on the axion mass");
-  sart_trace_params_t q = *p;   // a scan accumulates no image: whatever the caller left in the image fields is not read
-  q.image_nx = q.image_ny = 1;
-  q.image_x_min = q.image_y_min = 0.0;
-  q.image_x_max = q.image_y_max = 1.0;
-  q.spectra = 0;
   TraceArgs a;
-  if (int rc = make_args(c, &q, a)) return rc;
-  a.fx_scale_w = a.fx_scale_w2 = 0.0;
+  if (int rc = scan_args(c, p, a)) return rc;
   const bool fixed = c->accum_mode == SART_ACCUM_FIXED64;
   BandSpec bs = {0, 0u, 0u, 0};
   if (bands)
     if (int rc = bands_prepare(c, bands, bs)) return rc;
   const int variant = hist_variant_of(c);
   if (variant != 1 && variant != 2 && variant != 3 && variant != 6) return fail(SART_ERR_INTERNAL, "no scan kernel for this variant");
-  int& blocks_per_cu = bands ? c->blocks_per_cu_mspec[variant] : c->blocks_per_cu_hist[variant];
-  if (blocks_per_cu == 0) {
-    blocks_per_cu = std::max(1, bands ? mass_scan_spectra_blocks_per_cu(variant) : histogram_blocks_per_cu(variant));
-    if (c->knobs.hist_blocks_per_cu > 0) blocks_per_cu = c->knobs.hist_blocks_per_cu;
-  }
+  const int blocks_per_cu = cached_blocks_per_cu(c, bands ? c->blocks_per_cu_mspec[variant] : c->blocks_per_cu_hist[variant], [&] {
+    return bands ? mass_scan_spectra_blocks_per_cu(variant) : histogram_blocks_per_cu(variant);
+  });
   // ray indices inside one launch are 32-bit: pieces of at most 2^31 rays (banded: 2^30, see below); every piece runs once per group of masses
   const uint64_t piece = bands ? (1ull << 30) : (1ull << 31);
   if (bands && fixed) {
     // A band cell of a workgroup can receive every ray the workgroup traces in one launch (sart_kernels.hip: BANDS): chunks of 256
     // ids go round the grid's waves, 16 waves per workgroup.  Sum of w: < 2^(63 - headroom) quanta per ray; sum of w^2: < 2^39.
     const uint64_t room = std::min<uint64_t>(1ull << 23, 1ull << (c->headroom_bits - 1));
-    for (uint64_t done = 0; done < p->n_rays;) {
-      const uint64_t n = std::min<uint64_t>(p->n_rays - done, piece);
-      const uint64_t n_chunks = (((p->ray_id_offset + done) & 255u) + n + 255u) >> 8;
+    const int rc = for_each_piece(p, piece, [&](uint64_t n, uint64_t ray_id_offset) {
+      const uint64_t n_chunks = ((ray_id_offset & 255u) + n + 255u) >> 8;
       const uint64_t waves = static_cast<uint64_t>(grid_for(n, c->n_cu, blocks_per_cu, histogram_block_of(variant))) * 16u;
       if ((n_chunks + waves - 1) / waves * 16u * 256u > room)
         return fail(SART_ERR_INVALID_ARGUMENT, "FIXED64 banded mass scan: one workgroup would trace more rays in a launch than a band cell has "
                                                "room for at this headroom (2^(headroom_bits - 1), at most 2^23): use a larger headroom or "
                                                "split the rays over accumulating calls");
-      done += n;
-    }
+      return 0;
+    });
+    if (rc) return rc;
   }
   if (!p->accumulate) {
     SART_HIP(hipMemsetAsync(scan_dev, 0, sart_mass_scan_len(n_masses) * sizeof(double), c->stream));
@@ -3075,24 +3152,15 @@ int trace_mass_scan_impl(sart_context* c, const sart_trace_params_t* p, const do
   }
   if (p->n_rays == 0) return 0;
   const size_t n_cells = bands ? static_cast<size_t>(bands->n_bands) + 1u : 0u;
-  for (uint64_t done = 0; done < p->n_rays;) {
-    const uint64_t n = std::min<uint64_t>(p->n_rays - done, piece);
+  return for_each_piece(p, piece, [&](uint64_t n, uint64_t ray_id_offset) {
     a.n_rays = n;
-    a.ray_id_offset = p->ray_id_offset + done;
+    a.ray_id_offset = ray_id_offset;
     const int n_blocks = grid_for(n, c->n_cu, blocks_per_cu, histogram_block_of(variant));
-    if (c->d_partials.n < static_cast<size_t>(n_blocks) * SART_ACC_COUNT) {
-      SART_HIP(hipStreamSynchronize(c->stream));
-      const size_t rows = std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4);
-      if (int rc = c->d_partials.resize(rows * SART_ACC_COUNT)) return rc;
-    }
+    if (int rc = grow_partials(c, c->d_partials, n_blocks, SART_ACC_COUNT)) return rc;
     // (banded: a workgroup's cells behind the plain rows; plain stores cover every slot the folds read - no memset - and the scratch
     // is the context's, on the context's stream)
     const size_t per_block = static_cast<size_t>(kScanMaxMasses * kScanPartialSlots) + (bands ? static_cast<size_t>(kScanBandSlots) : 0u);
-    if (c->d_scan_partials.n < static_cast<size_t>(n_blocks) * per_block) {
-      SART_HIP(hipStreamSynchronize(c->stream));
-      const size_t rows = std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4);
-      if (int rc = c->d_scan_partials.resize(rows * per_block)) return rc;
-    }
+    if (int rc = grow_partials(c, c->d_scan_partials, n_blocks, per_block)) return rc;
     a.partials = c->d_partials.p;
     for (int32_t k0 = 0; k0 < n_masses; k0 += kScanMaxMasses) {
       ScanArgs sc;
@@ -3111,7 +3179,7 @@ int trace_mass_scan_impl(sart_context* c, const sart_trace_params_t* p, const do
         m.fx_scale_w = m.fx_scale_w2 = 0.0;
         if (fixed) {
           QuantaExp qe;
-          if (int rc = quanta_exp_of(c, weight_bound_of(c, p->flags, m.dm2_abs), qe)) return rc;
+          if (int rc = mass_quanta(c, p, masses[k0 + k], qe)) return rc;
           m.fx_scale_w = std::ldexp(1.0, -qe.w);
           m.fx_scale_w2 = std::ldexp(1.0, -qe.w2);
         }
@@ -3129,9 +3197,8 @@ int trace_mass_scan_impl(sart_context* c, const sart_trace_params_t* p, const do
       }
       SART_HIP(hipGetLastError());
     }
-    done += n;
-  }
-  return 0;
+    return 0;
+  });
 }
 
 }  // namespace
@@ -3158,41 +3225,17 @@ int sart_finalize_mass_scan_device(sart_context* c, const sart_trace_params_t* p
   if (int rc = refresh_derived(c)) return rc;
   if (int rc = sync_blob(c)) return rc;
   if (int rc = status_ensure(c)) return rc;
-  for (int32_t k0 = 0; k0 < n_masses; k0 += kScanMaxMasses) {
-    const int n = std::min<int32_t>(kScanMaxMasses, n_masses - k0);
-    double q_w[kScanMaxMasses], q_w2[kScanMaxMasses];
-    for (int k = 0; k < n; ++k) {
-      QuantaExp qe;
-      if (int rc = quanta_exp_of(c, weight_bound_of(c, p->flags, dm2_abs_of(c, masses[k0 + k])), qe)) return rc;
-      q_w[k] = std::ldexp(1.0, qe.w);
-      q_w2[k] = std::ldexp(1.0, qe.w2);
-    }
-    const size_t off = static_cast<size_t>(k0) * SART_SCAN_ROW;
-    launch_finalize_scan(static_cast<const long long*>(raw_dev) + off, out_dev + off, n, q_w, q_w2,
-                         (k0 + n == n_masses) ? n : -1, c->d_status.p, c->stream, 1u << SART_SCAN_N_PASSED);   // the counter row sits behind the last group
-    SART_HIP(hipGetLastError());
-  }
-  return status_enqueue_copy(c);
+  return finalize_scan_rows(c, raw_dev, out_dev, n_masses, SART_SCAN_ROW, 1u << SART_SCAN_N_PASSED,
+                            [&](int32_t k, QuantaExp& qe) { return mass_quanta(c, p, masses[k], qe); });
 }
 
 int sart_trace_mass_scan(sart_context* c, const sart_trace_params_t* p, const double* masses, int32_t n_masses, double* out_host) {
   if (int rc = scan_check(c, p, masses, n_masses)) return rc;
   if (!out_host) return fail(SART_ERR_INVALID_ARGUMENT, "output is NULL");
   SART_HIP(hipSetDevice(c->device));
-  const size_t len = sart_mass_scan_len(n_masses);
-  if (int rc = c->d_scan.resize(len)) return rc;
-  sart_trace_params_t q = *p;
-  q.accumulate = 0;   // the blocking form has no accumulator the caller could add into
-  if (int rc = sart_trace_mass_scan_device(c, &q, masses, n_masses, c->d_scan.p)) return rc;
-  const double* src = c->d_scan.p;
-  if (c->accum_mode == SART_ACCUM_FIXED64) {
-    if (int rc = c->d_scan_fin.resize(len)) return rc;
-    if (int rc = sart_finalize_mass_scan_device(c, p, masses, n_masses, c->d_scan.p, c->d_scan_fin.p)) return rc;
-    src = c->d_scan_fin.p;
-  }
-  SART_HIP(hipMemcpyAsync(out_host, src, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  SART_HIP(hipStreamSynchronize(c->stream));
-  return status_take(c);
+  return blocking_rows(
+      c, p, sart_mass_scan_len(n_masses), [&](const sart_trace_params_t* q, double* dev) { return sart_trace_mass_scan_device(c, q, masses, n_masses, dev); },
+      [&](const double* raw, double* fin) { return sart_finalize_mass_scan_device(c, p, masses, n_masses, raw, fin); }, out_host);
 }
 
 int sart_finalize_mass_scan_spectra_device(sart_context* c, const sart_trace_params_t* p, const double* masses, int32_t n_masses,
@@ -3213,12 +3256,7 @@ int sart_finalize_mass_scan_spectra_device(sart_context* c, const sart_trace_par
   for (int32_t k0 = 0; k0 < n_masses; k0 += kScanMaxMasses) {
     const int n = std::min<int32_t>(kScanMaxMasses, n_masses - k0);
     double q_w[kScanMaxMasses], q_w2[kScanMaxMasses];
-    for (int k = 0; k < n; ++k) {
-      QuantaExp qe;
-      if (int rc = quanta_exp_of(c, weight_bound_of(c, p->flags, dm2_abs_of(c, masses[k0 + k])), qe)) return rc;
-      q_w[k] = std::ldexp(1.0, qe.w);
-      q_w2[k] = std::ldexp(1.0, qe.w2);
-    }
+    if (int rc = group_quanta(k0, n, q_w, q_w2, [&](int32_t k, QuantaExp& qe) { return mass_quanta(c, p, masses[k], qe); })) return rc;
     const bool last = k0 + n == n_masses;   // the counts block sits behind the last group
     const size_t at = static_cast<size_t>(k0) * n_cells * SART_MSPEC_CELL, counts_at = static_cast<size_t>(n_masses) * n_cells * SART_MSPEC_CELL;
     launch_finalize_scan_bands(rows + static_cast<size_t>(k0) * SART_SCAN_ROW, rows + static_cast<size_t>(n_masses) * SART_SCAN_ROW, spec + at,
@@ -3236,22 +3274,17 @@ int sart_trace_mass_scan_spectra(sart_context* c, const sart_trace_params_t* p, 
   if (!scan_out_host || !spectra_out_host) return fail(SART_ERR_INVALID_ARGUMENT, "output is NULL");
   SART_HIP(hipSetDevice(c->device));
   const size_t len = sart_mass_scan_len(n_masses), slen = sart_mass_scan_spectra_len(n_masses, bands->n_bands);
-  if (int rc = c->d_scan.resize(len)) return rc;
-  if (int rc = c->d_mspec.resize(slen)) return rc;
-  sart_trace_params_t q = *p;
-  q.accumulate = 0;   // the blocking form has no accumulator the caller could add into
-  if (int rc = sart_trace_mass_scan_spectra_device(c, &q, masses, n_masses, bands, c->d_scan.p, c->d_mspec.p)) return rc;
-  const double *src = c->d_scan.p, *ssrc = c->d_mspec.p;
-  if (c->accum_mode == SART_ACCUM_FIXED64) {
-    if (int rc = c->d_mspec_fin.resize(len + slen)) return rc;
-    if (int rc = sart_finalize_mass_scan_spectra_device(c, p, masses, n_masses, bands, c->d_scan.p, c->d_mspec.p, c->d_mspec_fin.p)) return rc;
-    src = c->d_mspec_fin.p;
-    ssrc = c->d_mspec_fin.p + len;
-  }
-  SART_HIP(hipMemcpyAsync(scan_out_host, src, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  SART_HIP(hipMemcpyAsync(spectra_out_host, ssrc, slen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  SART_HIP(hipStreamSynchronize(c->stream));
-  return status_take(c);
+  return blocking_form(
+      c, p, len, slen, false,
+      [&](const sart_trace_params_t* q, double* dev, double* spec) { return sart_trace_mass_scan_spectra_device(c, q, masses, n_masses, bands, dev, spec); },
+      [&](const double* raw, const double* spec, double* fin) {   // rows, then spectra: the finalize's own layout
+        return sart_finalize_mass_scan_spectra_device(c, p, masses, n_masses, bands, raw, spec, fin);
+      },
+      [&](const double* src, const double* ssrc) {
+        SART_HIP(hipMemcpyAsync(scan_out_host, src, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        SART_HIP(hipMemcpyAsync(spectra_out_host, ssrc, slen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        return 0;
+      });
 }
 
 // ---- fused energy scan (include/sart.h) ----------------------------------------------------------------------------------------
@@ -3320,6 +3353,12 @@ double escan_weight_bound(const sart_context* c, uint32_t flags, int32_t k) {
                            gas_prob ? gas_prob_bound_rows(c, c->params.gas_dm2_abs, &c->escan_rows[k], 1) : 0.0);
 }
 
+// The quanta of energy k's row, after escan_tables: those a single launch at that energy freezes (sart_trace_histogram_device,
+// accumulate == 0).
+int escan_quanta(const sart_context* c, const sart_trace_params_t* p, int32_t k, QuantaExp& qe) {
+  return quanta_exp_of(c, escan_weight_bound(c, p->flags, k), qe);
+}
+
 // Balanced groups of at most kEScanMaxEnergies: group g of n_groups starts at first_of(g) (99 -> 25 + 25 + 25 + 24).
 struct EScanGroups {
   int32_t n, n_groups;
@@ -3336,14 +3375,8 @@ int sart_trace_energy_scan_device(sart_context* c, const sart_trace_params_t* p,
   if (int rc = escan_check(c, p, energies, n_energies)) return rc;
   if (!scan_dev) return fail(SART_ERR_INVALID_ARGUMENT, "scan accumulator is NULL");
   if (int rc = escan_prepare(c, p, energies, n_energies)) return rc;
-  sart_trace_params_t q = *p;   // a scan accumulates no image: whatever the caller left in the image fields is not read
-  q.image_nx = q.image_ny = 1;
-  q.image_x_min = q.image_y_min = 0.0;
-  q.image_x_max = q.image_y_max = 1.0;
-  q.spectra = 0;
   TraceArgs a;
-  if (int rc = make_args(c, &q, a)) return rc;
-  a.fx_scale_w = a.fx_scale_w2 = 0.0;
+  if (int rc = scan_args(c, p, a)) return rc;
   const bool fixed = c->accum_mode == SART_ACCUM_FIXED64;
   if (int rc = escan_tables(c, energies, n_energies, true)) return rc;
   EScanArgs en;
@@ -3357,9 +3390,9 @@ int sart_trace_energy_scan_device(sart_context* c, const sart_trace_params_t* p,
     std::memset(&r, 0, sizeof r);
     r.t_window = e.t_window; r.t_strongback = e.t_strongback; r.a_gas = e.a_gas;
     r.gamma = e.gamma; r.inv_two_e_ev = e.inv_two_e_ev; r.mu_pipe = e.mu_pipe; r.mu_magnet = e.mu_magnet;
-    if (fixed) {   // the quanta a single launch at this energy freezes (sart_trace_histogram_device, accumulate == 0)
+    if (fixed) {
       QuantaExp qe;
-      if (int rc = quanta_exp_of(c, escan_weight_bound(c, p->flags, k), qe)) return rc;
+      if (int rc = escan_quanta(c, p, k, qe)) return rc;
       r.fx_scale_w = std::ldexp(1.0, -qe.w);
       r.fx_scale_w2 = std::ldexp(1.0, -qe.w2);
     }
@@ -3367,25 +3400,14 @@ int sart_trace_energy_scan_device(sart_context* c, const sart_trace_params_t* p,
   if (!p->accumulate) SART_HIP(hipMemsetAsync(scan_dev, 0, sart_energy_scan_len(n_energies) * sizeof(double), c->stream));
   if (p->n_rays == 0) return 0;
   const bool rotated = c->params.rotated != 0;   // hist_variant_of: 1 / 2 for the test source
-  if (c->blocks_per_cu_escan[rotated] == 0) {
-    c->blocks_per_cu_escan[rotated] = std::max(1, energy_scan_blocks_per_cu(rotated));
-    if (c->knobs.hist_blocks_per_cu > 0) c->blocks_per_cu_escan[rotated] = c->knobs.hist_blocks_per_cu;
-  }
+  const int bpc = cached_blocks_per_cu(c, c->blocks_per_cu_escan[rotated], [&] { return energy_scan_blocks_per_cu(rotated); });
   // ray indices inside one launch are 32-bit: pieces of at most 2^31 rays; every piece runs once per group of energies
-  for (uint64_t done = 0; done < p->n_rays;) {
-    const uint64_t n = std::min<uint64_t>(p->n_rays - done, 1ull << 31);
+  return for_each_piece(p, 1ull << 31, [&](uint64_t n, uint64_t ray_id_offset) {
     a.n_rays = n;
-    a.ray_id_offset = p->ray_id_offset + done;
-    const int n_blocks = grid_for(n, c->n_cu, c->blocks_per_cu_escan[rotated], 1024);
-    const size_t rows_min = std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4);
-    if (c->d_partials.n < static_cast<size_t>(n_blocks) * SART_ACC_COUNT) {
-      SART_HIP(hipStreamSynchronize(c->stream));
-      if (int rc = c->d_partials.resize(rows_min * SART_ACC_COUNT)) return rc;
-    }
-    if (c->d_escan_partials.n < static_cast<size_t>(n_blocks) * kEScanMaxEnergies * kScanPartialSlots) {
-      SART_HIP(hipStreamSynchronize(c->stream));
-      if (int rc = c->d_escan_partials.resize(rows_min * kEScanMaxEnergies * kScanPartialSlots)) return rc;
-    }
+    a.ray_id_offset = ray_id_offset;
+    const int n_blocks = grid_for(n, c->n_cu, bpc, 1024);
+    if (int rc = grow_partials(c, c->d_partials, n_blocks, SART_ACC_COUNT)) return rc;
+    if (int rc = grow_partials(c, c->d_escan_partials, n_blocks, static_cast<size_t>(kEScanMaxEnergies) * kScanPartialSlots)) return rc;
     a.partials = c->d_partials.p;
     for (int32_t g = 0; g < groups.n_groups; ++g) {
       const int32_t k0 = groups.first_of(g);
@@ -3401,9 +3423,8 @@ int sart_trace_energy_scan_device(sart_context* c, const sart_trace_params_t* p,
       }
       SART_HIP(hipGetLastError());
     }
-    done += n;
-  }
-  return 0;
+    return 0;
+  });
 }
 
 int sart_finalize_energy_scan_device(sart_context* c, const sart_trace_params_t* p, const double* energies, int32_t n_energies,
@@ -3413,43 +3434,20 @@ int sart_finalize_energy_scan_device(sart_context* c, const sart_trace_params_t*
   if (int rc = escan_prepare(c, p, energies, n_energies)) return rc;
   if (int rc = status_ensure(c)) return rc;
   if (int rc = escan_tables(c, energies, n_energies, false)) return rc;
-  const EScanGroups groups(n_energies);
-  for (int32_t g = 0; g < groups.n_groups; ++g) {
-    const int32_t k0 = groups.first_of(g), n = groups.size_of(g);
-    double q_w[kScanMaxMasses], q_w2[kScanMaxMasses];
-    static_assert(kEScanMaxEnergies <= kScanMaxMasses, "finalize_scan_kernel takes the quanta of one group");
-    for (int k = 0; k < n; ++k) {
-      QuantaExp qe;
-      if (int rc = quanta_exp_of(c, escan_weight_bound(c, p->flags, k0 + k), qe)) return rc;
-      q_w[k] = std::ldexp(1.0, qe.w);
-      q_w2[k] = std::ldexp(1.0, qe.w2);
-    }
-    const size_t off = static_cast<size_t>(k0) * SART_ESCAN_ROW;
-    launch_finalize_scan(static_cast<const long long*>(raw_dev) + off, out_dev + off, n, q_w, q_w2, (k0 + n == n_energies) ? n : -1,
-                         c->d_status.p, c->stream, (1u << SART_ESCAN_N_PASSED) | (1u << SART_ESCAN_N_PASSED_TILL_WINDOW));
-    SART_HIP(hipGetLastError());
-  }
-  return status_enqueue_copy(c);
+  static_assert(SART_ESCAN_ROW == SART_SCAN_ROW, "the scans share the finalize kernel and its row");
+  return finalize_scan_rows(c, raw_dev, out_dev, n_energies, SART_ESCAN_ROW,
+                            (1u << SART_ESCAN_N_PASSED) | (1u << SART_ESCAN_N_PASSED_TILL_WINDOW),
+                            [&](int32_t k, QuantaExp& qe) { return escan_quanta(c, p, k, qe); });
 }
 
 int sart_trace_energy_scan(sart_context* c, const sart_trace_params_t* p, const double* energies, int32_t n_energies, double* out_host) {
   if (int rc = escan_check(c, p, energies, n_energies)) return rc;
   if (!out_host) return fail(SART_ERR_INVALID_ARGUMENT, "output is NULL");
   if (int rc = escan_prepare(c, p, energies, n_energies)) return rc;
-  const size_t len = sart_energy_scan_len(n_energies);
-  if (int rc = c->d_escan.reserve(len)) return rc;
-  sart_trace_params_t q = *p;
-  q.accumulate = 0;   // the blocking form has no accumulator the caller could add into
-  if (int rc = sart_trace_energy_scan_device(c, &q, energies, n_energies, c->d_escan.p)) return rc;
-  const double* src = c->d_escan.p;
-  if (c->accum_mode == SART_ACCUM_FIXED64) {
-    if (int rc = c->d_escan_fin.reserve(len)) return rc;
-    if (int rc = sart_finalize_energy_scan_device(c, p, energies, n_energies, c->d_escan.p, c->d_escan_fin.p)) return rc;
-    src = c->d_escan_fin.p;
-  }
-  SART_HIP(hipMemcpyAsync(out_host, src, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  SART_HIP(hipStreamSynchronize(c->stream));
-  return status_take(c);
+  return blocking_rows(
+      c, p, sart_energy_scan_len(n_energies),
+      [&](const sart_trace_params_t* q, double* dev) { return sart_trace_energy_scan_device(c, q, energies, n_energies, dev); },
+      [&](const double* raw, double* fin) { return sart_finalize_energy_scan_device(c, p, energies, n_energies, raw, fin); }, out_host);
 }
 
 // ---- fused angular scan (include/sart.h) ---------------------------------------------------------------------------------------
@@ -3502,26 +3500,16 @@ int ascan_launch(sart_context* c, const sart_trace_params_t* p, TraceArgs a, con
   // sampled, stashed or turned.
   HotA hot = c->hot;
   hot.rotated = 1;
-  int& bpc = c->blocks_per_cu_ascan[images ? 1 : 0][fast ? 1 : 0];
-  if (bpc == 0) {
-    bpc = std::max(1, angular_scan_blocks_per_cu(images, fast));
-    if (c->knobs.hist_blocks_per_cu > 0) bpc = c->knobs.hist_blocks_per_cu;
-  }
+  const int bpc = cached_blocks_per_cu(c, c->blocks_per_cu_ascan[images ? 1 : 0][fast ? 1 : 0], [&] { return angular_scan_blocks_per_cu(images, fast); });
   const int32_t n_groups = (n_angles + kAScanMaxAngles - 1) / kAScanMaxAngles;
   a.partials = nullptr;
-  for (uint64_t done = 0; done < p->n_rays;) {   // ray indices inside one launch are 32-bit: pieces of at most 2^31 rays
-    const uint64_t n = std::min<uint64_t>(p->n_rays - done, 1ull << 31);
+  return for_each_piece(p, 1ull << 31, [&](uint64_t n, uint64_t ray_id_offset) {   // ray indices inside one launch are 32-bit
     a.n_rays = n;
-    a.ray_id_offset = p->ray_id_offset + done;
+    a.ray_id_offset = ray_id_offset;
     const int n_blocks = grid_for(n, c->n_cu, bpc, 1024);
-    if (c->d_ascan_partials.n < static_cast<size_t>(n_blocks) * kAScanMaxAngles * kAScanPartialSlots ||
-        (images && c->d_aimg_partials.n < static_cast<size_t>(n_blocks) * kAScanMaxAngles * SART_ACC_COUNT)) {
-      SART_HIP(hipStreamSynchronize(c->stream));
-      const size_t rows_need = std::max<size_t>(static_cast<size_t>(n_blocks), static_cast<size_t>(c->n_cu) * 4);
-      if (int rc = c->d_ascan_partials.reserve(rows_need * kAScanMaxAngles * kAScanPartialSlots)) return rc;
-      if (images)
-        if (int rc = c->d_aimg_partials.reserve(rows_need * kAScanMaxAngles * SART_ACC_COUNT)) return rc;
-    }
+    if (int rc = grow_partials(c, c->d_ascan_partials, n_blocks, static_cast<size_t>(kAScanMaxAngles) * kAScanPartialSlots)) return rc;
+    if (images)
+      if (int rc = grow_partials(c, c->d_aimg_partials, n_blocks, static_cast<size_t>(kAScanMaxAngles) * SART_ACC_COUNT)) return rc;
     for (int32_t g = 0, k0 = 0; g < n_groups; ++g) {   // balanced groups: sizes differ by at most one
       AScanArgs an;
       std::memset(&an, 0, sizeof an);
@@ -3545,9 +3533,14 @@ int ascan_launch(sart_context* c, const sart_trace_params_t* p, TraceArgs a, con
       SART_HIP(hipGetLastError());
       k0 += an.n_angles;
     }
-    done += n;
-  }
-  return 0;
+    return 0;
+  });
+}
+
+// One quantum for all the angles of a scan: a pure function of setup, tables, flags and headroom (the bound does not depend on the
+// angle).
+int ascan_quanta(const sart_context* c, const sart_trace_params_t* p, QuantaExp& qe) {
+  return quanta_exp_of(c, weight_bound_of(c, p->flags, c->params.gas_dm2_abs), qe);
 }
 
 }  // namespace
@@ -3560,18 +3553,11 @@ int sart_trace_angular_scan_device(sart_context* c, const sart_trace_params_t* p
   SART_HIP(hipSetDevice(c->device));
   if (int rc = refresh_derived(c)) return rc;
   if (int rc = sync_blob(c)) return rc;
-  sart_trace_params_t q = *p;   // a scan accumulates no image: whatever the caller left in the image fields is not read
-  q.image_nx = q.image_ny = 1;
-  q.image_x_min = q.image_y_min = 0.0;
-  q.image_x_max = q.image_y_max = 1.0;
-  q.spectra = 0;
   TraceArgs a;
-  if (int rc = make_args(c, &q, a)) return rc;
-  a.fx_scale_w = a.fx_scale_w2 = 0.0;
-  const bool fixed = c->accum_mode == SART_ACCUM_FIXED64;
-  if (fixed) {   // a pure function of setup, tables, flags and headroom (the bound does not depend on the angle)
+  if (int rc = scan_args(c, p, a)) return rc;
+  if (c->accum_mode == SART_ACCUM_FIXED64) {
     QuantaExp qe;
-    if (int rc = quanta_exp_of(c, weight_bound_of(c, p->flags, c->params.gas_dm2_abs), qe)) return rc;
+    if (int rc = ascan_quanta(c, p, qe)) return rc;
     a.fx_scale_w = std::ldexp(1.0, -qe.w);
     a.fx_scale_w2 = std::ldexp(1.0, -qe.w2);
   }
@@ -3587,43 +3573,24 @@ int sart_finalize_angular_scan_device(sart_context* c, const sart_trace_params_t
   if (int rc = sync_blob(c)) return rc;
   if (int rc = status_ensure(c)) return rc;
   QuantaExp qe;
-  if (int rc = quanta_exp_of(c, weight_bound_of(c, p->flags, c->params.gas_dm2_abs), qe)) return rc;
-  double q_w[kScanMaxMasses], q_w2[kScanMaxMasses];
-  for (int k = 0; k < kScanMaxMasses; ++k) { q_w[k] = std::ldexp(1.0, qe.w); q_w2[k] = std::ldexp(1.0, qe.w2); }
+  if (int rc = ascan_quanta(c, p, qe)) return rc;
   // bit 31: an angle whose few, faint rays the common quantum does not resolve reads NaN in its own row (finalize_scan_kernel)
   constexpr uint32_t kCounters = (1u << SART_ASCAN_N_PASSED) | (1u << SART_ASCAN_N_SHELL_SELECTED) | (1u << SART_ASCAN_N_HIT_NICKEL) |
                                  (1u << SART_ASCAN_N_PASSED_TILL_WINDOW) | (1u << 31);
   static_assert(SART_ASCAN_ROW == SART_SCAN_ROW && SART_ASCAN_SUM_WEIGHTS == SART_SCAN_SUM_WEIGHTS && SART_ASCAN_SUM_WEIGHTS_SQ == SART_SCAN_SUM_WEIGHTS_SQ &&
                     SART_ASCAN_SUM_WEIGHTS_HI == SART_SCAN_SUM_WEIGHTS_HI && SART_ASCAN_SUM_WEIGHTS_SQ_HI == SART_SCAN_SUM_WEIGHTS_SQ_HI &&
                     SART_ASCAN_N_PASSED == SART_SCAN_N_PASSED, "the two scans share the row layout of their sums and the finalize kernel");
-  for (int32_t k0 = 0; k0 < n_angles; k0 += kScanMaxMasses) {
-    const int n = std::min<int32_t>(kScanMaxMasses, n_angles - k0);
-    const size_t off = static_cast<size_t>(k0) * SART_ASCAN_ROW;
-    launch_finalize_scan(static_cast<const long long*>(raw_dev) + off, out_dev + off, n, q_w, q_w2, (k0 + n == n_angles) ? n : -1,
-                         c->d_status.p, c->stream, kCounters);
-    SART_HIP(hipGetLastError());
-  }
-  return status_enqueue_copy(c);
+  return finalize_scan_rows(c, raw_dev, out_dev, n_angles, SART_ASCAN_ROW, kCounters, [qe](int32_t, QuantaExp& q) { q = qe; return 0; });
 }
 
 int sart_trace_angular_scan(sart_context* c, const sart_trace_params_t* p, const double* turned_y_deg, int32_t n_angles, double* out_host) {
   if (int rc = ascan_check(c, p, n_angles)) return rc;
   if (!turned_y_deg || !out_host) return fail(SART_ERR_INVALID_ARGUMENT, "NULL argument");
   SART_HIP(hipSetDevice(c->device));
-  const size_t len = sart_angular_scan_len(n_angles);
-  if (int rc = c->d_scan.resize(len)) return rc;
-  sart_trace_params_t q = *p;
-  q.accumulate = 0;   // the blocking form has no accumulator the caller could add into
-  if (int rc = sart_trace_angular_scan_device(c, &q, turned_y_deg, n_angles, c->d_scan.p)) return rc;
-  const double* src = c->d_scan.p;
-  if (c->accum_mode == SART_ACCUM_FIXED64) {
-    if (int rc = c->d_scan_fin.resize(len)) return rc;
-    if (int rc = sart_finalize_angular_scan_device(c, p, n_angles, c->d_scan.p, c->d_scan_fin.p)) return rc;
-    src = c->d_scan_fin.p;
-  }
-  SART_HIP(hipMemcpyAsync(out_host, src, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  SART_HIP(hipStreamSynchronize(c->stream));
-  return status_take(c);
+  return blocking_rows(
+      c, p, sart_angular_scan_len(n_angles),
+      [&](const sart_trace_params_t* q, double* dev) { return sart_trace_angular_scan_device(c, q, turned_y_deg, n_angles, dev); },
+      [&](const double* raw, double* fin) { return sart_finalize_angular_scan_device(c, p, n_angles, raw, fin); }, out_host);
 }
 
 // ---- fused angular scan with per-angle images (include/sart.h) --------------------------------------------------------------------
@@ -3657,13 +3624,12 @@ int sart_trace_angular_scan_images_device(sart_context* c, const sart_trace_para
   if (fixed) {
     // One quantum for the scan rows and the blocks: the scan's (a function of setup, tables, flags and headroom), frozen like a
     // histogram launch's so that sart_finalize_accumulator_device / sart_rollover_accumulator_device read the blocks with it.
-    const double b = weight_bound_of(c, p->flags, c->params.gas_dm2_abs);
     QuantaExp qe;
-    if (int rc = quanta_exp_of(c, b, qe)) return rc;
+    if (int rc = ascan_quanta(c, p, qe)) return rc;
     if (p->accumulate && c->quanta_frozen && (c->weight_exp != qe.w || c->weight_sq_exp != qe.w2))
       return fail(SART_ERR_INVALID_ARGUMENT, "FIXED64: the quanta frozen for the accumulator are not the scan's (setup, flags or mass "
                                              "changed since its accumulate == 0 launch)");
-    if (int rc = freeze_quanta(c, b, true)) return rc;
+    if (int rc = freeze_quanta(c, weight_bound_of(c, p->flags, c->params.gas_dm2_abs), true)) return rc;
     a.fx_scale_w = std::ldexp(1.0, -qe.w);
     a.fx_scale_w2 = std::ldexp(1.0, -qe.w2);
   }
@@ -3681,26 +3647,24 @@ int sart_trace_angular_scan_images(sart_context* c, const sart_trace_params_t* p
   if (int rc = aimg_check(c, p, turned_y_deg, n_angles, scan_out_host, blocks_out_host)) return rc;
   SART_HIP(hipSetDevice(c->device));
   const size_t len = sart_angular_scan_len(n_angles), block_len = acc_len_of(c, p);
-  if (int rc = c->d_scan.resize(len)) return rc;
-  if (int rc = c->d_aimg.reserve(static_cast<size_t>(n_angles) * block_len)) return rc;
-  sart_trace_params_t q = *p;
-  q.accumulate = 0;   // the blocking form has no accumulator the caller could add into
-  if (int rc = sart_trace_angular_scan_images_device(c, &q, turned_y_deg, n_angles, c->d_scan.p, c->d_aimg.p)) return rc;
-  const double* src = c->d_scan.p;
-  if (c->accum_mode == SART_ACCUM_FIXED64) {   // rows and blocks hold integers: finalize (each block in place, with its own checks)
-    if (int rc = c->d_scan_fin.resize(len)) return rc;
-    if (int rc = sart_finalize_angular_scan_device(c, p, n_angles, c->d_scan.p, c->d_scan_fin.p)) return rc;
-    src = c->d_scan_fin.p;
-    for (int32_t k = 0; k < n_angles; ++k) {
-      double* const blk = c->d_aimg.p + static_cast<size_t>(k) * block_len;
-      if (int rc = sart_finalize_accumulator_device(c, p, blk, blk)) return rc;
-    }
-  }
-  SART_HIP(hipMemcpyAsync(scan_out_host, src, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  SART_HIP(hipMemcpyAsync(blocks_out_host, c->d_aimg.p, static_cast<size_t>(n_angles) * block_len * sizeof(double), hipMemcpyDeviceToHost,
-                          c->stream));
-  SART_HIP(hipStreamSynchronize(c->stream));
-  return status_take(c);
+  return blocking_form(
+      c, p, len, static_cast<size_t>(n_angles) * block_len, true,
+      [&](const sart_trace_params_t* q, double* dev, double* blocks) {
+        return sart_trace_angular_scan_images_device(c, q, turned_y_deg, n_angles, dev, blocks);
+      },
+      [&](const double* raw, double* blocks, double* fin) {   // rows and blocks hold integers: each block in place, with its own checks
+        if (int rc = sart_finalize_angular_scan_device(c, p, n_angles, raw, fin)) return rc;
+        for (int32_t k = 0; k < n_angles; ++k) {
+          double* const blk = blocks + static_cast<size_t>(k) * block_len;
+          if (int rc = sart_finalize_accumulator_device(c, p, blk, blk)) return rc;
+        }
+        return 0;
+      },
+      [&](const double* src, const double* bsrc) {
+        SART_HIP(hipMemcpyAsync(scan_out_host, src, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        SART_HIP(hipMemcpyAsync(blocks_out_host, bsrc, static_cast<size_t>(n_angles) * block_len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        return 0;
+      });
 }
 
 // RCCL through dlopen (the library is only needed by hosts that drive several GPUs from one process).  Types, enum values and the
